@@ -1,8 +1,16 @@
 #!/usr/bin/env python
 """bench.py — points/sec through StratifiedAttention fwd+bwd on a 100k-point scene (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--shard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--shard] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of the headline leg (single_pass.cell below) and prints the line.
+--full adds every other leg and check below (the other single_pass legs, in_flight, roofline, fps, components,
+cpu_baseline, the sharded scene's collective terms); in a --full run the headline leg comes after the operator_api leg.
+--dump-outputs DIR: after the timed steps, what the headline leg's last step computed - per stage s the last block's
+output and its six gradients, the sampler's and the TransitionDown kNN's indices, both patterns' pair lists - as
+DIR/stage<s>_<name>.npy (float32; integer tensors as float64, exact).  An array above 512 KiB is a fixed, seeded sample
+of its rows (the same rows for the same shape).  The inputs are functions of the arguments alone (seeded).
 
 One step = one pass of the hot path over one synthetic S3DIS-like scene of 100 000 points (SURVEY.md 8d;
 stratified_transformer_amd/pipeline.py): for each of the 4 stages of s3dis_stratified_transformer.yaml the index build
@@ -13,7 +21,7 @@ What is timed, and what the line calls it:
   single_pass   K passes one after the other, each complete before the next starts (the unit of SURVEY 8d; `value`):
                   .cell          attention blocks = fused.cell_attention (window-centric kernels, csrc/cell_attn.hip)   <- value
                   .operator_api  attention blocks = the reference's five operators (A1, A2, add, A3, A4), what an
-                                 unmodified model/stratified_transformer.py calls
+                                 unmodified model/stratified_transformer.py calls (--full, as every leg below)
   in_flight     the same K passes with --in-flight L (default 4, fixed) batches in flight: the sampling chains of the
                 next L-1 batches - functions of the coordinates alone - queued ahead; forward+backward of consecutive
                 batches strictly in order (pipeline.passes_in_flight).  A stated throughput configuration, not `value`.
@@ -22,7 +30,7 @@ N > 1 ranks (one process per GPU; `--gpus N` without a launcher starts the N ran
   --shard       ONE scene over the N ranks (queries sharded by pair count, all-gather of k/v rows, reduce-scatter
                 of their gradients, all-reduce of the table gradients over RCCL): "scaling": "strong"
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0, with (--full)
   roofline      the attention kernels of the timed region (the dominant group once FPS is off the critical path; FPS is
                 latency-bound and reported as steps/s in `fps`): SURVEY 8(d)'s algorithmic bytes of every block of a step,
                 summed, over the HIP-event time of those blocks inside the timed region, vs the 8 TB/s HBM peak;
@@ -93,6 +101,49 @@ def no_gc():
             gc.enable()
 
 
+DUMP_ARRAY_BYTES = 512 * 1024  # per array of --dump-outputs: 4 stages x 15 arrays stay below 32 MB
+
+
+def pass_outputs(results, states):
+    """What one pass hands its caller (scene_pass's results, the gradients its blocks leave in the stage states), as host arrays
+    named stage<s>_<name>: float32, integer tensors as float64 (exact).  An array above DUMP_ARRAY_BYTES is a sample of its rows
+    drawn with a fixed seed: the same rows for the same shape."""
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def put(name, t):
+        t = t.detach()
+        dtype = np.dtype(np.float32 if t.is_floating_point() else np.float64)
+        rows = t.shape[0]
+        row_bytes = max(t[0].numel(), 1) * dtype.itemsize if rows else dtype.itemsize
+        keep = max(DUMP_ARRAY_BYTES // row_bytes, 1)
+        if rows > keep:
+            pick = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(pick).to(t.device))
+        arrays[name] = t.cpu().numpy().astype(dtype)
+
+    for r, s in zip(results, states):
+        p = "stage%d_" % r["stage"]
+        put(p + "out", r["out"])
+        for name, t in zip(("grad_q", "grad_k", "grad_v", "grad_table_q", "grad_table_k", "grad_table_v"), (s.q, s.k, s.v) + tuple(s.tables)):
+            put(p + name, t.grad)
+        put(p + "downsample_idx", r["downsample_idx"])
+        if "transition_knn" in r:
+            put(p + "transition_knn", r["transition_knn"])
+        for pattern in ("even", "odd"):
+            for name in ("index_1", "offsets", "rel_idx"):
+                put(p + pattern + "_" + name, getattr(r[pattern], name))
+    return arrays
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as children (torch.distributed.run), before this
     process touches the GPU, and return their exit code (non-zero if any rank fails or does not join)."""
@@ -143,11 +194,12 @@ def run_gpu(args, rank, world):
         """what the report needs of a pass's results (sizes only)"""
         return [dict(stage=r["stage"], n=r["n"], M_even=r["M_even"], M_odd=r["M_odd"]) for r in res]
 
-    def single_pass_leg(fused, overlap=True):
+    def single_pass_leg(fused, overlap=True, keep_outputs=False):
         # A leg keeps NOTHING of its passes but sizes and event timers: with the tensors of an earlier leg's last pass still alive
         # (pair lists, outputs) the next leg's backward kernels ran 45 % slower for the whole leg - 16.6 instead of 14.2 ms per
         # pass at --steps 20 (tools/leg_trace2.py; no device allocations involved: the same kernels on memory the allocator
         # carved differently).  The tensors the parity checks need come from one more pass after all timed legs.
+        # keep_outputs: host copies (sampled) of the last step's outputs, for --dump-outputs
         nonlocal states
         st, res = states, None
         for _ in range(max(args.warmup, 1)):
@@ -167,6 +219,8 @@ def run_gpu(args, rank, world):
             elapsed = max_over_ranks(time.perf_counter() - t0)
         states = st
         leg = dict(elapsed=elapsed, live=live, results=summary(res))
+        if keep_outputs:
+            leg["outputs"] = pass_outputs(res, st)
         leg["host"] = dict(library_calls_per_pass=round((_l.CALLS[0] - calls0) / args.steps, 1),
                            torch_allocations_per_pass=round((torch.cuda.memory_stats(dev).get("allocation.all.allocated", 0) - allocs0) / args.steps, 1))
         if shard:
@@ -175,10 +229,15 @@ def run_gpu(args, rank, world):
         return leg
 
     del results
+    dump = bool(args.dump_outputs) and rank == 0
+    if not args.full:
+        out["single_cell"] = single_pass_leg("cell", keep_outputs=dump)
+        out["speculation"] = dict(pipeline.SPECULATION)
+        return out
     out["single_ops"] = single_pass_leg(False)
     # (sharded scene: operator_api = queries cut by range, all-gather k / v; cell = every world-th cell of the size-sorted list per
     #  rank, all-gather q / k / v, reduce-scatter of the output - sharding.py)
-    out["single_cell"] = single_pass_leg("cell")
+    out["single_cell"] = single_pass_leg("cell", keep_outputs=dump)
     out["speculation"] = dict(pipeline.SPECULATION)
     if not shard:
         out["single_cell_one_stream"] = single_pass_leg("cell", overlap=False)
@@ -538,12 +597,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also every other leg and check (legs, in_flight, roofline, fps, components, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline leg's last-step outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--in-flight", type=int, default=IN_FLIGHT_DEFAULT, help="batches in flight of the in_flight leg (fixed; 1 = skip the leg)")
     ap.add_argument("--shard", action="store_true", help="N > 1: ONE scene sharded over the ranks (SURVEY 8e) instead of one scene per rank")
     ap.add_argument("--shard-mode", choices=("halo", "range"), default="halo",
                     help="halo: rows owned by large window, only boundary rows travel; range: contiguous index ranges, all-gather of every row")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         raise SystemExit(spawn_ranks(args))  # no GPU call has been made in this process
@@ -570,7 +633,7 @@ def main():
             ms = seconds / K * 1e3
             return dict(ms_per_step=round(ms, 3), value=round(N_POINTS * scenes / (ms / 1e3), 1))
 
-        cell, ops = leg(run["single_cell"]["elapsed"]), leg(run["single_ops"]["elapsed"])
+        cell = leg(run["single_cell"]["elapsed"])
         cell["reached_by"] = ("pipeline.scene_pass: the index build and kernels of stratified_transformer_amd.install(fast_layers=True) (index built once per stage, "
                               "fused.cell_attention per block) under the package's own schedule - sampling chain on a side stream beside the blocks, later stages' "
                               "samples taken as the identity prefix while the sampler verifies them; a training loop that calls the package's pass, not the "
@@ -578,9 +641,13 @@ def main():
         cell["speculation"] = run.get("speculation")
         cell["host"] = dict(run["single_cell"]["host"], note="launcher calls of the library (each a handful of kernel launches: ~900 kernels per pass, "
                             "profiles/r03_c_kernel_stats.csv) and caching-allocator allocations per pass; VERDICT r2 #5 asked for <= 120 launches and <= 20 allocations")
-        ops["host"] = run["single_ops"]["host"]
-        ops["reached_by"] = ("the five operators of the drop-in pointops API on a pair list built once per stage (index_build.stage_index_hip): a caller that "
-                             "owns its BasicLayer but keeps the reference's operators")
+        single = {"cell": cell}
+        if "single_ops" in run:
+            ops = leg(run["single_ops"]["elapsed"])
+            ops["host"] = run["single_ops"]["host"]
+            ops["reached_by"] = ("the five operators of the drop-in pointops API on a pair list built once per stage (index_build.stage_index_hip): a caller "
+                                 "that owns its BasicLayer but keeps the reference's operators")
+            single["operator_api"] = ops
         extra_legs = {}
         if "single_model" in run:
             extra_legs["model_call_order"] = dict(
@@ -612,7 +679,6 @@ def main():
             extra_legs["cell_forward_only"] = dict(leg(run["single_fwd"]["elapsed"]), note="BASELINE config 2: the same pass without the blocks' backward")
             extra_legs["cell_bf16_storage"] = dict(leg(run["single_bf16"]["elapsed"]), note="BASELINE config 3, second leg: q / k / v / tables stored as bf16, "
                                                    "fp32 arithmetic, outputs and gradient sums (an extension: the reference's operators are fp32-only)")
-        comp = component_table(run["timer"], K)
         line = {
             "metric": "points/sec through StratifiedAttention fwd+bwd, 100k-pt scene",
             "value": cell["value"], "unit": "points/s",
@@ -622,18 +688,22 @@ def main():
                                    "s3dis_stratified_transformer.yaml stages w=[.16,.32,.64,1.28] C=[48,96,192,384] h=[3,6,12,24] depths=[2,2,6,2]; "
                                    "unit = index build + FPS + depth x attention block fwd+bwd + TransitionDown FPS/kNN16 + Upsample kNN3 per stage; "
                                    "value = single_pass.%s" % ("sharded over the ranks" if sharded else "per GPU", "cell (sharded)" if sharded else "cell"),
-                       "points_per_scene": N_POINTS, "stages": step_attention_bytes(run["cfg"], run["results"])[1],
+                       "points_per_scene": N_POINTS, "stages": step_attention_bytes(run["cfg"], run["single_cell"]["results"])[1],
                        "parallelism": ("1 scene over %d ranks: cells dealt to the ranks by size order, all-gather q/k/v, reduce-scatter out and dq/dk/dv, all-reduce table grads "
                                        "(operator_api: queries sharded by pair count, all-gather k/v, reduce-scatter dk/dv)" % world)
                        if sharded else "1 scene per rank, no data-path collective"},
-            "single_pass": {"cell": cell, "operator_api": ops, **extra_legs,
+            "single_pass": {**single, **extra_legs,
                             "note": "K passes, each complete before the next starts; every leg says how a user of the reference reaches it (reached_by)"},
-            "roofline": attention_roofline(run["single_cell"], run, K, "cell"),
-            "roofline_operator_api": attention_roofline(run["single_ops"], run, K, "operator_api"),
-            "fps": fps_report(run["single_cell"], run, K, run["xyz"], run["offset"]),
-            "components_ms_per_step": {k: round(v["ms_per_step"], 3) for k, v in sorted(comp.items())},
-            "components_note": "per-op device times of passes repeated with events around every op (cell attention); chains overlap in wall time",
         }
+        if args.full:
+            comp = component_table(run["timer"], K)
+            line.update({
+                "roofline": attention_roofline(run["single_cell"], run, K, "cell"),
+                "roofline_operator_api": attention_roofline(run["single_ops"], run, K, "operator_api"),
+                "fps": fps_report(run["single_cell"], run, K, run["xyz"], run["offset"]),
+                "components_ms_per_step": {k: round(v["ms_per_step"], 3) for k, v in sorted(comp.items())},
+                "components_note": "per-op device times of passes repeated with events around every op (cell attention); chains overlap in wall time",
+            })
         if "inflight_cell" in run:
             line["in_flight"] = {"batches_in_flight": args.in_flight, "cell": leg(run["inflight_cell"]), "operator_api": leg(run["inflight_ops"]),
                                  "same_results_as_single_pass": run["inflight_same"],
@@ -641,7 +711,7 @@ def main():
                                          "queued ahead, forward+backward of consecutive batches strictly in order; a throughput configuration for a "
                                          "training loop that owns its data-side prefetch, not reachable by the unmodified model file; GPU_MAX_HW_QUEUES=%s"
                                          % os.environ.get("GPU_MAX_HW_QUEUES", "default")}
-        if sharded:
+        if sharded and args.full:
             live = component_table(run["single_cell"]["live"], K)
             line["collective_ms"] = round(sum(v["ms_per_step"] for k, v in live.items() if k.startswith("comm/")), 3)
             # what does NOT shrink with the rank count (every rank samples and builds the whole index) and what travels: the
@@ -651,10 +721,12 @@ def main():
                                                  "operator_api": int(run["single_ops"].get("bytes_moved", 0) // K)}
             line["shard_mode"] = args.shard_mode
             line["halo_fraction_per_stage_even_odd"] = run["single_cell"].get("halo_fraction")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base = cpu_baseline(run)
             line["cpu_baseline"] = base
             line["gpu_over_cpu"] = round(line["value"] / base["value"], 2)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, run["single_cell"]["outputs"])
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.barrier()
