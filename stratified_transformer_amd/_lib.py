@@ -10,7 +10,7 @@ import subprocess
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("P2_LIB_PATH") or os.path.join(_HERE, "lib", "libpointops2_hip.so")  # (P2_LIB_PATH: kernel experiments)
+LIB_PATH = os.path.join(_HERE, "lib", "libpointops2_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 _lib = None
 

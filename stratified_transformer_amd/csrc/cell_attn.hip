@@ -27,9 +27,6 @@
 
 namespace p2 {
 
-#ifdef CA_TRACE
-__device__ unsigned long long ca_trace[3 * 1024];
-#endif
 
 // ---- storage type of q / k / v / tables: fp32, or bf16 (BASELINE config 3's second leg: bf16 storage, fp32 arithmetic;
 // the reference's operators are fp32-only, stratified_transformer.py:183,194,208 `.float()`) ----
@@ -301,9 +298,6 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
     __syncthreads();
     const int nC = share_count(pl, pl.counts[0]);
     float *pb = pbuf + (size_t)x.head * plane;
-#ifdef CA_TRACE  // diagnostic build (tools/interference.py): when and where every workgroup of the forward kernel ran
-    const unsigned long long tr_t0 = wall_clock64();
-#endif
     const int slots = gridDim.x * CA_WAVES, slot = blockIdx.x * CA_WAVES + wave;
     for (int round = 0; round * slots < nC; round++) {
         const int task = snake_task(round, slot, slots);
@@ -322,26 +316,13 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
                 fwd_sweep_logits<decltype(tag)::value, TS, T>(x, ct, cb, rs_p, q, k, ml, ch, nch == 1, j0, nkc);
             });
         }
-#ifndef CA_SKIP_SWEEP2
         for (int ch = 0; ch < nch; ch++) {  // sweep 2: out = sum p (v + Tv)
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
                 fwd_sweep_values<decltype(tag)::value, TS, T>(x, ct, cb, rs_p, v, ml, out, ch, nch == 1, j0, nkc);
             });
         }
-#endif
     }
-#ifdef CA_TRACE
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-        if (wg < 1024) {
-            ca_trace[wg * 3 + 0] = tr_t0;
-            ca_trace[wg * 3 + 1] = wall_clock64();
-            ca_trace[wg * 3 + 2] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);  // HW_ID, XCC_ID
-        }
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -360,9 +341,7 @@ __device__ __forceinline__ void flush_key_pass(float *scr, float4 acc, rsrc_t rs
         const int s = (x.lane >> 4) + 4 * kk;
         const int jl = s * NPA + t;
         const int key = (int)bload_u32(rs_key, (j0 + jl) * 4);
-#ifndef CA_SKIP_FLUSH  // (experiment: what the dK / dV atomics cost)
         if (jl < nkc) unsafeAtomicAdd(grad + (size_t)key * x.C + x.head * 16 + (x.lane & 15), scr[s * 16 + (x.lane & 15)]);
-#endif
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
@@ -571,10 +550,7 @@ __device__ __forceinline__ CFixScale c_row_scale(unsigned maxbits, int n) {
     return sc;
 }
 
-#ifndef CT_WAVES_OVERRIDE
-#define CT_WAVES_OVERRIDE 8  // (12 in round 2; with the grid below 8 measured 5 % less backward time per step: tools/bench_cell.py, round 3)
-#endif
-constexpr int CT_WAVES = CT_WAVES_OVERRIDE;
+constexpr int CT_WAVES = 8;  // (12 in round 2; with the grid below 8 measured 5 % less backward time per step: tools/bench_cell.py, round 3)
 
 template <int TA>
 struct CellTableGeo {
@@ -740,13 +716,6 @@ __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &
     }
 }
 
-template <int TA, bool BYKEY, typename XT>
-__global__ __launch_bounds__(CT_WAVES * 64) void cell_table_grad_kernel(pointops2_cell_plan pl, int h, int L, const float *__restrict__ wbuf,
-                                                                        size_t plane, const XT *__restrict__ X,
-                                                                        float *__restrict__ grad_table) {
-    cell_table_grad_body<TA, BYKEY, XT>(pl, h, L, wbuf, plane, X, grad_table);
-}
-
 // the three table gradients of a block as ONE grid (blockIdx.z: 0 = key side, the longest, first in dispatch order; 1 = query side;
 // 2 = value side): each of them alone is short of independent work on the small stages, together they overlap
 template <int TA, typename T>
@@ -760,13 +729,6 @@ __global__ __launch_bounds__(CT_WAVES * 64) void cell_table_grad3_kernel(pointop
     else cell_table_grad_body<TA, false, float>(pl, h, L, pbuf, plane, grad_out, gtv);
 }
 
-static int device_cus() { return num_cus(); }
-#ifdef CA_TRACE
-} // namespace p2
-extern "C" void pointops2_diag_read_cell_trace(unsigned long long *host) { (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(p2::ca_trace), sizeof(unsigned long long) * 3 * 1024); }
-namespace p2 {
-#endif
-
 template <typename T>
 static void launch_cell_fwd(const pointops2_cell_plan *plan, int h, int hdim, int L, const T *q, const T *k, const T *v, const T *table_q,
                             const T *table_k, const T *table_v, float *out, float *ml, float *pbuf) {
@@ -776,7 +738,7 @@ static void launch_cell_fwd(const pointops2_cell_plan *plan, int h, int hdim, in
     // relp's indices were clamped to [0, plan->table_rows) and L is the axis stride of the LDS table image
     if (L != plan->table_rows) { set_error("cell_attention: the tables' row count differs from the plan's table_rows"); return; }
     if constexpr (std::is_same<T, float>::value) {
-        // the matrix-core forward (cell_attn_mfma.hip); P2_CELL_MFMA=0 keeps the VALU walkers below
+        // the matrix-core forward (cell_attn_mfma.hip) where it was measured faster than the VALU walkers below
         if (cell_fwd_mfma_launch(plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf)) {
             check_launch();
             return;
@@ -815,8 +777,7 @@ static void launch_cell_bwd(const pointops2_cell_plan *plan, int h, int hdim, in
     const size_t lds = TabGeo<80>::bytes(sizeof(T)) + (size_t)CA_WAVES_BWD * 256 * sizeof(float);
     allow_big_lds(cell_bwd_kernel<CA_NP_BWD, 80, T>, lds);
     const size_t plane = (size_t)plan->n_pairs;
-    static const int cb_div = getenv("P2_CB_DIV") ? atoi(getenv("P2_CB_DIV")) : 1;
-    hipLaunchKernelGGL((cell_bwd_kernel<CA_NP_BWD, 80, T>), dim3(std::max(1, cell_grid_x(1, plan->n_cells, h, CA_WAVES_BWD) / cb_div), h),
+    hipLaunchKernelGGL((cell_bwd_kernel<CA_NP_BWD, 80, T>), dim3(cell_grid_x(1, plan->n_cells, h, CA_WAVES_BWD), h),
                        dim3(CA_WAVES_BWD * 64), lds, st, *plan, h, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, plane, grad_q,
                        grad_k, grad_v);
     // the three table gradients read p / gs only
@@ -825,34 +786,14 @@ static void launch_cell_bwd(const pointops2_cell_plan *plan, int h, int hdim, in
     // pattern), stage 1 512 -> 448 -> 433 / 505 -> 452 -> 423, stage 2 381 -> 345 -> 304 / 361 -> 302 -> 292, stage 3 317 -> 301 -> 303 /
     // 265 -> 223 -> 212: every workgroup pays a fixed zero-fill, a 12-round reduction through LDS and a 3 072-float atomic flush per body, and
     // the bodies are latency-bound - more resident workgroups only add to both.  (Halving the grids of cell_fwd / cell_bwd the same way
-    // costs 40-70 %: those are bound by resident waves.)  P2_CT_PER_CU / P2_CT_DIV override.
-    static const int ct_per_cu = getenv("P2_CT_PER_CU") ? atoi(getenv("P2_CT_PER_CU")) : 1;
-    static const int ct_div_env = getenv("P2_CT_DIV") ? atoi(getenv("P2_CT_DIV")) : 0;
-    const int ct_div = ct_div_env > 0 ? ct_div_env : 1;  // (with 12 waves per workgroup, halving the grid on the smaller stages paid; with 8 it does not)
-    const int gx_t = std::max(1, cell_grid_x(ct_per_cu, plan->n_cells, h, CT_WAVES) / ct_div);
-    const dim3 tgrid(gx_t, h), tblock(CT_WAVES * 64);
-    // one grid for the three (P2_CELL_TABLE3=0: three launches in a row): backward of a block 10-120 us shorter, most on the small stages
-    static const bool one_grid = getenv("P2_CELL_TABLE3") == nullptr || atoi(getenv("P2_CELL_TABLE3")) != 0;
-    if (one_grid) {
-        const dim3 grid3(gx_t, h, 3);
-        if (L <= 64) hipLaunchKernelGGL((cell_table_grad3_kernel<4, T>), grid3, tblock, CellTableGeo<4>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
-                                        grad_table_q, grad_table_k, grad_table_v);
-        else hipLaunchKernelGGL((cell_table_grad3_kernel<5, T>), grid3, tblock, CellTableGeo<5>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
-                                grad_table_q, grad_table_k, grad_table_v);
-        check_launch();
-        return;
-    }
-    if (L <= 64) {
-        using G = CellTableGeo<4>;
-        hipLaunchKernelGGL((cell_table_grad_kernel<4, false, T>), tgrid, tblock, G::lds_bytes(), st, *plan, h, L, gsbuf, plane, q, grad_table_q);
-        hipLaunchKernelGGL((cell_table_grad_kernel<4, false, float>), tgrid, tblock, G::lds_bytes(), st, *plan, h, L, pbuf, plane, grad_out, grad_table_v);
-        hipLaunchKernelGGL((cell_table_grad_kernel<4, true, T>), tgrid, tblock, G::lds_bytes(), st, *plan, h, L, gsbuf, plane, k, grad_table_k);
-    } else {
-        using G = CellTableGeo<5>;
-        hipLaunchKernelGGL((cell_table_grad_kernel<5, false, T>), tgrid, tblock, G::lds_bytes(), st, *plan, h, L, gsbuf, plane, q, grad_table_q);
-        hipLaunchKernelGGL((cell_table_grad_kernel<5, false, float>), tgrid, tblock, G::lds_bytes(), st, *plan, h, L, pbuf, plane, grad_out, grad_table_v);
-        hipLaunchKernelGGL((cell_table_grad_kernel<5, true, T>), tgrid, tblock, G::lds_bytes(), st, *plan, h, L, gsbuf, plane, k, grad_table_k);
-    }
+    // costs 40-70 %: those are bound by resident waves.  With 12 waves per workgroup, halving the grid on the smaller stages paid; with 8
+    // it does not.)  The three as ONE grid rather than three launches in a row: backward of a block 10-120 us shorter, most on the small
+    // stages.
+    const dim3 grid3(cell_grid_x(1, plan->n_cells, h, CT_WAVES), h, 3), tblock(CT_WAVES * 64);
+    if (L <= 64) hipLaunchKernelGGL((cell_table_grad3_kernel<4, T>), grid3, tblock, CellTableGeo<4>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
+                                    grad_table_q, grad_table_k, grad_table_v);
+    else hipLaunchKernelGGL((cell_table_grad3_kernel<5, T>), grid3, tblock, CellTableGeo<5>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
+                            grad_table_q, grad_table_k, grad_table_v);
     check_launch();
 }
 

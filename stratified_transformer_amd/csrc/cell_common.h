@@ -3,25 +3,15 @@
 #pragma once
 #include "rpe_common.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace p2 {
 
 typedef float __attribute__((ext_vector_type(4))) f32x4c;
 
-#ifndef CA_NP_OVERRIDE
-#define CA_NP_OVERRIDE 8
-#endif
-constexpr int CA_NP = CA_NP_OVERRIDE;  // forward: passes of 16 keys a lane keeps in registers (128 keys per chunk)
+constexpr int CA_NP = 8;  // forward: passes of 16 keys a lane keeps in registers (128 keys per chunk)
 constexpr int CA_NP_BWD = 3;  // backward: 48 keys per chunk (key rows AND their gradient accumulators in registers; chunks simply add up)
-#ifndef CA_WAVES_OVERRIDE
-#define CA_WAVES_OVERRIDE 12
-#endif
-constexpr int CA_WAVES = CA_WAVES_OVERRIDE;  // waves per workgroup (one head's three tables in LDS per workgroup)
-#ifndef CA_WAVES_BWD_OVERRIDE
-#define CA_WAVES_BWD_OVERRIDE 12
-#endif
-constexpr int CA_WAVES_BWD = CA_WAVES_BWD_OVERRIDE;  // backward workgroup
+constexpr int CA_WAVES = 12;  // waves per workgroup (one head's three tables in LDS per workgroup)
+constexpr int CA_WAVES_BWD = 12;  // backward workgroup
 
 // ---- cross-lane sums without LDS round trips where the hardware has a lane network for it ----
 template <int CTRL>
@@ -155,7 +145,8 @@ __device__ __forceinline__ int share_task(const pointops2_cell_plan &pl, int i) 
 
 // Persistent grid of the cell walkers: `per_cu` workgroups for every CU that is FREE, over all heads; never more waves than
 // tasks.  Tasks are dealt by position, so a workgroup that has to wait for a CU serves its whole share late and the kernel
-// takes twice as long (tools/cell_trace.py: 16 CUs held -> 31 of 255 workgroups start when the others finish).  The one
+// takes twice as long (measured with a workgroup-trace build, since removed: 16 CUs held -> 31 of 255 workgroups start when the others
+// finish).  The one
 // long-running kernel of this library is the round sampler (16 workgroups per cloud for milliseconds): its launches are noted
 // (common.h, held_cus_*), and while any of them has not finished the grid leaves its shader engines room: workgroups go to
 // the 32 shader engines (8 CUs each) in turn, so one CU per engine is left out (usable_cus(), common.h).  Measured, stage-0

@@ -25,7 +25,6 @@
 // One workgroup per batch element (as the reference): no cross-workgroup synchronisation at all.
 #include "fps_common.h"
 #include <hipcub/hipcub.hpp>
-#include <cstdio>
 #include <cstdlib>
 
 namespace p2 {
@@ -348,20 +347,13 @@ __device__ __forceinline__ KeyMax wave_key_max_bf(unsigned long long v) {
     return r;
 }
 
-// STAMP: diagnostic build only (P2_FPS_STAMPS=1): per-wave cycle sums of the step phases -> dbg; P2_FPS_TRACE=file
-// also dumps the absolute phase times of every wave for FPS_TRACE_STEPS steps (tools/fps_trace.py)
-constexpr int FPS_TRACE_STEPS = 512;
-template <int NBL, int NW, bool STAMP = false, bool B64 = false>
+template <int NBL, int NW, bool B64>
 __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B, int BSZ_arg, const float *__restrict__ xyz,
                                                              const int *__restrict__ offset, const int *__restrict__ new_offset,
                                                              float4 *__restrict__ pts, const unsigned *__restrict__ rank,
                                                              const int *__restrict__ prev_idx, const int *__restrict__ prev_offset,
-                                                             const int *__restrict__ verified, int *__restrict__ idx,
-                                                             unsigned long long *__restrict__ dbg = nullptr) {
+                                                             const int *__restrict__ verified, int *__restrict__ idx) {
     constexpr int NT = NW * 64;
-    unsigned long long c_test = 0, c_red = 0, c_bar = 0, c_fin = 0, n_upd = 0, t_a = 0, t_b = 0;
-    unsigned long long rt0 = 0, ct0 = 0;
-    if (STAMP) { rt0 = __builtin_amdgcn_s_memrealtime(); ct0 = __builtin_amdgcn_s_memtime(); }
     __shared__ unsigned long long wkey[2][NW];
     __shared__ float4 wbest[2][NW];
 
@@ -448,7 +440,7 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B
 
     // The owner lane (code & 63) of slot code >> 6 takes the bucket's new key and best point.  With 64-point buckets
     // this is five v_writelane_b32 (lane select in m0) under a wave-uniform slot test; the generic form masks lanes.
-    // (On the step's critical path an instruction costs ~9 cycles, tools/fps_trace.py: count them.)
+    // (On the step's critical path an instruction costs ~9 cycles - measured with a phase-stamp build, since removed: count them.)
     auto update_regs = [&](int code, const KeyMax &km, float cx, float cy, float cz) {
         if (BSZ == 64) {
             const int ol = __builtin_amdgcn_readfirstlane(code & 63);
@@ -481,11 +473,6 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B
     };
 
     for (int j = start_m + max(done, 1); j < end_m; j++) {
-        const bool trace = STAMP && dbg && (j - start_m) >= 5000 && (j - start_m) < 5000 + FPS_TRACE_STEPS;
-        unsigned long long *tr = nullptr;
-        if (trace) tr = dbg + 16 * 8 + ((size_t)(j - start_m - 5000) * NW + wave) * 8;
-        if (STAMP) t_a = __builtin_amdgcn_s_memtime();
-        if (trace && lane == 0) tr[0] = t_a;
         unsigned long long hm[NBL];
         unsigned long long any = 0ull;
         int ntouched = 0;
@@ -498,8 +485,6 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B
             any |= hm[s];
             ntouched += __popcll(hm[s]);
         }
-        if (STAMP) n_upd += ntouched;
-        if (trace && lane == 0) { tr[1] = __builtin_amdgcn_s_memtime(); tr[7] = ntouched; }
         if (ntouched == 1 && BSZ == 64) {
             // the common case: exactly one owned bucket to update, straight-line
             int code = -1;
@@ -644,8 +629,6 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B
                 }
             }
         }
-        if (STAMP) { t_b = __builtin_amdgcn_s_memtime(); c_test += t_b - t_a; t_a = t_b; }
-        if (trace && lane == 0) tr[2] = t_b;
         if (recompute) {  // wave-uniform
             unsigned long long mk = key[0];
             float mx_ = bx[0], my_ = by[0], mz_ = bz[0];
@@ -663,12 +646,8 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B
                 wbest[0][wave] = make_float4(wx, wy, wz, 0.f);
             }
         }
-        if (STAMP) { t_b = __builtin_amdgcn_s_memtime(); c_red += t_b - t_a; t_a = t_b; }
-        if (trace && lane == 0) tr[3] = t_b;
         lds_barrier();  // every wave's slot is current
         unsigned long long win_key = 0ull;
-        if (STAMP) { t_b = __builtin_amdgcn_s_memtime(); c_bar += t_b - t_a; t_a = t_b; }
-        if (trace && lane == 0) tr[4] = t_b;
         if (wave == 0) {
             // arg-max over the NW slots (one wave, so the others do not compete for issue slots)
             const int src = lane < NW ? lane : 0;
@@ -693,7 +672,6 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B
             if (lane == 0) wbest[1][0] = make_float4(rl(gc.x, gm.lane), rl(gc.y, gm.lane), rl(gc.z, gm.lane), 0.f);
             win_key = gm.key;
         }
-        if (trace && lane == 0) tr[5] = __builtin_amdgcn_s_memtime();
         lds_barrier();  // the new sample is published
         {
             const float4 ns = wbest[1][0];
@@ -702,14 +680,20 @@ __global__ __launch_bounds__(NW * 64) void fps_bucket_kernel(int Bref, int log2B
         // the sample's index (key -> position, a dozen instructions and a store) is nobody's input: it is written
         // behind the barrier, off the path the 15 other waves wait on
         if (wave == 0 && lane == 0) idx[j] = start_n + rel_of(win_key, Bref, log2B);
-        if (STAMP) { t_b = __builtin_amdgcn_s_memtime(); c_fin += t_b - t_a; }
-        if (trace && lane == 0) tr[6] = t_b;
     }
-    if (STAMP && dbg && lane == 0) {
-        unsigned long long *o = dbg + (blockIdx.x * NW + wave) * 8;
-        o[0] = c_test; o[1] = 0; o[2] = c_red; o[3] = c_bar; o[4] = c_fin; o[5] = n_upd;
-        o[6] = __builtin_amdgcn_s_memtime() - ct0; o[7] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
+}
+
+// the step-by-step kernel, 16 waves per workgroup: NBL owned buckets per lane, 64-point buckets a compile-time fact
+constexpr int FPS_NW = 16;
+template <int NBL>
+static void fps_stepwise_launch(int b, int Bref, int log2B, int BSZ, const float *xyz, const int *offset, const int *new_offset, float4 *pts,
+                                const unsigned *rank, const int *prev_idx, const int *prev_offset, const int *verified, int *idx, hipStream_t st) {
+    if (BSZ == 64)
+        hipLaunchKernelGGL((fps_bucket_kernel<NBL, FPS_NW, true>), dim3(b), dim3(FPS_NW * 64), 0, st, Bref, log2B, BSZ, xyz, offset, new_offset, pts,
+                           rank, prev_idx, prev_offset, verified, idx);
+    else
+        hipLaunchKernelGGL((fps_bucket_kernel<NBL, FPS_NW, false>), dim3(b), dim3(FPS_NW * 64), 0, st, Bref, log2B, BSZ, xyz, offset, new_offset, pts,
+                           rank, prev_idx, prev_offset, verified, idx);
 }
 
 static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -718,7 +702,7 @@ static int bits_for(int b) {
     while ((1 << r) < b) r++;
     return r;
 }
-constexpr int FPS_HEAD_MAX = 4096;  // samples of a cloud the round sampler may leave to the step-by-step kernel (P2_FPS_HEAD)
+constexpr int FPS_HEAD = 256;  // samples of a fresh chain the round sampler leaves to the step-by-step kernel (fps_bucket_launch)
 
 static size_t fps_cub_bytes(int b, int N) {
     size_t bytes = 0;
@@ -772,7 +756,7 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
     int *first_bad = (int *)p; p += al((size_t)b * 4);
     void *xchg = p; p += al((size_t)b * LZ_XCHG);                  // where the round sampler's workgroups meet (fps_lazy.hip)
     int *head_offset = (int *)p; p += al((size_t)b * 4);            // the chain's head, sampled step by step (below)
-    int *head_idx = (int *)p; p += al((size_t)b * FPS_HEAD_MAX * 4);
+    int *head_idx = (int *)p; p += al((size_t)b * FPS_HEAD * 4);
     void *cub_tmp = p;
     size_t cub_bytes = w.bytes - (size_t)(p - reinterpret_cast<char *>(w.ptr));
     FpsResume rs = fps_resume();
@@ -786,9 +770,8 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
         hipLaunchKernelGGL(fps_gather_kernel, dim3(div_up(N_total, 256)), dim3(256), 0, st, N_total, b, Bref, log2B, xyz, offset, sorig, pts, rank, inv);
     }
     // identity-prefix verification (exact; see above): a cheap probe of the first 64 steps, then everything
-    static const bool no_verify = getenv("P2_FPS_NO_VERIFY") != nullptr;
     const int *verified = nullptr;
-    if (!no_verify && !rs.unordered) {
+    if (!rs.unordered) {
         hipLaunchKernelGGL(fps_verify_init_kernel, dim3(div_up(b, 64)), dim3(64), 0, st, b, offset, new_offset, first_bad);
         hipLaunchKernelGGL(fps_verify_threshold_kernel, dim3(1, b), dim3(VER_T), 0, st, Bref, log2B, 1, xyz, offset, new_offset, first_bad, thr);
         hipLaunchKernelGGL(fps_verify_scan_kernel, dim3(div_up(n, VER_P), b), dim3(VER_T), 0, st, Bref, log2B, 1, 64, xyz, offset, new_offset, thr, first_bad);
@@ -799,41 +782,21 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
     }
     const int BSZ = 64 * div_up(n, 64 * FPS_MAX_BUCKETS);
     const int nbuckets = div_up(n, BSZ);
-    static const int nw_env = getenv("P2_FPS_WAVES") ? atoi(getenv("P2_FPS_WAVES")) : 0;
-    const int NWsel = nw_env == 8 ? 8 : 16;
-    const int per_lane = div_up(nbuckets, NWsel * 64);
-#define P2_FPS_LAUNCH(NBL_, NW_, STAMP_, DBG_, NEWOFF_, PIDX_, POFF_, IDX_)                                                 \
-    do {                                                                                                                    \
-        if (BSZ == 64)                                                                                                      \
-            hipLaunchKernelGGL((fps_bucket_kernel<NBL_, NW_, STAMP_, true>), dim3(b), dim3(NW_ * 64), 0, st, Bref, log2B, BSZ, xyz, \
-                               offset, NEWOFF_, pts, rank, PIDX_, POFF_, verified, IDX_, DBG_);                             \
-        else                                                                                                                \
-            hipLaunchKernelGGL((fps_bucket_kernel<NBL_, NW_, STAMP_, false>), dim3(b), dim3(NW_ * 64), 0, st, Bref, log2B, BSZ, xyz, \
-                               offset, NEWOFF_, pts, rank, PIDX_, POFF_, verified, IDX_, DBG_);                             \
-    } while (0)
-#define P2_FPS_STEPWISE(NEWOFF_, PIDX_, POFF_, IDX_)                                                                       \
-    do {                                                                                                                    \
-        if (NWsel == 8) {                                                                                                   \
-            if (per_lane <= 1) P2_FPS_LAUNCH(1, 8, false, nullptr, NEWOFF_, PIDX_, POFF_, IDX_);                            \
-            else if (per_lane <= 2) P2_FPS_LAUNCH(2, 8, false, nullptr, NEWOFF_, PIDX_, POFF_, IDX_);                       \
-            else P2_FPS_LAUNCH(4, 8, false, nullptr, NEWOFF_, PIDX_, POFF_, IDX_);                                          \
-        } else {                                                                                                            \
-            if (per_lane <= 1) P2_FPS_LAUNCH(1, 16, false, nullptr, NEWOFF_, PIDX_, POFF_, IDX_);                           \
-            else P2_FPS_LAUNCH(2, 16, false, nullptr, NEWOFF_, PIDX_, POFF_, IDX_);                                         \
-        }                                                                                                                   \
-    } while (0)
+    const int per_lane = div_up(nbuckets, FPS_NW * 64);
+    auto step_by_step = [&](const int *noff, const int *pidx, const int *poff, int *out) {
+        if (per_lane <= 1) fps_stepwise_launch<1>(b, Bref, log2B, BSZ, xyz, offset, noff, pts, rank, pidx, poff, verified, out, st);
+        else fps_stepwise_launch<2>(b, Bref, log2B, BSZ, xyz, offset, noff, pts, rank, pidx, poff, verified, out, st);
+    };
     // Round-based sampler (fps_lazy.hip) on the same state; P2_FPS_STEPWISE=1 keeps the step-by-step kernel.  The first few
     // hundred samples of a fresh chain interact so strongly that a round decides one or two of them (and a round costs what
     // ~30 dependent steps cost): the HEAD of the chain is therefore sampled step by step and the rounds resume from it -
     // same state conventions, same sequence.
     static const bool stepwise = getenv("P2_FPS_STEPWISE") != nullptr;
     if (!stepwise && fps_lazy_groups(n) > 0) {
-        static const int head_env = getenv("P2_FPS_HEAD") ? atoi(getenv("P2_FPS_HEAD")) : 256;
-        const int head = std::min(std::max(head_env, 0), FPS_HEAD_MAX);
         const int *pidx = rs.prev_idx, *poff = rs.prev_offset;
-        if (pidx == nullptr && head > 0 && n >= 8192) {
-            hipLaunchKernelGGL(fps_head_offsets_kernel, dim3(1), dim3(64), 0, st, b, head, new_offset, head_offset);
-            P2_FPS_STEPWISE(head_offset, (const int *)nullptr, (const int *)nullptr, head_idx);
+        if (pidx == nullptr && n >= 8192) {
+            hipLaunchKernelGGL(fps_head_offsets_kernel, dim3(1), dim3(64), 0, st, b, FPS_HEAD, new_offset, head_offset);
+            step_by_step(head_offset, nullptr, nullptr, head_idx);
             held_cus_note(st, b);  // (one workgroup per cloud holds a CU for the head's ~1 ms)
             pidx = head_idx;
             poff = head_offset;
@@ -841,31 +804,8 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
         fps_lazy_launch(b, n, Bref, log2B, xyz, offset, new_offset, pts, rank, pidx, poff, verified, idx, xchg, st);
         return true;
     }
-    if (getenv("P2_FPS_STAMPS") && nbuckets > 1024) {  // diagnostic only: synchronous, prints phase shares to stderr
-        unsigned long long *dbg = nullptr, host[16 * 8];
-        const size_t trace_words = (size_t)FPS_TRACE_STEPS * 16 * 8;
-        (void)hipMalloc(&dbg, (sizeof(host) + trace_words * 8) * b);
-        (void)hipMemset(dbg, 0, (sizeof(host) + trace_words * 8) * b);
-        if (NWsel == 8) P2_FPS_LAUNCH(4, 8, true, dbg, new_offset, rs.prev_idx, rs.prev_offset, idx); else P2_FPS_LAUNCH(2, 16, true, dbg, new_offset, rs.prev_idx, rs.prev_offset, idx);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(host, dbg, sizeof(host), hipMemcpyDeviceToHost);
-        if (const char *tf = getenv("P2_FPS_TRACE")) {
-            unsigned long long *tbuf = (unsigned long long *)malloc(trace_words * 8);
-            (void)hipMemcpy(tbuf, dbg + 16 * 8, trace_words * 8, hipMemcpyDeviceToHost);
-            if (FILE *f = fopen(tf, "wb")) { fwrite(tbuf, 8, trace_words, f); fclose(f); }
-            free(tbuf);
-        }
-        (void)hipFree(dbg);
-        for (int w = 0; w < NWsel; w++)
-            fprintf(stderr, "[fps stamps] wave %2d: test+update %llu reduce %llu barrier %llu final %llu | updates %llu | cycles %llu realtime(100MHz) %llu -> %.0f MHz\n",
-                    w, host[w * 8 + 0], host[w * 8 + 2], host[w * 8 + 3], host[w * 8 + 4], host[w * 8 + 5], host[w * 8 + 6], host[w * 8 + 7],
-                    host[w * 8 + 7] ? 100.0 * host[w * 8 + 6] / host[w * 8 + 7] : 0.0);
-        return true;
-    }
-    P2_FPS_STEPWISE(new_offset, rs.prev_idx, rs.prev_offset, idx);
+    step_by_step(new_offset, rs.prev_idx, rs.prev_offset, idx);
     held_cus_note(st, b);
-#undef P2_FPS_STEPWISE
-#undef P2_FPS_LAUNCH
     return true;
 }
 
@@ -882,7 +822,7 @@ void pointops2_set_workspace(void *ptr, size_t bytes) {
 
 size_t pointops2_fps_workspace_bytes(int b, int N) {
     if (b <= 0 || N <= 0) return 0;
-    return al((size_t)N * 16) + 4 * al((size_t)N * 4) + 3 * al((size_t)N * 8) + al((size_t)b * 6 * 4) + al((size_t)b * 4) + al((size_t)b * LZ_XCHG) + al((size_t)b * 4) + al((size_t)b * FPS_HEAD_MAX * 4) +
+    return al((size_t)N * 16) + 4 * al((size_t)N * 4) + 3 * al((size_t)N * 8) + al((size_t)b * 6 * 4) + al((size_t)b * 4) + al((size_t)b * LZ_XCHG) + al((size_t)b * 4) + al((size_t)b * FPS_HEAD * 4) +
            al(fps_cub_bytes(b, N));
 }
 

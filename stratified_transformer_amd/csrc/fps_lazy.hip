@@ -34,8 +34,6 @@
 // conventions are fps_bucket.hip's.
 #include "fps_common.h"
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 
 namespace p2 {
 
@@ -69,7 +67,7 @@ __device__ __forceinline__ void st_agent(T *p, T v) { __hip_atomic_store(p, v, _
 // the counter itself is a relaxed device-scope atomic: no release / acquire FENCE anywhere.  A fence would write back and
 // invalidate the whole L2 of the workgroup's XCD - sixteen workgroups on eight XCDs, every ~35 us - and the attention kernels
 // that run beside the sampler live on L2 hits: with release / acquire atomics here they took 1.6x (forward) to 2x (backward)
-// as long (tools/interference.py).
+// as long (measured with a CU-holding interference tool, since removed).
 // Safety net: a workgroup that has waited `patience` ticks of the 100 MHz clock (2 s: the whole kernel takes milliseconds)
 // poisons the counter, which releases every waiter of the element, and all of them leave (returns false): a grid that cannot
 // make progress for a reason outside the algorithm (its workgroups not resident together: CUs held by other work) must still
@@ -127,25 +125,13 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
     return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
 }
 
-// STAMP: diagnostic build only (P2_FPS_STAMPS=1): cycle sums of the phases of wave 0 of workgroup 0 and round statistics -> dbg
-template <bool STAMP, int NSLOT>
+template <int NSLOT>
 __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, int bid0, const float *__restrict__ xyz, const int *__restrict__ offset,
                                                          const int *__restrict__ new_offset, float4 *__restrict__ pts,
                                                          const unsigned *__restrict__ rank, const int *__restrict__ prev_idx,
                                                          const int *__restrict__ prev_offset, const int *__restrict__ verified,
                                                          int *__restrict__ idx, unsigned char *__restrict__ xchg_all,
-                                                         unsigned long long patience, unsigned *__restrict__ status,
-                                                         unsigned long long *__restrict__ dbg = nullptr) {
-    unsigned long long c_ph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_last = 0;
-    auto stamp = [&](int ph) {
-        if (STAMP) {
-            __builtin_amdgcn_s_waitcnt(0);
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            c_ph[ph] += t - t_last;
-            t_last = t;
-        }
-    };
-    if (STAMP) t_last = __builtin_amdgcn_s_memtime();
+                                                         unsigned long long patience, unsigned *__restrict__ status) {
     constexpr int NW = LZ_NW, NT = LZ_NT, CAP = LZ_CAP, WORDS = LZ_WORDS;
     static_assert(NSLOT <= LZ_NSLOT, "LDS is sized for LZ_NSLOT super-buckets");
     // LDS: carved from one dynamic block (more than the 64 KiB a kernel may declare statically)
@@ -272,11 +258,9 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
     unsigned round = 0;
     __syncthreads();
 
-    stamp(0);  // 0: set-up
     for (;;) {
         // ================= update: apply the A accepted samples =================
         const int nwA = (A + 31) >> 5;
-        if (STAMP) { c_ph[12] += 1; c_ph[13] += A; }
         // (1) sample x super-bucket box tests -> sbhit (zero on entry); one (super-bucket, 8 samples) unit per thread trip
         {
             const int nu8 = (A + 7) >> 3;
@@ -294,7 +278,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
         }
         if (tid < NSLOT) sbmax[buf ^ 1][tid] = 0u;
         __syncthreads();
-        stamp(1);  // 1: sample x super-bucket tests
         // (2) lane sl: which of those samples reach its bucket (up to four ids kept; more: all of the super-bucket's)
         unsigned long long lst = 0ull;
         int cntl = 0;
@@ -312,7 +295,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
                 }
             }
         }
-        stamp(2);  // 2: own-bucket tests
         // (3) the wave updates its touched buckets in registers
         {
             const unsigned touched = (unsigned)__ballot(cntl > 0);  // (bits = slots, wave-uniform)
@@ -342,7 +324,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
                 if (lane == sl) key = km.key;
             }
         }
-        stamp(3);  // 3: bucket updates
         // ================= select =================
         {
             const KeyMax wm = wave_key_max(own ? key : 0ull);
@@ -355,7 +336,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
         for (int t = tid; t < CAP; t += NT) hcnt[t] = 0;
         __syncthreads();
         for (int t = tid; t < NSLOT * WORDS; t += NT) sbhit[t / WORDS][t % WORDS] = 0u;  // (last read above; written again after more barriers)
-        stamp(4);  // 4: maxima + barrier (waiting for the slowest wave's updates)
         if (done >= m) break;  // (uniform, and the same in every workgroup) everything selected, and applied
         unsigned long long ltop = 0ull;  // this workgroup's largest key
         {
@@ -399,10 +379,8 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
             st_agent(&h->tover, (unsigned long long)s_tover);
             st_agent(&h->count, (int)s_cnt);
         }
-        stamp(5);  // 5: gather
         round++;
         if (!group_barrier(bar, round * (unsigned)G, G, &s_abort, patience, status)) return;  // (uniform in the workgroup; see LZ_PATIENCE)
-        stamp(10);  // 10: waiting for the other workgroups
         // ---- everybody reads everybody's list (in workgroup order, cut at CAP: what is cut is bounded by its workgroup's top).
         //      One trip: lane q of every wave fetches header q while the wave fetches - speculatively - entries of "its" workgroup ----
         int K = 0, found = 0;
@@ -463,7 +441,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
             else frac = fminf(fmaxf(frac * ratio, 1e-7f), 0.5f);
         }
         __syncthreads();
-        stamp(11);  // 11: reading the lists
         lastK = K;
         // ---- order the candidates by key, descending: sorted position = the order the reference would select them in.  Keys are
         //      unique, so the position of a candidate is the number of larger keys: counted by all threads (NT / KP of them share a
@@ -500,7 +477,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
             __syncthreads();
             if (tid < K) hcnt[tid] = 0;
         }
-        stamp(6);  // 6: sort
         // ---- hitters.  hit(r, r2) = r2 < r (larger key) && d(r2, r) < d_r.  Few candidates: all pairs, spread over the whole
         //      workgroup.  Many: a hash grid - a hit needs |p_r - p_r2| < sqrt(d_top) per axis, so with cells of that edge (plus
         //      slack for the rounding of the cell index; cell indices wrap at 1024, which only merges cells) only the 27 cells
@@ -534,7 +510,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
                 gnext[tid] = (short)atomicExch(&ghead[cell_hash(gx, gy, gz)], tid);
             }
             __syncthreads();
-            stamp(14);  // 14: grid build (of rounds that use the grid)
             const int KP = (K + 63) & ~63, S = NT / KP;  // S = 2 ... 5 threads share a candidate (K > 128)
             const int part = tid / KP, j = tid - part * KP;
             if (part < S && j < K) {
@@ -566,7 +541,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
                     }
                 }
             }
-            stamp(15);  // 15: grid walk
         }
         if (tid < WORDS) {
             const int lo = tid * 32;
@@ -574,7 +548,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
         }
         __syncthreads();
         const int nh = tid < K ? hcnt[tid] : 0;
-        stamp(7);  // 7: hitters
         // ---- resolve: fixed point of acc_r = !exists r2 in hitters(r): acc_r2  (a candidate with more hitters than the list holds
         //      is simply not decided in this round) ----
         int cur = 0;
@@ -599,7 +572,6 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
             cur ^= 1;
             if (!s_changed[it & 1]) break;  // uniform: read after the barrier, reset two iterations later
         }
-        stamp(8);  // 8: fixed point
         // ---- what was not accepted bounds what may be: a dropped candidate's new key is at most its key at the distance to
         //      the accepted candidates that hit it; an undecided one keeps its key ----
         bool acc = false;
@@ -666,9 +638,7 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
             bnd = dtop;
             __syncthreads();
         }
-        if (STAMP && dbg && tid == 0 && g == 0 && round <= 512) dbg[16 + round - 1] = ((unsigned long long)found << 40) | ((unsigned long long)lastK << 20) | (unsigned)A;
         done += A;
-        stamp(9);  // 9: bounds, ranks, output
     }
     // the state a resumed call (or fps_bucket.hip) continues from
 #pragma unroll
@@ -676,19 +646,16 @@ __global__ __launch_bounds__(LZ_NT) void fps_lazy_kernel(int Bref, int log2B, in
         const int pos = start_n + (b0 + sl * NW + wave) * 64 + lane;
         if (sl * NW + wave < nbl && pos < end_n) reinterpret_cast<float *>(pts + pos)[3] = W[sl];
     }
-    if (STAMP && dbg && tid == 0 && g == 0)
-        for (int i = 0; i < 16; i++) dbg[bid * 16 + i] = c_ph[i];
 }
 
 // Workgroups per batch element: enough that a workgroup's buckets fit its registers (NW * NSLOT), and about a hundred
 // buckets each beyond that (more workgroups = less to do per round for each; the barrier costs the same).  0: the cloud is
 // too large for this kernel.
 int fps_lazy_groups(int n_max) {
-    static const int env = getenv("P2_FPS_GROUPS") ? atoi(getenv("P2_FPS_GROUPS")) : 0;
     const int nb = (n_max + 63) / 64, cap = LZ_NW * LZ_NSLOT;
     const int need = (nb + cap - 1) / cap;
     if (need > LZ_GMAX) return 0;
-    int G = env > 0 ? env : (nb + 99) / 100;
+    int G = (nb + 99) / 100;
     G = std::max(std::max(need, 1), std::min(G, LZ_GMAX));
     while (G < LZ_GMAX && LZ_NT % G != 0) G++;  // the list readers want G to divide the workgroup: 1, 2, 4, 8, 16
     return G;
@@ -699,46 +666,19 @@ void fps_lazy_launch(int b, int n_max, int Bref, int log2B, const float *xyz, co
     const int G = fps_lazy_groups(n_max);
     const int slots = div_up(div_up(div_up(n_max, 64), G), LZ_NW);  // register slots a wave needs
     (void)hipMemsetAsync(xchg, 0, (size_t)b * LZ_XCHG, st);          // barrier counters (and headers)
-    if (getenv("P2_FPS_STAMPS")) {  // diagnostic only: synchronous, prints the phase cycles of wave 0 of workgroup 0 to stderr
-        unsigned long long *dbg = nullptr, host[16 + 512];  // (per-round trace of batch element 0 only)
-        (void)hipMalloc(&dbg, sizeof(host) * b);
-        (void)hipMemset(dbg, 0, sizeof(host) * b);
-        if (slots <= 8) {
-            allow_big_lds(fps_lazy_kernel<true, 8>, lz_lds_bytes());
-            hipLaunchKernelGGL((fps_lazy_kernel<true, 8>), dim3(G, b), dim3(LZ_NT), lz_lds_bytes(), st, Bref, log2B, 0, xyz, offset, new_offset, pts, rank, prev_idx,
-                               prev_offset, verified, idx, (unsigned char *)xchg, g_fps_patience, async_status_word(), dbg);
-        } else {
-            allow_big_lds(fps_lazy_kernel<true, LZ_NSLOT>, lz_lds_bytes());
-            hipLaunchKernelGGL((fps_lazy_kernel<true, LZ_NSLOT>), dim3(G, b), dim3(LZ_NT), lz_lds_bytes(), st, Bref, log2B, 0, xyz, offset, new_offset, pts, rank, prev_idx,
-                               prev_offset, verified, idx, (unsigned char *)xchg, g_fps_patience, async_status_word(), dbg);
-        }
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(host, dbg, sizeof(host), hipMemcpyDeviceToHost);
-        (void)hipFree(dbg);
-        fprintf(stderr, "[fps lazy] G %d slots %d rounds %llu samples %llu | cycles: setup %llu sbtests %llu owntests %llu updates %llu maxima+wait %llu gather %llu gridwait %llu "
-                        "lists %llu sort %llu hitters %llu (grid build %llu walk %llu) fixedpoint %llu output %llu\n", G, slots, host[12], host[13], host[0], host[1], host[2], host[3],
-                host[4], host[5], host[10], host[11], host[6], host[7] + host[14] + host[15], host[14], host[15], host[8], host[9]);
-        if (getenv("P2_FPS_TRACE_ROUNDS")) {
-            fprintf(stderr, "[fps lazy] found/listed/accepted per round:");
-            for (int i = 0; i < 512 && host[16 + i]; i++)
-                fprintf(stderr, " %llu/%llu/%llu", host[16 + i] >> 40, (host[16 + i] >> 20) & 0xfffff, host[16 + i] & 0xfffff);
-            fprintf(stderr, "\n");
-        }
-        return;
-    }
     // the workgroups of an element wait for each other: all of a launch must be resident together (one workgroup per CU) -> at
     // most half the device's CUs per launch
     const int chunk = std::max(1, std::min(128, num_cus() / 2) / G);
     for (int c0 = 0; c0 < b; c0 += chunk) {
         const dim3 grid(G, std::min(chunk, b - c0));
         if (slots <= 8) {
-            allow_big_lds(fps_lazy_kernel<false, 8>, lz_lds_bytes());
-            hipLaunchKernelGGL((fps_lazy_kernel<false, 8>), grid, dim3(LZ_NT), lz_lds_bytes(), st, Bref, log2B, c0, xyz, offset, new_offset, pts, rank, prev_idx,
-                               prev_offset, verified, idx, (unsigned char *)xchg, g_fps_patience, async_status_word(), (unsigned long long *)nullptr);
+            allow_big_lds(fps_lazy_kernel<8>, lz_lds_bytes());
+            hipLaunchKernelGGL((fps_lazy_kernel<8>), grid, dim3(LZ_NT), lz_lds_bytes(), st, Bref, log2B, c0, xyz, offset, new_offset, pts, rank, prev_idx,
+                               prev_offset, verified, idx, (unsigned char *)xchg, g_fps_patience, async_status_word());
         } else {
-            allow_big_lds(fps_lazy_kernel<false, LZ_NSLOT>, lz_lds_bytes());
-            hipLaunchKernelGGL((fps_lazy_kernel<false, LZ_NSLOT>), grid, dim3(LZ_NT), lz_lds_bytes(), st, Bref, log2B, c0, xyz, offset, new_offset, pts, rank, prev_idx,
-                               prev_offset, verified, idx, (unsigned char *)xchg, g_fps_patience, async_status_word(), (unsigned long long *)nullptr);
+            allow_big_lds(fps_lazy_kernel<LZ_NSLOT>, lz_lds_bytes());
+            hipLaunchKernelGGL((fps_lazy_kernel<LZ_NSLOT>), grid, dim3(LZ_NT), lz_lds_bytes(), st, Bref, log2B, c0, xyz, offset, new_offset, pts, rank, prev_idx,
+                               prev_offset, verified, idx, (unsigned char *)xchg, g_fps_patience, async_status_word());
         }
         held_cus_note(st, (int)(grid.x * grid.y));
     }

@@ -453,8 +453,7 @@ bool knn_grid_launch(int m, int k, int n, int b, const float *xyz, const float *
     e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, (const unsigned *)qkeys_in, qkeys_out, (const int *)qvals_in, qperm, m, 0,
                                            bits_for_cells(b), st);
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); return true; }
-    static const bool one_lane = getenv("P2_KNN_ONE_LANE") != nullptr;
-    if (k + 1 <= 64 && !one_lane) {  // several lanes per query
+    if (k + 1 <= 64) {  // several lanes per query
 #define P2_KNN_LANES(LQ_)                                                                                                              \
     hipLaunchKernelGGL(knn_lanes_kernel<LQ_>, dim3((unsigned)div_up64((int64_t)m * LQ_, 256)), dim3(256), 0, st, m, k, new_xyz, offset, new_offset, \
                        plan, cell_start, rec, idx, dist2, replay, replay_count, qperm)

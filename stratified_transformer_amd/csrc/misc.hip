@@ -37,8 +37,7 @@ SideStreams *side_streams() {
 }  // namespace
 
 ForkJoin::ForkJoin(hipStream_t main, bool small) : main_(main) {
-    static const bool off = getenv("P2_NO_FORK") != nullptr;
-    enabled_ = !off && small;
+    enabled_ = small;
     if (enabled_) {  // the fork point is where the call starts: side lanes do not wait for this call's own lane-0 kernels
         SideStreams *s = side_streams();
         if (s) (void)hipEventRecord(s->fork, main_);
@@ -174,8 +173,6 @@ void held_cus_note(hipStream_t st, int workgroups) {
     s.live = true;
 }
 int held_cus_now() {
-    static const bool off = getenv("P2_NO_HELD_CUS") != nullptr;
-    if (off) return 0;
     std::lock_guard<std::mutex> g(held_mutex);
     int total = 0;
     for (HeldSlot &s : held_slots) {
@@ -184,25 +181,6 @@ int held_cus_now() {
         else s.live = false;
     }
     return total;
-}
-}  // namespace p2
-
-namespace p2 {
-__global__ __launch_bounds__(1024) void diag_hold_kernel(int micros, int mode, unsigned *word) {
-    extern __shared__ unsigned char diag_lds[];
-    const unsigned long long t0 = wall_clock64(), ticks = (unsigned long long)micros * 100ull;  // 100 MHz
-    unsigned acc = 0;
-    while (wall_clock64() - t0 < ticks) {
-        if (mode >= 1 && threadIdx.x == 0) acc += __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (mode >= 2) {
-            __hip_atomic_store(word + 64 + blockIdx.x * 1024 + threadIdx.x, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            acc += __hip_atomic_load(word + 64 + ((blockIdx.x + 1) % gridDim.x) * 1024 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int i = 0; i < 300; i++) __builtin_amdgcn_s_sleep(1);
-        } else {
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    if (acc == 0xdeadbeefu) diag_lds[threadIdx.x] = 1;  // (keeps acc and the LDS allocation alive)
 }
 }  // namespace p2
 
@@ -327,14 +305,6 @@ void pointops2_csc_build(int N, int M, const int *index0_offsets, const int *ind
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); return; }
     hipLaunchKernelGGL(csc_finish_kernel, dim3(div_up(M, 256)), dim3(256), 0, st, NK, M, keys, csc_pair, index0, csc_offsets, csc_query);
     check_launch();
-}
-
-// Diagnostic only (tools/interference.py; not part of the header): `blocks` workgroups of 1024 threads with 128 VGPRs' worth of
-// occupancy hold their CUs for `micros` microseconds; mode 0 spins in registers, 1 polls `word` with device-scope atomic loads,
-// 2 also stores to / loads from `word + 64...` with device-scope accesses every ~10 us.
-void pointops2_diag_hold_cus_launcher(int blocks, int micros, int mode, unsigned *word, int lds_kb) {
-    allow_big_lds(diag_hold_kernel, (size_t)lds_kb * 1024);  // (120 KB: no cell workgroup fits beside it)
-    hipLaunchKernelGGL(diag_hold_kernel, dim3(blocks), dim3(1024), (size_t)lds_kb * 1024, state().stream, micros, mode, word);
 }
 
 }  // extern "C"

@@ -18,7 +18,6 @@ tests compare it with the oracle on CPU); on the GPU the heavy steps dispatch to
 `use_hip=True` (stratified_transformer_amd/csrc/index.hip).
 """
 import ctypes
-import os
 from dataclasses import dataclass
 
 import torch
@@ -268,18 +267,14 @@ def cell_query_cap(n_points, heads):
     # measured on the four stages of the S3DIS configuration (points x heads = 300k, 150k, 75k, 37k; tools/bench_cell.py): pieces of 32
     # queries for the two large ones, 16 for the two small ones (8 / 4 there cost 5-25 % of the backward: every piece flushes its
     # keys' gradients; 32 there leaves too few pieces for the chip)
-    big, small = int(os.environ.get("P2_CELL_CAP_BIG", 32)), int(os.environ.get("P2_CELL_CAP_SMALL", 16))   # (experiment knobs)
-    return big if n_points * heads >= 96000 else small
+    return 32 if n_points * heads >= 96000 else 16
 
 
 class _KeyOverflow(Exception):
     """a voxel coordinate did not fit the fixed-width key of the one-sort partitions"""
 
 
-FUSED_PARTITIONS = os.environ.get("P2_PARTITIONS4", "1") != "0"
-
-
-def stage_partitions_hip(xyz, offset, window_size, one_sort=None, cell_max_queries=None):
+def stage_partitions_hip(xyz, offset, window_size, one_sort=True, cell_max_queries=None):
     """The part of a stage's index build that needs the coordinates only: bounding box and the four window partitions
     (grid_sample x 4, stratified_transformer.py:277,280,297,300).  Returns the context stage_index_hip continues from - a caller
     can run this beside the stage's FPS instead of behind it.
@@ -300,8 +295,6 @@ def stage_partitions_hip(xyz, offset, window_size, one_sort=None, cell_max_queri
     l = _lib.lib()
     w32 = np.float32(window_size)
     i32 = dict(dtype=torch.int32, device=dev)
-    if one_sort is None:
-        one_sort = FUSED_PARTITIONS
     names = ("small", "small_shift", "large", "large_shift")
     with torch.cuda.device(dev):
         ws_bytes = int(l.pointops2_index_workspace_bytes(N))

@@ -277,46 +277,8 @@ def geometry_stream(device, which=0):
     return _GEO_STREAMS[key]
 
 
-EVEN_FIRST = os.environ.get("P2_EVEN_FIRST", "1") != "0"  # the first stage's first block is enqueued from inside its index build
 SPECULATION = {"passes": 0, "reruns": 0}  # speculated passes / how many of them had to be run again (an exact tie among later-stage samples)
 SPECULATE = os.environ.get("P2_SPECULATE", "1") != "0"  # later stages' samples are taken as the identity prefix while the sampler verifies them
-INDEX_THREAD = os.environ.get("P2_INDEX_THREAD", "0") == "1"  # measured: 16.2 ms against 15.5 ms per pass (the two host threads contend), so opt-in
-
-
-class _IndexBuilder:
-    """Runs index(si) for every stage, in order, on a helper thread; wait(si) returns when stage si's index is enqueued
-    (its tensors exist, its event is recorded) and re-raises what the build raised."""
-
-    def __init__(self, index_fn, stages):
-        import threading
-        self._done = {si: threading.Event() for si in stages}
-        self._error = None
-        dev = torch.cuda.current_device()
-
-        def work():
-            try:
-                torch.cuda.set_device(dev)
-                for si in stages:
-                    index_fn(si)
-                    self._done[si].set()
-            except BaseException as e:  # noqa: BLE001 - handed to the waiting thread
-                self._error = e
-            finally:
-                for ev in self._done.values():
-                    ev.set()
-
-        self._thread = threading.Thread(target=work, name="p2-index-build", daemon=True)
-        self._thread.start()
-
-    def wait(self, si):
-        self._done[si].wait()
-        if self._error is not None:
-            raise self._error
-
-    def join(self):
-        self._thread.join()
-        if self._error is not None:
-            raise self._error
 
 
 _FLAG_HOST = {}  # (device index, lane) -> pinned bool [1]: the speculation check of a pass arrives here
@@ -587,10 +549,9 @@ def scene_pass_phases(xyz, offset, cfg, states=None, timer=None, seed=0, overlap
     after = yield "geometry queued"
     if after is not None:  # passes_in_flight: the attention blocks of this batch follow those of the previous one
         main.wait_event(after)
-    # The index builds stop the host twice each (key width, pair count) and each waits for its stage's samples.  They run on a
-    # helper thread (own stream; the library's launch state is thread-local), one stage after the other as the geometry
-    # arrives, so the launches of the attention blocks never wait behind a later stage's sampling.
-    builder = _IndexBuilder(index, stages) if (overlap and INDEX_THREAD) else None
+    # The index builds stop the host twice each (key width, pair count) and each waits for its stage's samples.  (Running them on
+    # a helper thread, one stage after the other as the geometry arrives, was measured slower: 16.2 against 15.5 ms per pass - the
+    # two host threads contend.)
     started = {}  # si -> output of block 0, when it was enqueued from inside the stage's index build
 
     def first_block_early(even_blk):
@@ -618,13 +579,11 @@ def scene_pass_phases(xyz, offset, cfg, states=None, timer=None, seed=0, overlap
             timer.stage = None
 
     halo_mode = shard is not None and len(shard) > 2 and shard[2] == "halo"  # (ownership is cut over BOTH patterns' pairs: no early block)
-    if builder is None:
-        index(first, first_block_early if (overlap and use_hip_index and EVEN_FIRST and not halo_mode) else None)
+    # the first stage's first block is enqueued from inside its index build
+    index(first, first_block_early if (overlap and use_hip_index and not halo_mode) else None)
     for si in stages:
         st = cfg.stages[si]
         x, off, _ = clouds[si]
-        if builder is not None:
-            builder.wait(si)
         even, odd, ev_idx, parts_ctx = idx_out[si]
         if shard is not None and len(shard) > 2 and shard[2] == "halo" and even is not None and odd is not None:
             from . import sharding as _sh
@@ -665,7 +624,7 @@ def scene_pass_phases(xyz, offset, cfg, states=None, timer=None, seed=0, overlap
             timer.stage = si
             out = attention_block(state, blk_b, timer, fused, shard)
             timer.stage = None
-            if early and b == early_after and builder is None:
+            if early and b == early_after:
                 index(si + 1)
         results.append(dict(stage=si, n=x.shape[0], M_even=int(even.index_1.shape[0]), M_odd=int(odd.index_1.shape[0]),
                             even=even, odd=odd, downsample_idx=ds, out=out))
@@ -678,10 +637,8 @@ def scene_pass_phases(xyz, offset, cfg, states=None, timer=None, seed=0, overlap
                 results[-1]["out_rows"] = (last_blk.shard[0].lo, last_blk.shard[0].hi)
         if knn_idx is not None:
             results[-1]["transition_knn"] = knn_idx
-        if si + 1 in stages and not early and builder is None:
+        if si + 1 in stages and not early:
             index(si + 1)
-    if builder is not None:
-        builder.join()
     timer.run("mark/blocks_done", lambda: None)
     if overlap:
         main.wait_stream(geo)
@@ -730,25 +687,26 @@ def passes_in_flight(xyz_list, offset_list, cfg, lanes, steps, timer=None, fused
 
     prev_done = None
     done_events = []
-    pace_lag = int(os.environ.get("P2_PACE_LAG", "1"))  # released on batch k-lag: 22.2 / 24.0 / 28.8 ms per step for 1 / 2 / 3
     ahead = len(lanes) - 1  # geometry phases queued in front of the attention phase being enqueued
     queue = [start(k) for k in range(min(ahead, steps))]
-    blocks_first = os.environ.get("P2_BLOCKS_FIRST", "1") != "0" and ahead > 0
+    blocks_first = ahead > 0
 
     def release_geometry(k):
         if k + ahead < steps:
             # Pacing: the geometry of batch k+ahead is released when batch k-1 is through, so a fixed number of
             # sampling chains is in flight, evenly spaced.  Released as early as the host can (three chains start
             # in a burst, slow each other and the attention kernels beside them) a step takes 28.5 instead of 24.8 ms;
-            # with the same dependency on the device only (side streams waiting for the lane's main stream) 26.9 ms.
-            if paced and len(done_events) >= pace_lag + (1 if blocks_first else 0):
-                done_events[-pace_lag - (1 if blocks_first else 0)].synchronize()
+            # with the same dependency on the device only (side streams waiting for the lane's main stream) 26.9 ms.  (Released on
+            # batch k-2 or k-3 instead: 24.0 / 28.8 against 22.2 ms per step.)
+            lag = 2 if blocks_first else 1  # (with the blocks first, the last done event is batch k's own)
+            if paced and len(done_events) >= lag:
+                done_events[-lag].synchronize()
             queue.append(start(k + ahead))
 
     for k in range(steps):
         # Round 2: the index builds and blocks of batch k are enqueued BEFORE the host waits for batch k-1 (the pacing of the
         # geometry): with the sampler at 5 instead of 27 ms the wait, the geometry launches and the first index build of batch k
-        # otherwise leave the attention stream idle for 2-3 ms per batch (P2_BLOCKS_FIRST=0: the round-1 order).
+        # otherwise leave the attention stream idle for 2-3 ms per batch (the round-1 order, kept where nothing runs ahead).
         if not blocks_first:
             release_geometry(k)
         gen = queue.pop(0)

@@ -4,6 +4,7 @@ import ctypes
 import inspect
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -152,6 +153,12 @@ def test_library_exports_every_symbol_of_the_header():
     for n in names:
         assert hasattr(l, n), f"{n} declared in include/pointops2_hip.h but not exported"
     assert set(_lib.exported_symbols()) == set(names), set(_lib.exported_symbols()) ^ set(names)
+    # and the reverse: every ABI-named symbol the library exports is declared in the header
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    abi = {l.split()[-1] for l in nm.splitlines() if l.strip()}
+    abi = {n for n in abi if n.startswith("pointops2_") or n.endswith("_launcher")}
+    assert len(abi) >= 30
+    assert abi <= set(names), f"exported but not declared in include/pointops2_hip.h: {sorted(abi - set(names))}"
     assert _lib.lib().pointops2_abi_version() >= 2
 
 

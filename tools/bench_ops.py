@@ -44,6 +44,6 @@ def main():
     res['A1 bwd'] = timeit(lambda: bwd(a1, g_pairs))
     res['A2 bwd'] = timeit(lambda: bwd(a2, g_pairs))
     res['A4 bwd'] = timeit(lambda: bwd(out, g_rows))
-    print('ablate', os.environ.get('P2_ABLATE', '0'), {k_: round(v_) for k_, v_ in res.items()})
+    print({k_: round(v_) for k_, v_ in res.items()})
 
 main()

@@ -1,4 +1,4 @@
-"""FPS alone on the bench scene: stage-0 stratified + transition calls (diagnostic; GPU box only).  P2_FPS_STAMPS=1 prints phase cycles."""
+"""FPS alone on the bench scene: stage-0 stratified + transition calls (diagnostic; GPU box only)."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

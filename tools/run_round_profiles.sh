@@ -5,7 +5,6 @@ D=${OUT:-$R/runs}/r2a
 mkdir -p $D
 cd $R
 timeout -k 10 600 python -m pytest tests -x -q -m gpu > $D/gpu_tests.log 2>&1 ; echo "tests rc=$?"; tail -3 $D/gpu_tests.log
-P2_FPS_STAMPS=1 timeout -k 10 200 python tools/fps_only.py 100000 2>&1 | tail -3
 ( time timeout -k 10 500 python bench.py --full > $D/bench_default.log 2>&1 ) 2>&1 | grep real; tail -c 600 $D/bench_default.log
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/kt -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $D/kt.log 2>&1; echo "kt rc=$?"
