@@ -16,9 +16,9 @@
  *   - outputs are fully written by the kernels (the caller's zero-fill is harmless, not required),
  *     except where noted "accumulates".
  *
- * PART 2 are the additional native entry points this build adds on the same path (segment softmax
- * = the torch_scatter.scatter_softmax call of the model, CSC transposition used by the backward
- * kernels, scratch memory for the bucketed exact FPS).
+ * PART 2 are the launch options (pointops2_launch_opts) and the additional native entry points this
+ * build adds on the same path (segment softmax = the torch_scatter.scatter_softmax call of the model,
+ * CSC transposition used by the backward kernels, the index build, ...).
  */
 #ifndef POINTOPS2_HIP_H
 #define POINTOPS2_HIP_H
@@ -38,7 +38,7 @@ void pointops2_set_stream(void *hip_stream);
 void *pointops2_get_stream(void);
 /* NULL when the last call on this thread succeeded; otherwise a static message.  Reading clears. */
 const char *pointops2_last_error(void);
-/* library/ABI version, bumped when a signature changes */
+/* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters) */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -113,7 +113,7 @@ void attention_step2_with_rel_pos_value_backward_cuda_launcher(int N, int M, int
 /* rpe_v2/relative_pos_encoding_cuda_kernel_v2.h:22-29 — CSR forms.  table [L,h,hdim,3]; rel_idx [M,3].
  * hdim must be 16 or 32.  backward: grad_q / grad_attn fully written; grad_k / grad_v / table grads
  * ACCUMULATE (pre-zeroed by the caller).  The table length L is not part of the reference signature
- * but the fast kernels stage the tables in LDS: announce it with pointops2_set_table_rows(L) before any
+ * but the fast kernels stage the tables in LDS: pass it as launch_opts.table_rows (PART 2) for any
  * *_v3 bias or *_v2 rel-pos-value launcher (forward and backward).  Without it the launchers are still
  * callable with the reference's arguments alone: generic kernels then read the tables from global
  * memory and accumulate with atomics as the reference does (same results, several times slower). */
@@ -161,46 +161,52 @@ void aggregation_backward_cuda_launcher(int n, int nsample, int c, int w_c, cons
 /* PART 2 — additional entry points of this build                                             */
 /* ------------------------------------------------------------------------------------------ */
 
-/* Rows L of the [L,h,hdim,3] tables for the next *_v2/_v3 rel-pos call on this thread. */
-void pointops2_set_table_rows(int L);
-
-/* Bucketed exact FPS (same index sequence as the reference, ~30x fewer bytes per step): taken by
- * furthestsampling_cuda_launcher when the caller has lent a scratch buffer of at least
- * pointops2_fps_workspace_bytes(b, N) bytes with pointops2_set_workspace() and announced the total
- * point count N = offset[b-1] of the next call with pointops2_set_point_count() (the reference
- * signature only carries the largest batch element).  Otherwise the single-workgroup scan runs. */
-void pointops2_set_workspace(void *device_ptr, size_t bytes);
-void pointops2_set_point_count(int N);
-/* Grid-accelerated exact kNN (same idx/dist2 as the reference's full scan, ties replayed literally):
- * taken by knnquery_cuda_launcher when a workspace of pointops2_knn_workspace_bytes(n, m, b) bytes is
- * lent and the candidate count n (pointops2_set_point_count) and batch count b are announced. */
-void pointops2_set_batch_count(int b);
-size_t pointops2_knn_workspace_bytes(int n, int m, int b);
+/* ---- launch options: the facts the fast kernels need that the PART-1 signatures do not carry ------------------
+ * ONE RULE: the options set with pointops2_set_launch_opts() apply to the next library launch on this thread, and that
+ * launch resets them, whether or not it used them (the stream is not an option: it stays until set again).  0 / NULL = not
+ * given; all-zero = the reference's arguments alone (same results, in places slower generic kernels).  The *_workspace_bytes
+ * queries, pointops2_last_error, pointops2_get_stream and pointops2_abi_version are no launches: they leave the options. */
+typedef struct pointops2_launch_opts {
+    /* L of the [L,h,hdim,3] tables of a *_v3 bias, *_v2 rel-pos-value or window_* call: the fast kernels stage them in LDS.
+     * Without it the rel-pos launchers read the tables from global memory (several times slower), window_* record an error. */
+    int table_rows;
+    /* rows of k / v when they outnumber the CSR's query rows N (a rank of a sharded scene); 0 = N */
+    int key_rows;
+    /* key-major view of the call's pair list (pointops2_csc_build): the *_backward_* launchers gather the key-side gradients
+     * by key; without it they accumulate them with global float atomics, as the reference does */
+    const int *csc_offsets;
+    const int *csc_pair;
+    const int *csc_query;
+    /* rows in window order (pointops2_row_order_launcher) and their count: the A1 / A2 / A4 pair walkers take their rows in
+     * that order when a launch walks exactly row_order_rows >= 2048 rows (same results, partner gathers hit L2) */
+    const int *row_order;
+    int row_order_rows;
+    /* scratch lent to furthestsampling_cuda_launcher (>= pointops2_fps_workspace_bytes(b, N)) or knnquery_cuda_launcher
+     * (>= pointops2_knn_workspace_bytes(n, m, b)) with the counts the signatures lack: point_count = N = offset[b-1] (FPS) or
+     * n (kNN), batch_count = b (kNN).  FPS: bucketed exact sampler in rounds when n >= 2048; kNN: exact grid search; without
+     * them the reference's scans.  Same indices either way. */
+    void *workspace;
+    size_t workspace_bytes;
+    int point_count;
+    int batch_count;
+    /* FPS resume: idx / new_offset of the previous call on the SAME xyz/offset whose state the workspace still holds - the
+     * sampler continues that chain instead of starting over (the model asks for n/8+1, then n/4+1 samples, :289,103) */
+    const int *fps_prev_idx;
+    const int *fps_prev_new_offset;
+    /* != 0: the FPS cloud is a raw scene, not an earlier FPS output in selection order - skips the identity-prefix probe
+     * (~60 us); same result with a wrong flag */
+    int fps_unordered;
+} pointops2_launch_opts;
+/* copies *opts into this thread's launch options (NULL clears them) */
+void pointops2_set_launch_opts(const pointops2_launch_opts *opts);
 size_t pointops2_fps_workspace_bytes(int b, int N);
-/* FPS is deterministic, so a request for fewer samples of the same cloud is a prefix of a longer one
- * (the model asks for n/8+1 and then n/4+1 samples of the same points, stratified_transformer.py:289,103).
- * If the workspace still holds the state of the previous call on the SAME xyz/offset, pass that call's
- * idx/new_offset here: the next furthestsampling_cuda_launcher copies those samples and continues
- * instead of starting over.  One-shot (cleared by the launch). */
-void pointops2_set_fps_resume(const int *prev_idx, const int *prev_new_offset);
-/* One-shot hint for the next furthestsampling_cuda_launcher: unordered != 0 = the caller knows that the cloud is NOT the output of an
- * earlier FPS in selection order (a raw scene), so the identity-prefix probe (six small launches, ~60 us in front of the sampler) is
- * skipped.  The result is the same with or without the hint, and with a wrong hint. */
-void pointops2_set_fps_hint(int unordered);
-
-/* Key-major ("CSC") transposition of a CSR pair list, used by the backward kernels instead of
- * global float atomics.  When set (thread-local, cleared with NULLs), the *_backward_* launchers
- * above gather by key; otherwise they build a temporary one themselves in `workspace`.
- *   csc_offsets [N+1], csc_pair [M] (pair id m, ascending per key), csc_query [M] (query of m). */
+size_t pointops2_knn_workspace_bytes(int n, int m, int b);
+/* key-major ("CSC") transposition of a CSR pair list: csc_offsets [keys+1] (keys = launch_opts.key_rows, 0: N), csc_pair [M]
+ * (pair ids, ascending per key), csc_query [M] (query of each pair) */
 size_t pointops2_csc_workspace_bytes(int N, int M);
 void pointops2_csc_build(int N, int M, const int *index0_offsets, const int *index1,
                          int *csc_offsets, int *csc_pair, int *csc_query,
                          void *workspace, size_t workspace_bytes);
-void pointops2_set_csc(const int *csc_offsets, const int *csc_pair, const int *csc_query);
-/* Rows of k / v when they outnumber the CSR's query rows N (a rank of a sharded scene holds all keys but only
- * its own queries); read by pointops2_csc_build (then csc_offsets has n+1 entries) and by the *_backward_*
- * launchers' key-side kernels.  0 (default) = N, the reference's implicit assumption. */
-void pointops2_set_key_rows(int n);
 
 /* torch_scatter.scatter_softmax(src [M,h], index_0, dim=0) over CSR segments
  * (model/stratified_transformer.py:205) and its backward. */
@@ -229,13 +235,10 @@ void pointops2_window_partition_launcher(int N, int b, const float *xyz, const i
  * window): cluster / order [4][N], starts [4][N+2], n_windows [4], same contents as four partition calls.  The key is of fixed width
  * (ten bits per voxel coordinate: no bounding-box read-back); *overflow = 1 when a coordinate does not fit - the outputs are then
  * meaningless (but in range) and the caller builds the partitions one by one. */
-/* Rows in window order: order [N] = the rows of a CSR pair list sorted by their first partner (rows of one window become neighbours).
- * pointops2_set_row_order(order, N) makes the operators' pair walkers (A1 / A2 / A4 forward and backward, by query and by key) take
- * their rows in that order, eight runs over the eight XCDs, whenever a launch walks exactly N rows: same results (the sums of a row
- * do not change), the gathers of neighbouring waves hit the second-level cache.  nullptr (the default): rows by index. */
+/* Rows in window order: order [N] = the rows of a CSR pair list sorted by their first partner (rows of one window become neighbours),
+ * for launch_opts.row_order. */
 size_t pointops2_row_order_workspace_bytes(int N);
 void pointops2_row_order_launcher(int N, int M, const int *offsets, const int *index1, int *order, void *ws, size_t ws_bytes);
-void pointops2_set_row_order(const int *order, int n_rows);
 size_t pointops2_partitions4_workspace_bytes(int N);
 void pointops2_window_partitions4_launcher(int N, int b, const float *xyz, const int *offset, const float *bbox6, float window,
                                            int *cluster, int *order, int *starts, int *n_windows, int *overflow, void *ws,
@@ -262,15 +265,15 @@ void pointops2_csr_matches_launcher(int N, int M, const int *offsets, const void
 /* ---- optional fused path (no counterpart in the reference's launcher set) -----------------------
  * attn[m,hh] = softmax over the query's pairs of (<q,k[j]> + <q,Tq(m)> + <k[j],Tk(m)>): A1 + A2 + add + A3 of
  * WindowAttention.forward (model/stratified_transformer.py:183-205) in one kernel.  d = 16 only; needs
- * pointops2_set_table_rows(L).  attn [M,h] is fully written (no zero-fill needed). */
+ * launch_opts.table_rows.  attn [M,h] is fully written (no zero-fill needed). */
 void window_logits_softmax_forward_launcher(int N, int M, int h, int hdim, const float *q, const int *index_q_offsets,
                                              const float *k, const int *index_k, const float *table_q,
                                              const float *table_k, const int *rel_idx, float *attn);
 
 /* Backward of the whole sequence for that module: grad_logit [M,h] (scratch/output, fully written), grad_q [N,h,16],
  * grad_k / grad_v [rows of k, h, 16] fully written; the three table gradients [L,h,16,3] are ACCUMULATED (zero-fill them).
- * attn = the forward's softmax output.  Needs pointops2_set_table_rows(L), pointops2_set_csc(...) and, when k / v have
- * other rows than q, pointops2_set_key_rows. */
+ * attn = the forward's softmax output.  Needs launch_opts.table_rows, launch_opts.csc_* and, when k / v have other rows
+ * than q, launch_opts.key_rows. */
 void window_attention_backward_launcher(int N, int M, int h, int hdim, const float *grad_out, const float *q, const float *k,
                                         const float *v, const float *attn, const int *index0_offsets, const int *index1,
                                         const float *table_q, const float *table_k, const float *table_v,

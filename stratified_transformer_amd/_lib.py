@@ -16,18 +16,27 @@ _lib = None
 
 I, U, P, Z, F = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float
 
+
+class LaunchOpts(ctypes.Structure):
+    """pointops2_launch_opts (include/pointops2_hip.h): options of the next launch on this thread only; all-zero = the
+    reference's arguments alone.  Pointers are raw device addresses of tensors the caller keeps alive over the launch."""
+    _fields_ = [("table_rows", I), ("key_rows", I), ("csc_offsets", P), ("csc_pair", P), ("csc_query", P), ("row_order", P),
+                ("row_order_rows", I), ("workspace", P), ("workspace_bytes", Z), ("point_count", I), ("batch_count", I),
+                ("fps_prev_idx", P), ("fps_prev_new_offset", P), ("fps_unordered", I)]
+
+
+def with_table_rows(opts, L):
+    """`opts` (a new LaunchOpts if None) with table_rows = L, which the rel-pos and window_* fast kernels need"""
+    opts = opts if opts is not None else LaunchOpts()
+    opts.table_rows = int(L)
+    return opts
+
+
 # name -> argtypes; mirrors include/pointops2_hip.h one to one
 SIGNATURES = {
     "pointops2_set_stream": [P],
     "pointops2_diag_set_fps_patience": [ctypes.c_ulonglong],
-    "pointops2_set_table_rows": [I],
-    "pointops2_set_workspace": [P, Z],
-    "pointops2_set_point_count": [I],
-    "pointops2_set_batch_count": [I],
-    "pointops2_set_key_rows": [I],
-    "pointops2_set_fps_resume": [P, P],
-    "pointops2_set_fps_hint": [I],
-    "pointops2_set_csc": [P, P, P],
+    "pointops2_set_launch_opts": [ctypes.POINTER(LaunchOpts)],
     "pointops2_csc_build": [I, I, P, P, P, P, P, P, Z],
     "furthestsampling_cuda_launcher": [I, I, P, P, P, P, P],
     "knnquery_cuda_launcher": [I, I, P, P, P, P, P, P],
@@ -67,7 +76,6 @@ SIGNATURES = {
     "pointops2_window_partition_launcher": [I, I, P, P, P, F, F, I, P, P, P, P, P, Z],
     "pointops2_window_partitions4_launcher": [I, I, P, P, P, F, P, P, P, P, P, P, Z],
     "pointops2_row_order_launcher": [I, I, P, P, P, P, Z],
-    "pointops2_set_row_order": [P, I],
     "pointops2_window_coord_launcher": [I, P, P, F, I, P],
     "pointops2_sampled_buckets_launcher": [I, I, P, P, P, P, P, P, P, P, Z],
     "pointops2_pairs_count_launcher": [I, P, P, P, P, P, P, P, P, Z],
@@ -154,8 +162,9 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 CALLS = [0]  # library launcher calls so far (bench.py: per pass)
 
 
-def call(name, *args, device=None):
-    """Launch `name` on torch's current stream of `device` and surface library errors."""
+def call(name, *args, device=None, opts=None):
+    """Launch `name` on torch's current stream of `device` and surface library errors.  opts: LaunchOpts for this launch
+    (None: the reference's arguments alone)."""
     CALLS[0] += 1
     l = lib()
     if _raw_stream is not None and device is not None and device.index is not None:
@@ -163,6 +172,8 @@ def call(name, *args, device=None):
     else:
         stream = torch.cuda.current_stream(device).cuda_stream
     l.pointops2_set_stream(stream)
+    if opts is not None:
+        l.pointops2_set_launch_opts(opts)
     getattr(l, name)(*args)
     err = l.pointops2_last_error()
     if err is not None:

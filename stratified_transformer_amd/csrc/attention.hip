@@ -11,7 +11,7 @@
 // LPG lanes of the pair's group so the [PPW, h] output tile is written as one contiguous run.
 //
 // Backward never scatters with global float atomics when a key-major (CSC) view of the pair list
-// is available (pointops2_set_csc): grad_q is a by-query gather-accumulate, grad_k the same kernel
+// is available (launch_opts.csc_*): grad_q is a by-query gather-accumulate, grad_k the same kernel
 // run by key.  Without a CSC the by-query kernel falls back to global atomics (the reference's own
 // scheme, attention_cuda_kernel_v2.cu:84).
 #include "common.h"
@@ -238,9 +238,10 @@ void attention_step1_forward_cuda_launcher_v2(int N, int M, int h, int C, const 
                                               const float *q, const float *k, const int *index0_offsets,
                                               const int *index1, float *attn) {
     (void)n_max;
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    hipStream_t st = state().stream;
-    const int *rord = rows_in_order(N);
+    const hipStream_t st = ln.stream;
+    const int *rord = ln.rows_in_order(N);
     const int blocks = rord ? ordered_grid(N, 4) : div_up(N, 4);
     const size_t lds = 4 * (size_t)C * sizeof(float);
     dispatch_d(C / h,
@@ -254,12 +255,12 @@ void attention_step1_backward_cuda_launcher_v2(int N, int M, int h, int C, const
                                                const int *index1, const float *q, const float *k,
                                                float *grad_q, float *grad_k) {
     (void)n_max;
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    hipStream_t st = state().stream;
-    const LaunchState &ls = state();
-    const int *rord = rows_in_order(N);
+    const hipStream_t st = ln.stream;
+    const int *rord = ln.rows_in_order(N);
     const int blocks = rord ? ordered_grid(N, 4) : div_up(N, 4);
-    const int *co = ls.csc_offsets, *cp = ls.csc_pair, *cq = ls.csc_query;
+    const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair, *cq = ln.opts.csc_query;
     ForkJoin fj(st, fork_worthwhile((int64_t)M * h));  // grad_q and grad_k are independent
     auto run = [&](auto dtag) {
         constexpr int D = decltype(dtag)::value;
@@ -267,8 +268,8 @@ void attention_step1_backward_cuda_launcher_v2(int N, int M, int h, int C, const
         hipLaunchKernelGGL((gather_accum_kernel<D, false>), dim3(blocks, chunks), dim3(256), 0, st, N, h, index0_offsets,
                            index1, (const int *)nullptr, grad_out, k, grad_q, rord);
         if (co) {
-            const int NK = ls.key_rows > 0 ? ls.key_rows : N;
-            const int *kord = rows_in_order(NK);  // (the keys of a window are its queries: the same order serves the transposed list)
+            const int NK = ln.key_rows(N);
+            const int *kord = ln.rows_in_order(NK);  // (the keys of a window are its queries: the same order serves the transposed list)
             hipLaunchKernelGGL((gather_accum_kernel<D, true>), dim3(kord ? ordered_grid(NK, 4) : div_up(NK, 4), chunks), dim3(256), 0, fj.lane(1), NK, h, co, cq, cp,
                                grad_out, q, grad_k, kord);
         }
@@ -283,35 +284,40 @@ void attention_step1_backward_cuda_launcher_v2(int N, int M, int h, int C, const
 void attention_step1_forward_cuda_launcher(int N, int M, int h, int C, const float *q, const float *k,
                                            const int *index0, const int *index1, float *attn) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
     if ((C / h) % 4) { set_error("head dim must be a multiple of 4"); return; }
-    hipLaunchKernelGGL(step1_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, C / h, q, k, index0, index1, attn);
+    hipLaunchKernelGGL(step1_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, q, k, index0, index1, attn);
     check_launch();
 }
 void attention_step1_backward_cuda_launcher(int N, int M, int h, int C, const float *grad_out,
                                             const int *index0, const int *index1, const float *q,
                                             const float *k, float *grad_q, float *grad_k) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
-    hipLaunchKernelGGL(step1_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, C / h, grad_out, index0, index1, q, k, grad_q, grad_k);
+    hipLaunchKernelGGL(step1_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, grad_out, index0, index1, q, k, grad_q, grad_k);
     check_launch();
 }
 void attention_step2_forward_cuda_launcher(int N, int M, int h, int C, const float *attn, const float *v,
                                            const int *index0, const int *index1, float *output) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
-    hipLaunchKernelGGL(step2_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, C / h, attn, v, index0, index1, output);
+    hipLaunchKernelGGL(step2_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, attn, v, index0, index1, output);
     check_launch();
 }
 void attention_step2_backward_cuda_launcher(int N, int M, int h, int C, const float *grad_out,
                                             const int *index0, const int *index1, const float *attn,
                                             const float *v, float *grad_attn, float *grad_v) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
-    hipLaunchKernelGGL(step2_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, C / h, grad_out, index0, index1, attn, v, grad_attn, grad_v);
+    hipLaunchKernelGGL(step2_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, grad_out, index0, index1, attn, v, grad_attn, grad_v);
     check_launch();
 }
-// attention_cuda_kernel_v2.cu:148-195 is a byte-for-byte copy of the v1 step2 kernels
+// attention_cuda_kernel_v2.cu:148-195 is a byte-for-byte copy of the v1 step2 kernels.  (No begin_launch() here: the v1
+// launcher takes the stream and resets the launch options, of which it reads none.)
 void attention_step2_forward_cuda_launcher_v2(int N, int M, int h, int C, const float *attn, const float *v,
                                               const int *index0, const int *index1, float *output) {
     attention_step2_forward_cuda_launcher(N, M, h, C, attn, v, index0, index1, output);

@@ -730,7 +730,7 @@ __global__ __launch_bounds__(CT_WAVES * 64) void cell_table_grad3_kernel(pointop
 }
 
 template <typename T>
-static void launch_cell_fwd(const pointops2_cell_plan *plan, int h, int hdim, int L, const T *q, const T *k, const T *v, const T *table_q,
+static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const T *q, const T *k, const T *v, const T *table_q,
                             const T *table_k, const T *table_v, float *out, float *ml, float *pbuf) {
     if (plan == nullptr || plan->n_points <= 0) return;
     if (hdim != 16) { set_error("cell_attention: d != 16"); return; }
@@ -739,7 +739,7 @@ static void launch_cell_fwd(const pointops2_cell_plan *plan, int h, int hdim, in
     if (L != plan->table_rows) { set_error("cell_attention: the tables' row count differs from the plan's table_rows"); return; }
     if constexpr (std::is_same<T, float>::value) {
         // the matrix-core forward (cell_attn_mfma.hip) where it was measured faster than the VALU walkers below
-        if (cell_fwd_mfma_launch(plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf)) {
+        if (cell_fwd_mfma_launch(st, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf)) {
             check_launch();
             return;
         }
@@ -750,13 +750,13 @@ static void launch_cell_fwd(const pointops2_cell_plan *plan, int h, int hdim, in
         const size_t lds = TabGeo<80>::bytes(sizeof(T));
         allow_big_lds(cell_fwd_kernel<CA_NP, 80, T>, lds);
         const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
-        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 80, T>), grid, block, lds, state().stream, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
+        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 80, T>), grid, block, lds, st, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
                            pbuf, plane);
     } else if (L <= 160) {
         const size_t lds = TabGeo<160>::bytes(sizeof(T));
         allow_big_lds(cell_fwd_kernel<CA_NP, 160, T>, lds);
         const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
-        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 160, T>), grid, block, lds, state().stream, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
+        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 160, T>), grid, block, lds, st, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
                            pbuf, plane);
     } else {
         set_error("cell_attention: more than 160 table rows (use the operators)");
@@ -766,14 +766,13 @@ static void launch_cell_fwd(const pointops2_cell_plan *plan, int h, int hdim, in
 }
 
 template <typename T>
-static void launch_cell_bwd(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const T *q, const T *k, const T *v,
+static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const T *q, const T *k, const T *v,
                             const float *out, const T *table_q, const T *table_k, const T *table_v, const float *pbuf, float *gsbuf, float *grad_q,
                             float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
     if (plan == nullptr || plan->n_points <= 0) return;
     if (hdim != 16) { set_error("cell_attention: d != 16"); return; }
     if (L < 1 || L > 80) { set_error("cell_attention backward: table rows L must be in 1..80"); return; }
     if (L != plan->table_rows) { set_error("cell_attention backward: the tables' row count differs from the plan's table_rows"); return; }
-    hipStream_t st = state().stream;
     const size_t lds = TabGeo<80>::bytes(sizeof(T)) + (size_t)CA_WAVES_BWD * 256 * sizeof(float);
     allow_big_lds(cell_bwd_kernel<CA_NP_BWD, 80, T>, lds);
     const size_t plane = (size_t)plan->n_pairs;
@@ -806,26 +805,26 @@ extern "C" {
 void cell_attention_forward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *q, const float *k,
                                      const float *v, const float *table_q, const float *table_k, const float *table_v, float *out,
                                      float *ml, float *pbuf) {
-    launch_cell_fwd<float>(plan, h, hdim, L, q, k, v, table_q, table_k, table_v, out, ml, pbuf);
+    launch_cell_fwd<float>(begin_launch().stream, plan, h, hdim, L, q, k, v, table_q, table_k, table_v, out, ml, pbuf);
 }
 void cell_attention_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const float *q,
                                       const float *k, const float *v, const float *out, const float *table_q, const float *table_k,
                                       const float *table_v, const float *pbuf, float *gsbuf, float *grad_q, float *grad_k,
                                       float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
-    launch_cell_bwd<float>(plan, h, hdim, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
+    launch_cell_bwd<float>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
                            grad_table_k, grad_table_v);
 }
 // bf16 storage of q / k / v / tables (raw 16-bit patterns), fp32 arithmetic, fp32 outputs and gradients
 void cell_attention_forward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const uint16_t *q, const uint16_t *k,
                                           const uint16_t *v, const uint16_t *table_q, const uint16_t *table_k, const uint16_t *table_v,
                                           float *out, float *ml, float *pbuf) {
-    launch_cell_fwd<bf16_t>(plan, h, hdim, L, q, k, v, table_q, table_k, table_v, out, ml, pbuf);
+    launch_cell_fwd<bf16_t>(begin_launch().stream, plan, h, hdim, L, q, k, v, table_q, table_k, table_v, out, ml, pbuf);
 }
 void cell_attention_backward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const uint16_t *q,
                                            const uint16_t *k, const uint16_t *v, const float *out, const uint16_t *table_q,
                                            const uint16_t *table_k, const uint16_t *table_v, const float *pbuf, float *gsbuf, float *grad_q,
                                            float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
-    launch_cell_bwd<bf16_t>(plan, h, hdim, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
+    launch_cell_bwd<bf16_t>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
                             grad_table_k, grad_table_v);
 }
 

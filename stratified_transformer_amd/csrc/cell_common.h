@@ -160,7 +160,7 @@ static int cell_grid_x(int per_cu, int tasks, int h, int waves) {
 }
 
 // cell_attn_mfma.hip: the forward on the matrix cores (fp32 operands, L <= 80); false = does not apply
-bool cell_fwd_mfma_launch(const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v, const float *table_q,
+bool cell_fwd_mfma_launch(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v, const float *table_q,
                           const float *table_k, const float *table_v, float *out, float *pbuf);
 
 }  // namespace p2

@@ -8,37 +8,54 @@
 
 namespace p2 {
 
-// ---- per-thread launch state (pointops2_set_stream / _set_table_rows / _set_csc) ----
+// ---- per-thread launch state: the stream (pointops2_set_stream, sticky), the last error, the next launch's options ----
 struct LaunchState {
     hipStream_t stream = nullptr;
     const char *error = nullptr;
-    int table_rows = 0;
-    const int *csc_offsets = nullptr;
-    const int *csc_pair = nullptr;
-    const int *csc_query = nullptr;
-    int total_points = 0;  // pointops2_set_point_count: N of the next furthestsampling / knnquery call (0 = unknown)
-    int batch_count = 0;   // pointops2_set_batch_count: b of the next knnquery call (0 = unknown)
-    int key_rows = 0;      // pointops2_set_key_rows: rows of k / v when they differ from the CSR's query rows (0 = same)
-    const int *row_order = nullptr;  // pointops2_set_row_order: the rows in an order that keeps neighbours together (nullptr = by index)
-    int row_order_n = 0;             // ... and the row count it was built for
+    pointops2_launch_opts opts = {};  // pointops2_set_launch_opts: for the next launch only (begin_launch resets them)
 };
-
-// scratch memory lent by the caller (pointops2_set_workspace), thread-local
-struct Workspace {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-Workspace &workspace();
 LaunchState &state();
 
+inline int div_up(int a, int b) { return (a + b - 1) / b; }
+
+// What one launch works with: the caller's stream and the options set for it (include/pointops2_hip.h, PART 2).
+struct Launch {
+    hipStream_t stream;
+    pointops2_launch_opts opts;
+
+    // rows of k / v: opts.key_rows, or the CSR's query rows n_rows when not given
+    int key_rows(int n_rows) const { return opts.key_rows > 0 ? opts.key_rows : n_rows; }
+
+    // ---- rows in window order (opts.row_order) ----
+    // The pair walkers give a wave a row (a query, or a key of the transposed list) and gather the rows of its partners: 64-byte
+    // head rows of k / v / q / grad_out, and - by key - 12-byte snippets of the pair-indexed arrays.  In INDEX order neighbouring
+    // waves work on unrelated windows and every gather goes to memory (the operator path moves 12x its compulsory
+    // bytes).  In an order that keeps the rows of a window together (misc.hip, row_order_kernel: by the row's first partner,
+    // which is the lowest point id of its window) the waves that run at one time share their partners and the second-level
+    // cache serves the gathers.  Workgroups are handed to the eight XCDs in turn and every XCD has its own L2, so the order is
+    // cut into eight runs and workgroup b takes its slots from run b % 8.
+    const int *rows_in_order(int n_rows) const {
+        return (opts.row_order != nullptr && opts.row_order_rows == n_rows && n_rows >= 2048) ? opts.row_order : nullptr;
+    }
+};
+
+// Every exported function that enqueues work calls this exactly once, before anything else (an early return included):
+// it takes the stream and the options and resets the options, whether or not the launch uses them.
+inline Launch begin_launch() {
+    LaunchState &s = state();
+    const Launch ln{s.stream, s.opts};
+    s.opts = pointops2_launch_opts{};
+    return ln;
+}
+
 // fps_bucket.hip: returns false when the bucketed path does not apply (no workspace / unknown N)
-bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, const int *offset, const int *new_offset,
-                       int N_total, int *idx);
+bool fps_bucket_launch(const Launch &ln, int b, int n, int Bref, int log2B, const float *xyz, const int *offset,
+                       const int *new_offset, int *idx);
 
 // fps_bucket.hip: per-batch-element bounding boxes [b][6] (min xyz, max xyz)
 void launch_bbox(int b, const float *xyz, const int *offset, float *bbox, hipStream_t st);
 // knn_grid.hip: returns false when the grid path does not apply (no workspace / unknown n, b / tiny problem)
-bool knn_grid_launch(int m, int k, int n, int b, const float *xyz, const float *new_xyz, const int *offset,
+bool knn_grid_launch(const Launch &ln, int m, int k, const float *xyz, const float *new_xyz, const int *offset,
                      const int *new_offset, int *idx, float *dist2);
 
 inline void set_error(const char *msg) { state().error = msg; }
@@ -127,20 +144,6 @@ inline void allow_big_lds(K kernel, size_t bytes) {
     }
 }
 
-inline int div_up(int a, int b) { return (a + b - 1) / b; }
-
-// ---- rows in window order (pointops2_set_row_order) ----
-// The pair walkers give a wave a row (a query, or a key of the transposed list) and gather the rows of its partners: 64-byte head
-// rows of k / v / q / grad_out, and - by key - 12-byte snippets of the pair-indexed arrays.  In INDEX order neighbouring waves work
-// on unrelated windows and every gather goes to memory (the operator path moves 12x its compulsory bytes).  In an order
-// that keeps the rows of a window together (misc.hip, row_order_kernel: by the row's first partner, which is the lowest point id of
-// its window) the waves that run at one time share their partners and the second-level cache serves the gathers.  Workgroups are
-// handed to the eight XCDs in turn and every XCD has its own L2, so the order is cut into eight runs and workgroup b takes its slots
-// from run b % 8.
-inline const int *rows_in_order(int n_rows) {
-    const LaunchState &s = state();
-    return (s.row_order != nullptr && s.row_order_n == n_rows && n_rows >= 2048) ? s.row_order : nullptr;
-}
 // grid.x for a one-slot-per-wave launch (rows_per_wg waves): eight equal runs
 inline int ordered_grid(int n_rows, int rows_per_wg) { return 8 * div_up(div_up(n_rows, 8), rows_per_wg); }
 inline int64_t div_up64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -44,21 +44,23 @@ using namespace p2;
 extern "C" {
 
 void pointops2_voxel_keys_launcher(int N, int is_f64, const void *coord, double voxel, unsigned long long *keys) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (is_f64)
-        hipLaunchKernelGGL(voxel_key_fnv_kernel<double>, dim3(div_up(N, 256)), dim3(256), 0, state().stream, N, (const double *)coord, voxel, keys);
+        hipLaunchKernelGGL(voxel_key_fnv_kernel<double>, dim3(div_up(N, 256)), dim3(256), 0, st, N, (const double *)coord, voxel, keys);
     else
-        hipLaunchKernelGGL(voxel_key_fnv_kernel<float>, dim3(div_up(N, 256)), dim3(256), 0, state().stream, N, (const float *)coord, (float)voxel, keys);
+        hipLaunchKernelGGL(voxel_key_fnv_kernel<float>, dim3(div_up(N, 256)), dim3(256), 0, st, N, (const float *)coord, (float)voxel, keys);
     check_launch();
 }
 
 void pointops2_crop_dist_launcher(int N, int is_f64, const void *coord, int seed, void *dist) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (seed < 0 || seed >= N) { set_error("pointops2_crop_dist: seed point out of range"); return; }
     if (is_f64)
-        hipLaunchKernelGGL(crop_dist_kernel<double>, dim3(div_up(N, 256)), dim3(256), 0, state().stream, N, (const double *)coord, seed, (double *)dist);
+        hipLaunchKernelGGL(crop_dist_kernel<double>, dim3(div_up(N, 256)), dim3(256), 0, st, N, (const double *)coord, seed, (double *)dist);
     else
-        hipLaunchKernelGGL(crop_dist_kernel<float>, dim3(div_up(N, 256)), dim3(256), 0, state().stream, N, (const float *)coord, seed, (float *)dist);
+        hipLaunchKernelGGL(crop_dist_kernel<float>, dim3(div_up(N, 256)), dim3(256), 0, st, N, (const float *)coord, seed, (float *)dist);
     check_launch();
 }
 

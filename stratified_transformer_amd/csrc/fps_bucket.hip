@@ -29,11 +29,6 @@
 
 namespace p2 {
 
-Workspace &workspace() {
-    static thread_local Workspace w;
-    return w;
-}
-
 constexpr int FPS_MAX_BUCKETS = 2048;
 
 // maximum over lanes 0..15 only (values in the first row): four row steps, result in every lane of row 0
@@ -722,25 +717,17 @@ __global__ void fps_head_offsets_kernel(int b, int head, const int *__restrict__
     }
 }
 
-struct FpsResume {
-    const int *prev_idx = nullptr;
-    const int *prev_offset = nullptr;
-    bool unordered = false;  // pointops2_set_fps_hint: the caller knows the cloud is in no selection order (no identity-prefix probe)
-};
-FpsResume &fps_resume() {
-    static thread_local FpsResume r;
-    return r;
-}
-
-// returns false when the bucket path does not apply (caller falls back to the block kernel)
-bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, const int *offset, const int *new_offset,
-                       int N_total, int *idx) {
-    Workspace &w = workspace();
-    if (w.ptr == nullptr || N_total <= 0) return false;
+// returns false when the bucket path does not apply (caller falls back to the block kernel).  Reads the launch options
+// workspace / workspace_bytes, point_count (N_total), fps_prev_idx / fps_prev_new_offset (resume) and fps_unordered.
+bool fps_bucket_launch(const Launch &ln, int b, int n, int Bref, int log2B, const float *xyz, const int *offset,
+                       const int *new_offset, int *idx) {
+    const pointops2_launch_opts &o = ln.opts;
+    const int N_total = o.point_count;
+    if (o.workspace == nullptr || N_total <= 0) return false;
     const size_t need = pointops2_fps_workspace_bytes(b, N_total);
-    if (w.bytes < need) return false;
-    hipStream_t st = state().stream;
-    char *p = reinterpret_cast<char *>(w.ptr);
+    if (o.workspace_bytes < need) return false;
+    const hipStream_t st = ln.stream;
+    char *p = reinterpret_cast<char *>(o.workspace);
     const size_t f4 = al((size_t)N_total * 4), f8 = al((size_t)N_total * 8), f16 = al((size_t)N_total * 16);
     // persistent part of the workspace (what a resumed call needs)
     float4 *pts = (float4 *)p; p += f16;
@@ -758,10 +745,8 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
     int *head_offset = (int *)p; p += al((size_t)b * 4);            // the chain's head, sampled step by step (below)
     int *head_idx = (int *)p; p += al((size_t)b * FPS_HEAD * 4);
     void *cub_tmp = p;
-    size_t cub_bytes = w.bytes - (size_t)(p - reinterpret_cast<char *>(w.ptr));
-    FpsResume rs = fps_resume();
-    fps_resume() = FpsResume();
-    if (rs.prev_idx == nullptr) {
+    size_t cub_bytes = o.workspace_bytes - (size_t)(p - reinterpret_cast<char *>(o.workspace));
+    if (o.fps_prev_idx == nullptr) {
         hipLaunchKernelGGL(fps_bbox_kernel, dim3(b), dim3(BBOX_T), 0, st, xyz, offset, bbox);
         hipLaunchKernelGGL(fps_morton_kernel, dim3(div_up(N_total, 256)), dim3(256), 0, st, N_total, b, xyz, offset, bbox, keys_in, vals_in);
         hipError_t e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_in, keys_out, (const int *)vals_in, sorig, N_total, 0,
@@ -771,13 +756,13 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
     }
     // identity-prefix verification (exact; see above): a cheap probe of the first 64 steps, then everything
     const int *verified = nullptr;
-    if (!rs.unordered) {
+    if (!o.fps_unordered) {
         hipLaunchKernelGGL(fps_verify_init_kernel, dim3(div_up(b, 64)), dim3(64), 0, st, b, offset, new_offset, first_bad);
         hipLaunchKernelGGL(fps_verify_threshold_kernel, dim3(1, b), dim3(VER_T), 0, st, Bref, log2B, 1, xyz, offset, new_offset, first_bad, thr);
         hipLaunchKernelGGL(fps_verify_scan_kernel, dim3(div_up(n, VER_P), b), dim3(VER_T), 0, st, Bref, log2B, 1, 64, xyz, offset, new_offset, thr, first_bad);
         hipLaunchKernelGGL(fps_verify_threshold_kernel, dim3(div_up(n, VER_P), b), dim3(VER_T), 0, st, Bref, log2B, 64, xyz, offset, new_offset, first_bad, thr);
         hipLaunchKernelGGL(fps_verify_scan_kernel, dim3(div_up(n, VER_P), b), dim3(VER_T), 0, st, Bref, log2B, 64, 0x7fffffff, xyz, offset, new_offset, thr, first_bad);
-        hipLaunchKernelGGL(fps_rebuild_kernel, dim3(div_up(n, VER_P), b), dim3(VER_T), 0, st, xyz, offset, rs.prev_offset, first_bad, inv, pts);
+        hipLaunchKernelGGL(fps_rebuild_kernel, dim3(div_up(n, VER_P), b), dim3(VER_T), 0, st, xyz, offset, o.fps_prev_new_offset, first_bad, inv, pts);
         verified = first_bad;
     }
     const int BSZ = 64 * div_up(n, 64 * FPS_MAX_BUCKETS);
@@ -793,7 +778,7 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
     // same state conventions, same sequence.
     static const bool stepwise = getenv("P2_FPS_STEPWISE") != nullptr;
     if (!stepwise && fps_lazy_groups(n) > 0) {
-        const int *pidx = rs.prev_idx, *poff = rs.prev_offset;
+        const int *pidx = o.fps_prev_idx, *poff = o.fps_prev_new_offset;
         if (pidx == nullptr && n >= 8192) {
             hipLaunchKernelGGL(fps_head_offsets_kernel, dim3(1), dim3(64), 0, st, b, FPS_HEAD, new_offset, head_offset);
             step_by_step(head_offset, nullptr, nullptr, head_idx);
@@ -804,7 +789,7 @@ bool fps_bucket_launch(int b, int n, int Bref, int log2B, const float *xyz, cons
         fps_lazy_launch(b, n, Bref, log2B, xyz, offset, new_offset, pts, rank, pidx, poff, verified, idx, xchg, st);
         return true;
     }
-    step_by_step(new_offset, rs.prev_idx, rs.prev_offset, idx);
+    step_by_step(new_offset, o.fps_prev_idx, o.fps_prev_new_offset, idx);
     held_cus_note(st, b);
     return true;
 }
@@ -815,22 +800,10 @@ using namespace p2;
 
 extern "C" {
 
-void pointops2_set_workspace(void *ptr, size_t bytes) {
-    workspace().ptr = ptr;
-    workspace().bytes = bytes;
-}
-
 size_t pointops2_fps_workspace_bytes(int b, int N) {
     if (b <= 0 || N <= 0) return 0;
     return al((size_t)N * 16) + 4 * al((size_t)N * 4) + 3 * al((size_t)N * 8) + al((size_t)b * 6 * 4) + al((size_t)b * 4) + al((size_t)b * LZ_XCHG) + al((size_t)b * 4) + al((size_t)b * FPS_HEAD * 4) +
            al(fps_cub_bytes(b, N));
 }
-
-void pointops2_set_fps_resume(const int *prev_idx, const int *prev_offset) {
-    fps_resume().prev_idx = prev_idx;
-    fps_resume().prev_offset = prev_offset;
-}
-
-void pointops2_set_fps_hint(int unordered) { fps_resume().unordered = unordered != 0; }
 
 }  // extern "C"

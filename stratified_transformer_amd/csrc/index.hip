@@ -419,8 +419,9 @@ using namespace p2;
 extern "C" {
 
 void pointops2_bbox_launcher(int N, const float *xyz, float *out6) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
-    hipLaunchKernelGGL(bbox_kernel, dim3(1), dim3(1024), 0, state().stream, N, xyz, out6);
+    hipLaunchKernelGGL(bbox_kernel, dim3(1), dim3(1024), 0, st, N, xyz, out6);
     check_launch();
 }
 
@@ -433,9 +434,9 @@ size_t pointops2_index_workspace_bytes(int N) {
 void pointops2_window_partition_launcher(int N, int b, const float *xyz, const int *offset, const float *bbox6, float size,
                                          float shift, int key_bits, int *cluster, int *order, int *starts, int *n_windows, void *ws,
                                          size_t ws_bytes) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (ws_bytes < pointops2_index_workspace_bytes(N)) { set_error("pointops2_window_partition: workspace too small"); return; }
-    hipStream_t st = state().stream;
     char *p = reinterpret_cast<char *>(ws);
     unsigned long long *keys_in = (unsigned long long *)p; p += al((size_t)N * 8);
     unsigned long long *keys_out = (unsigned long long *)p; p += al((size_t)N * 8);
@@ -465,9 +466,9 @@ size_t pointops2_row_order_workspace_bytes(int N) {
 // order [N]: the rows of the CSR pair list (offsets [N+1], index1 [M]) sorted by their first partner, ties by row id - rows of one
 // window become neighbours (common.h, rows_in_order)
 void pointops2_row_order_launcher(int N, int M, const int *offsets, const int *index1, int *order, void *ws, size_t ws_bytes) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (ws_bytes < pointops2_row_order_workspace_bytes(N)) { set_error("pointops2_row_order: workspace too small"); return; }
-    hipStream_t st = state().stream;
     char *p = reinterpret_cast<char *>(ws);
     unsigned *keys_in = (unsigned *)p; p += al((size_t)N * 4);
     unsigned *keys_out = (unsigned *)p; p += al((size_t)N * 4);
@@ -490,10 +491,10 @@ size_t pointops2_partitions4_workspace_bytes(int N) {
 // (window); *overflow = 1 when a voxel coordinate does not fit the fixed key (the outputs are then in range but meaningless)
 void pointops2_window_partitions4_launcher(int N, int b, const float *xyz, const int *offset, const float *bbox6, float window, int *cluster,
                                            int *order, int *starts, int *n_windows, int *overflow, void *ws, size_t ws_bytes) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if ((size_t)N * 4 >= (size_t)1 << 30) { set_error("pointops2_window_partitions4: too many points"); return; }
     if (ws_bytes < pointops2_partitions4_workspace_bytes(N)) { set_error("pointops2_window_partitions4: workspace too small"); return; }
-    hipStream_t st = state().stream;
     const int n4 = 4 * N;
     char *p = reinterpret_cast<char *>(ws);
     unsigned long long *keys_in = (unsigned long long *)p; p += al((size_t)n4 * 8);
@@ -519,8 +520,9 @@ void pointops2_window_partitions4_launcher(int N, int b, const float *xyz, const
 }
 
 void pointops2_window_coord_launcher(int N, const float *xyz, const float *bbox6, float window, int shifted, float *wc) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
-    hipLaunchKernelGGL(window_coord_kernel, dim3(div_up(N * 3, 256)), dim3(256), 0, state().stream, N, xyz, bbox6, window, shifted, wc);
+    hipLaunchKernelGGL(window_coord_kernel, dim3(div_up(N * 3, 256)), dim3(256), 0, st, N, xyz, bbox6, window, shifted, wc);
     check_launch();
 }
 
@@ -528,9 +530,9 @@ void pointops2_window_coord_launcher(int N, const float *xyz, const float *bbox6
 void pointops2_sampled_buckets_launcher(int N, int m, const int *sample_idx, const int *l_order, const int *l_starts,
                                         const int *l_n_windows, int *sampled /*[N] zeroed by the caller*/, int *ls /*[m]*/,
                                         int *ls_starts /*[N+1]*/, void *ws, size_t ws_bytes) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (ws_bytes < pointops2_index_workspace_bytes(N)) { set_error("pointops2_sampled_buckets: workspace too small"); return; }
-    hipStream_t st = state().stream;
     char *p = reinterpret_cast<char *>(ws);
     int *flag = (int *)p; p += al(((size_t)N + 1) * 4);
     int *pos = (int *)p; p += al(((size_t)N + 1) * 4);
@@ -548,9 +550,9 @@ void pointops2_sampled_buckets_launcher(int N, int m, const int *sample_idx, con
 // pass 1: offsets[N+1] (exclusive scan of the per-query key counts; offsets[N] = M)
 void pointops2_pairs_count_launcher(int N, const int *s_cluster, const int *s_starts, const int *l_cluster, const int *ls,
                                     const int *ls_starts, const float *wc, int *offsets, void *ws, size_t ws_bytes) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (ws_bytes < pointops2_index_workspace_bytes(N)) { set_error("pointops2_pairs_count: workspace too small"); return; }
-    hipStream_t st = state().stream;
     char *p = reinterpret_cast<char *>(ws);
     int *total = (int *)p; p += al(((size_t)N + 1) * 4);
     void *tmp = p;
@@ -566,10 +568,11 @@ void pointops2_pairs_count_launcher(int N, const int *s_cluster, const int *s_st
 void pointops2_pairs_fill_launcher(int N, const float *xyz, float window, float quant, const int *s_cluster, const int *s_order,
                                    const int *s_starts, const int *l_cluster, const int *ls, const int *ls_starts, const float *wc,
                                    const int *offsets, int *index_0, int *index_1, int *rel_idx) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     // 2 * self.window_size is a Python float product rounded to fp32 when added to the tensor (:188)
     const float two_w = (float)(2.0 * (double)window);
-    hipLaunchKernelGGL(pairs_fill_kernel, dim3(div_up(N, 4)), dim3(256), 0, state().stream, N, xyz, two_w, quant, s_cluster, s_order, s_starts,
+    hipLaunchKernelGGL(pairs_fill_kernel, dim3(div_up(N, 4)), dim3(256), 0, st, N, xyz, two_w, quant, s_cluster, s_order, s_starts,
                        l_cluster, ls, ls_starts, wc, offsets, index_0, index_1, rel_idx);
     check_launch();
 }
@@ -612,9 +615,9 @@ static CellWs cell_ws(int N, void *ws, size_t ws_bytes) {
 // max_queries queries, the parents.  A caller runs it BESIDE the stage's sampler; `ws` must stay untouched until pass 1b has run.
 void pointops2_cell_plan_prepare_launcher(int N, int max_queries, const int *s_cluster, const int *l_cluster, int *cell_order,
                                           int *parent_first, int *counts, void *ws, size_t ws_bytes) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (ws_bytes < pointops2_cell_plan_workspace_bytes(N)) { set_error("pointops2_cell_plan_prepare: workspace too small"); return; }
-    hipStream_t st = state().stream;
     CellWs w = cell_ws(N, ws, ws_bytes);
     const int g = div_up(N, 256);
     int lbits = 1;
@@ -645,9 +648,9 @@ void pointops2_cell_plan_prepare_launcher(int N, int max_queries, const int *s_c
 void pointops2_cell_plan_sizes_launcher(int N, const int *s_cluster, const int *s_starts, const int *l_cluster, const int *ls_starts,
                                         const int *cell_order, int *qcell, int *cell_desc, int *cell_qstart, int *cell_kbase,
                                         int *cell_pbase, int *cell_perm, int *counts, void *ws, size_t ws_bytes) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (ws_bytes < pointops2_cell_plan_workspace_bytes(N)) { set_error("pointops2_cell_plan_sizes: workspace too small"); return; }
-    hipStream_t st = state().stream;
     CellWs w = cell_ws(N, ws, ws_bytes);
     const int g = div_up(N, 256);
     hipLaunchKernelGGL(cell_describe_kernel, dim3(g), dim3(256), 0, st, N, cell_order, w.flags, w.rank, s_cluster, s_starts, l_cluster, ls_starts,
@@ -665,7 +668,7 @@ void pointops2_cell_plan_sizes_launcher(int N, const int *s_cluster, const int *
     check_launch();
 }
 
-// pass 1 in one call (1a + 1b)
+// pass 1 in one call (1a + 1b; no begin_launch() here: each half takes the stream and resets the options, of which it reads none)
 void pointops2_cell_plan_count_launcher(int N, int max_queries, const int *s_cluster, const int *s_starts, const int *l_cluster,
                                         const int *ls_starts, int *cell_order, int *qcell, int *cell_desc, int *cell_qstart,
                                         int *cell_kbase, int *cell_pbase, int *cell_perm, int *parent_first, int *counts, void *ws,
@@ -681,10 +684,11 @@ void pointops2_cell_plan_fill_launcher(int N, const float *xyz, float window, fl
                                        const float *wc, const int *cell_order, const int *qcell, const int *cell_qstart,
                                        const int *cell_desc, const int *cell_kbase, const int *cell_pbase, int *cell_keys, int *kcell,
                                        unsigned *relp) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0) return;
     if (L < 1 || L > 255) { set_error("pointops2_cell_plan_fill: table rows L must be in 1..255 (packed rel-pos index)"); return; }
     const float two_w = (float)(2.0 * (double)window);
-    hipLaunchKernelGGL(cell_fill_kernel, dim3(div_up(N, 4)), dim3(256), 0, state().stream, N, xyz, two_w, quant, L, s_order, ls, wc, cell_order,
+    hipLaunchKernelGGL(cell_fill_kernel, dim3(div_up(N, 4)), dim3(256), 0, st, N, xyz, two_w, quant, L, s_order, ls, wc, cell_order,
                        qcell, cell_qstart, cell_desc, cell_kbase, cell_pbase, cell_keys, kcell, relp);
     check_launch();
 }

@@ -122,14 +122,12 @@ extern "C" {
 
 void knnquery_cuda_launcher(int m, int nsample, const float *xyz, const float *new_xyz,
                             const int *offset, const int *new_offset, int *idx, float *dist2) {
+    const Launch ln = begin_launch();
     if (m <= 0) return;
     if (nsample < 1 || nsample > 100) { set_error("knnquery: nsample must be in [1, 100]"); return; }
-    hipStream_t st = state().stream;
-    const int n_total = state().total_points, nbatch = state().batch_count;
-    state().total_points = 0;
-    state().batch_count = 0;
-    // grid-accelerated exact kNN (knn_grid.hip) when the caller lent scratch memory and announced n and b
-    if (knn_grid_launch(m, nsample, n_total, nbatch, xyz, new_xyz, offset, new_offset, idx, dist2)) {
+    const hipStream_t st = ln.stream;
+    // grid-accelerated exact kNN (knn_grid.hip) when the caller lent scratch memory and gave n and b
+    if (knn_grid_launch(ln, m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2)) {
         check_launch();
         return;
     }

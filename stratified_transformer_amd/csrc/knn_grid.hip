@@ -16,8 +16,8 @@
 //   3. a query whose k+1 best contain two equal distances is put on a replay list and recomputed by
 //      the literal heap procedure of knn.hip (bit-exact ties); everything else is final.
 //
-// Needs scratch memory (pointops2_set_workspace) and the candidate / batch counts
-// (pointops2_set_point_count, pointops2_set_batch_count); without them knn.hip's full scan runs.
+// Needs scratch memory (launch_opts.workspace) and the candidate / batch counts (launch_opts.point_count,
+// launch_opts.batch_count); without them knn.hip's full scan runs.
 #include "common.h"
 #include <hipcub/hipcub.hpp>
 
@@ -414,15 +414,17 @@ static size_t knn_ws_bytes(int n, int m, int b) {
            al(knn_cub_bytes(max(n, m), b));
 }
 
-// returns false when the grid path does not apply (caller runs the full scan)
-bool knn_grid_launch(int m, int k, int n, int b, const float *xyz, const float *new_xyz, const int *offset,
+// returns false when the grid path does not apply (caller runs the full scan).  Reads the launch options workspace /
+// workspace_bytes, point_count (n) and batch_count (b).
+bool knn_grid_launch(const Launch &ln, int m, int k, const float *xyz, const float *new_xyz, const int *offset,
                      const int *new_offset, int *idx, float *dist2) {
-    Workspace &w = workspace();
-    if (w.ptr == nullptr || n <= 0 || b <= 0 || (long long)KNN_CELL_CAP * b > (1ll << 30)) return false;
-    if (w.bytes < knn_ws_bytes(n, m, b)) return false;
+    const pointops2_launch_opts &o = ln.opts;
+    const int n = o.point_count, b = o.batch_count;
+    if (o.workspace == nullptr || n <= 0 || b <= 0 || (long long)KNN_CELL_CAP * b > (1ll << 30)) return false;
+    if (o.workspace_bytes < knn_ws_bytes(n, m, b)) return false;
     if ((long long)m * n < (1ll << 22)) return false;  // small problems: the scan is as fast as building a grid
-    hipStream_t st = state().stream;
-    char *p = reinterpret_cast<char *>(w.ptr);
+    const hipStream_t st = ln.stream;
+    char *p = reinterpret_cast<char *>(o.workspace);
     KnnPlan *plan = (KnnPlan *)p; p += al(sizeof(KnnPlan));
     float *bbox = (float *)p; p += al((size_t)b * 24);
     unsigned *keys_in = (unsigned *)p; p += al((size_t)n * 4);
@@ -438,7 +440,7 @@ bool knn_grid_launch(int m, int k, int n, int b, const float *xyz, const float *
     int *qvals_in = (int *)p; p += al((size_t)m * 4);
     int *qperm = (int *)p; p += al((size_t)m * 4);
     void *cub_tmp = p;
-    size_t cub_bytes = w.bytes - (size_t)(p - reinterpret_cast<char *>(w.ptr));
+    size_t cub_bytes = o.workspace_bytes - (size_t)(p - reinterpret_cast<char *>(o.workspace));
 
     (void)hipMemsetAsync(replay_count, 0, sizeof(int), st);
     launch_bbox(b, xyz, offset, bbox, st);

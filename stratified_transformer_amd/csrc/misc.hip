@@ -220,54 +220,45 @@ const char *pointops2_last_error(void) {
     return e;
 }
 void pointops2_diag_set_fps_patience(unsigned long long ticks_100mhz) { g_fps_patience = ticks_100mhz; }
-int pointops2_abi_version(void) { return 2; }  // 2: pointops2_cell_plan.table_rows, pointops2_csr_matches_launcher
-void pointops2_set_table_rows(int L) { state().table_rows = L; }
-void pointops2_set_point_count(int N) { state().total_points = N; }
-void pointops2_set_batch_count(int b) { state().batch_count = b; }
-void pointops2_set_key_rows(int n) { state().key_rows = n; }
-void pointops2_set_row_order(const int *order, int n_rows) {
-    LaunchState &s = state();
-    s.row_order = order;
-    s.row_order_n = order != nullptr ? n_rows : 0;
-}
-void pointops2_set_csc(const int *csc_offsets, const int *csc_pair, const int *csc_query) {
-    LaunchState &s = state();
-    s.csc_offsets = csc_offsets;
-    s.csc_pair = csc_pair;
-    s.csc_query = csc_query;
-}
+int pointops2_abi_version(void) { return 3; }  // 2: pointops2_cell_plan.table_rows, pointops2_csr_matches_launcher; 3: pointops2_launch_opts
+void pointops2_set_launch_opts(const pointops2_launch_opts *opts) { state().opts = opts != nullptr ? *opts : pointops2_launch_opts{}; }
 
 void grouping_forward_cuda_launcher(int m, int nsample, int c, const float *input, const int *idx, float *output) {
+    const hipStream_t st = begin_launch().stream;
     const int64_t total = (int64_t)m * nsample * c;
     if (total <= 0) return;
-    hipLaunchKernelGGL(grouping_fwd_kernel, dim3(div_up64(total, 256)), dim3(256), 0, state().stream, total, c, input, idx, output);
+    hipLaunchKernelGGL(grouping_fwd_kernel, dim3(div_up64(total, 256)), dim3(256), 0, st, total, c, input, idx, output);
     check_launch();
 }
 void grouping_backward_cuda_launcher(int m, int nsample, int c, const float *grad_output, const int *idx, float *grad_input) {
+    const hipStream_t st = begin_launch().stream;
     const int64_t total = (int64_t)m * nsample * c;
     if (total <= 0) return;
-    hipLaunchKernelGGL(grouping_bwd_kernel, dim3(div_up64(total, 256)), dim3(256), 0, state().stream, total, c, grad_output, idx, grad_input);
+    hipLaunchKernelGGL(grouping_bwd_kernel, dim3(div_up64(total, 256)), dim3(256), 0, st, total, c, grad_output, idx, grad_input);
     check_launch();
 }
 void interpolation_forward_cuda_launcher(int n, int c, int k, const float *input, const int *idx, const float *weight, float *output) {
+    const hipStream_t st = begin_launch().stream;
     if ((int64_t)n * c <= 0) return;
-    hipLaunchKernelGGL(interp_fwd_kernel, dim3(div_up64((int64_t)n * c, 256)), dim3(256), 0, state().stream, n, c, k, input, idx, weight, output);
+    hipLaunchKernelGGL(interp_fwd_kernel, dim3(div_up64((int64_t)n * c, 256)), dim3(256), 0, st, n, c, k, input, idx, weight, output);
     check_launch();
 }
 void interpolation_backward_cuda_launcher(int n, int c, int k, const float *grad_output, const int *idx, const float *weight, float *grad_input) {
+    const hipStream_t st = begin_launch().stream;
     if ((int64_t)n * c <= 0) return;
-    hipLaunchKernelGGL(interp_bwd_kernel, dim3(div_up64((int64_t)n * c, 256)), dim3(256), 0, state().stream, n, c, k, grad_output, idx, weight, grad_input);
+    hipLaunchKernelGGL(interp_bwd_kernel, dim3(div_up64((int64_t)n * c, 256)), dim3(256), 0, st, n, c, k, grad_output, idx, weight, grad_input);
     check_launch();
 }
 
 void csr_expand_launcher(int N, int M, const int *offsets, int *index0) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0 || M <= 0) return;
-    hipLaunchKernelGGL(csr_expand_kernel, dim3(div_up(N, 4)), dim3(256), 0, state().stream, N, M, offsets, index0);
+    hipLaunchKernelGGL(csr_expand_kernel, dim3(div_up(N, 4)), dim3(256), 0, st, N, M, offsets, index0);
     check_launch();
 }
 
 void pointops2_csr_matches_launcher(int N, int M, const int *offsets, const void *index, int index_is_int64, int *bad) {
-    hipStream_t st = state().stream;
+    const hipStream_t st = begin_launch().stream;
     // N == 0 describes M == 0 only; a non-empty pair list needs at least one row
     if (hipMemsetAsync(bad, (N <= 0 && M > 0) ? 1 : 0, sizeof(int), st) != hipSuccess) { set_error("pointops2_csr_matches: memset failed"); return; }
     if (N <= 0) return;
@@ -286,11 +277,11 @@ size_t pointops2_csc_workspace_bytes(int N, int M) {
 
 void pointops2_csc_build(int N, int M, const int *index0_offsets, const int *index1,
                          int *csc_offsets, int *csc_pair, int *csc_query, void *workspace, size_t workspace_bytes) {
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    const int NK = state().key_rows > 0 ? state().key_rows : N;  // keys may outnumber the CSR's queries (sharded attention)
-    state().key_rows = 0;
+    const int NK = ln.key_rows(N);  // keys may outnumber the CSR's queries (sharded attention)
     if (workspace_bytes < pointops2_csc_workspace_bytes(NK > N ? NK : N, M)) { set_error("pointops2_csc_build: workspace too small"); return; }
-    hipStream_t st = state().stream;
+    const hipStream_t st = ln.stream;
     char *ws = reinterpret_cast<char *>(workspace);
     const size_t seg = align256((size_t)M * sizeof(int));
     int *index0 = reinterpret_cast<int *>(ws);

@@ -15,7 +15,7 @@
 //  * Backward: table gradients are accumulated in LDS (ds_add_f32) and flushed once per workgroup
 //    with global atomics — the reference issues 6-8 global atomics per (pair, channel) into a
 //    9216-float table.  Key-side gradients are produced by key through the CSC view
-//    (pointops2_set_csc); without it the by-query kernel falls back to global atomics.
+//    (launch_opts.csc_*); without it the by-query kernel falls back to global atomics.
 #include "rpe_common.h"
 #include <cstdlib>
 
@@ -551,9 +551,9 @@ static int pick_hg(int h, int L, int D, int narr) {
     return hg;
 }
 
-static int table_rows_or_error() {
-    const int L = state().table_rows;
-    if (L <= 0) set_error("rel-pos tables: call pointops2_set_table_rows(L) before this launcher");
+static int table_rows_or_error(const Launch &ln) {
+    const int L = ln.opts.table_rows;
+    if (L <= 0) set_error("rel-pos tables: this launcher needs the tables' row count L (pointops2_launch_opts.table_rows)");
     return L;
 }
 
@@ -599,23 +599,24 @@ void dot_prod_with_idx_forward_cuda_launcher_v3(int N, int M, int h, int hdim, i
                                                 const float *table_q, const float *table_k, const int *rel_idx,
                                                 float *output) {
     (void)n_max;
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    const int L = state().table_rows;
-    if (L <= 0) {  // table length not announced: the generic global-memory kernels (rpe_fallback.hip)
-        a2_fwd_global(N, M, h, hdim, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output);
+    const hipStream_t st = ln.stream;
+    const int L = ln.opts.table_rows;
+    if (L <= 0) {  // table length not given: the generic global-memory kernels (rpe_fallback.hip)
+        a2_fwd_global(st, N, M, h, hdim, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output);
         check_launch();
         return;
     }
-    hipStream_t st = state().stream;
     if (hdim == 16) P2_LAUNCH_HG(16, 2, {
         allow_big_lds(a2_fwd_kernel<Dc, HGc>, lds_bytes);
         hipLaunchKernelGGL((a2_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
-                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output, rows_in_order(N));
+                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output, ln.rows_in_order(N));
     })
     else if (hdim == 32) P2_LAUNCH_HG(32, 2, {
         allow_big_lds(a2_fwd_kernel<Dc, HGc>, lds_bytes);
         hipLaunchKernelGGL((a2_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
-                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output, rows_in_order(N));
+                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output, ln.rows_in_order(N));
     })
     else { set_error("d != 16 and d != 32"); return; }
     check_launch();
@@ -624,15 +625,16 @@ void dot_prod_with_idx_forward_cuda_launcher_v3(int N, int M, int h, int hdim, i
 void window_logits_softmax_forward_launcher(int N, int M, int h, int hdim, const float *q, const int *index_q_offsets,
                                              const float *k, const int *index_k, const float *table_q, const float *table_k,
                                              const int *rel_idx, float *attn) {
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    const int L = table_rows_or_error();
+    const int L = table_rows_or_error(ln);
     if (L <= 0) return;
     if (hdim != 16) { set_error("window_logits_softmax: d != 16"); return; }
-    hipStream_t st = state().stream;
+    const hipStream_t st = ln.stream;
     P2_LAUNCH_HG(16, 2, {
         allow_big_lds(wlogit_softmax_kernel<HGc>, lds_bytes);
         hipLaunchKernelGGL((wlogit_softmax_kernel<HGc>), dim3(persistent_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
-                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, attn, rows_in_order(N));
+                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, attn, ln.rows_in_order(N));
     })
     check_launch();
 }
@@ -642,15 +644,13 @@ void window_attention_backward_launcher(int N, int M, int h, int hdim, const flo
                                         const float *table_q, const float *table_k, const float *table_v, const int *rel_idx,
                                         float *grad_logit, float *grad_q, float *grad_k, float *grad_v, float *grad_table_q,
                                         float *grad_table_k, float *grad_table_v) {
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    const int L = table_rows_or_error();
+    const int L = table_rows_or_error(ln);
     if (L <= 0) return;
-    const LaunchState &ls = state();
-    const int NK = ls.key_rows > 0 ? ls.key_rows : N;
-    if (!wattn_bwd(N, NK, M, h, hdim, L, grad_out, q, k, v, attn, index0_offsets, index1, table_q, table_k, table_v, rel_idx,
-                   ls.csc_offsets, ls.csc_pair, ls.csc_query, grad_logit, grad_q, grad_k, grad_v, grad_table_q, grad_table_k,
-                   grad_table_v)) {
-        set_error("window_attention_backward: needs d = 16, L <= 80 and a key-major view (pointops2_set_csc)");
+    if (!wattn_bwd(ln, N, M, h, hdim, L, grad_out, q, k, v, attn, index0_offsets, index1, table_q, table_k, table_v, rel_idx,
+                   grad_logit, grad_q, grad_k, grad_v, grad_table_q, grad_table_k, grad_table_v)) {
+        set_error("window_attention_backward: needs d = 16, L <= 80 and a key-major view (pointops2_launch_opts.csc_*)");
         return;
     }
     check_launch();
@@ -662,20 +662,20 @@ void dot_prod_with_idx_backward_cuda_launcher_v3(int N, int M, int h, int hdim, 
                                                  const int *rel_idx, float *grad_q, float *grad_k,
                                                  float *grad_table_q, float *grad_table_k) {
     (void)n_max;
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    const int L = state().table_rows;
+    const hipStream_t st = ln.stream;
+    const int L = ln.opts.table_rows;
     if (L <= 0) {
-        a2_bwd_global(N, M, h, hdim, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q, grad_table_k);
+        a2_bwd_global(st, N, M, h, hdim, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q, grad_table_k);
         check_launch();
         return;
     }
-    hipStream_t st = state().stream;
-    const LaunchState &ls = state();
-    const int *co = ls.csc_offsets, *cp = ls.csc_pair;
-    const int NK = ls.key_rows > 0 ? ls.key_rows : N;
+    const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair;
+    const int NK = ln.key_rows(N);
     // D=16, L<=80 with a CSC view: table gradients on the matrix cores (rpe_bwd_mfma.hip)
-    if (a2_bwd_mfma(N, NK, M, h, hdim, L, grad_out, q, index_q_offsets, k, table_q, table_k, rel_idx, co, cp, grad_q, grad_k,
-                    grad_table_q, grad_table_k)) {
+    if (a2_bwd_mfma(ln, N, M, h, hdim, L, grad_out, q, index_q_offsets, k, table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q,
+                    grad_table_k)) {
         check_launch();
         return;
     }
@@ -710,23 +710,24 @@ void attention_step2_with_rel_pos_value_forward_cuda_launcher_v2(int N, int M, i
                                                                  const int *index0_offsets, const int *index1,
                                                                  const float *table, const int *rel_idx, float *output) {
     (void)n_max;
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    const int L = state().table_rows;
+    const hipStream_t st = ln.stream;
+    const int L = ln.opts.table_rows;
     if (L <= 0) {
-        a4_fwd_global(N, M, h, hdim, attn, v, index0_offsets, index1, table, rel_idx, output);
+        a4_fwd_global(st, N, M, h, hdim, attn, v, index0_offsets, index1, table, rel_idx, output);
         check_launch();
         return;
     }
-    hipStream_t st = state().stream;
     if (hdim == 16) P2_LAUNCH_HG(16, 1, {
         allow_big_lds(a4_fwd_kernel<Dc, HGc>, lds_bytes);
         hipLaunchKernelGGL((a4_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 8, 3), ngroups), dim3(512), lds_bytes, st,
-                           N, h, L, attn, v, index0_offsets, index1, table, rel_idx, output, rows_in_order(N));
+                           N, h, L, attn, v, index0_offsets, index1, table, rel_idx, output, ln.rows_in_order(N));
     })
     else if (hdim == 32) P2_LAUNCH_HG(32, 1, {
         allow_big_lds(a4_fwd_kernel<Dc, HGc>, lds_bytes);
         hipLaunchKernelGGL((a4_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 8, 3), ngroups), dim3(512), lds_bytes, st,
-                           N, h, L, attn, v, index0_offsets, index1, table, rel_idx, output, rows_in_order(N));
+                           N, h, L, attn, v, index0_offsets, index1, table, rel_idx, output, ln.rows_in_order(N));
     })
     else { set_error("d != 16 and d != 32"); return; }
     check_launch();
@@ -738,22 +739,22 @@ void attention_step2_with_rel_pos_value_backward_cuda_launcher_v2(int N, int M, 
                                                                   const float *table, const int *rel_idx,
                                                                   float *grad_attn, float *grad_v, float *grad_table) {
     (void)n_max;
+    const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
-    const int L = state().table_rows;
+    const hipStream_t st = ln.stream;
+    const int L = ln.opts.table_rows;
     if (L <= 0) {
-        a4_bwd_global(N, M, h, hdim, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
+        a4_bwd_global(st, N, M, h, hdim, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
         check_launch();
         return;
     }
-    hipStream_t st = state().stream;
-    const LaunchState &ls = state();
-    const int *co = ls.csc_offsets, *cp = ls.csc_pair, *cq = ls.csc_query;
-    const int NK4 = ls.key_rows > 0 ? ls.key_rows : N;
+    const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair, *cq = ln.opts.csc_query;
+    const int NK4 = ln.key_rows(N);
     if (co && hdim == 16 && L <= 80) {
         ForkJoin fj(st, fork_worthwhile((int64_t)M * h));  // grad_attn, grad_v and grad_table are independent
-        const int *kord = rows_in_order(NK4);
+        const int *kord = ln.rows_in_order(NK4);
         hipLaunchKernelGGL(key_accum_kernel<16>, dim3(kord ? ordered_grid(NK4, 4) : div_up(NK4, 4), div_up(h, 4)), dim3(256), 0, fj.lane(2), NK4, h, co, cq, cp, attn, grad_out, grad_v, kord);
-        a4_bwd_mfma(N, h, hdim, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_table, fj);
+        a4_bwd_mfma(ln, N, h, hdim, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_table, fj);
         check_launch();
         return;
     }
@@ -784,24 +785,27 @@ void attention_step2_with_rel_pos_value_backward_cuda_launcher_v2(int N, int M, 
 void dot_prod_with_idx_forward_cuda_launcher(int N, int M, int h, int hdim, const float *q, const int *index,
                                              const float *table, const int *rel_idx, float *output) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
-    hipLaunchKernelGGL(dot_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, hdim, q, index, table, rel_idx, output);
+    hipLaunchKernelGGL(dot_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, q, index, table, rel_idx, output);
     check_launch();
 }
 void dot_prod_with_idx_backward_cuda_launcher(int N, int M, int h, int hdim, const float *grad_out,
                                               const float *q, const int *index, const float *table,
                                               const int *rel_idx, float *grad_q, float *grad_table) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
-    hipLaunchKernelGGL(dot_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, hdim, grad_out, q, index, table, rel_idx, grad_q, grad_table);
+    hipLaunchKernelGGL(dot_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, grad_out, q, index, table, rel_idx, grad_q, grad_table);
     check_launch();
 }
 void attention_step2_with_rel_pos_value_forward_cuda_launcher(int N, int M, int h, int hdim, const float *attn,
                                                               const float *v, const int *index0, const int *index1,
                                                               const float *table, const int *rel_idx, float *output) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
-    hipLaunchKernelGGL(av_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, hdim, attn, v, index0, index1, table, rel_idx, output);
+    hipLaunchKernelGGL(av_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, attn, v, index0, index1, table, rel_idx, output);
     check_launch();
 }
 void attention_step2_with_rel_pos_value_backward_cuda_launcher(int N, int M, int h, int hdim, const float *grad_out,
@@ -809,8 +813,9 @@ void attention_step2_with_rel_pos_value_backward_cuda_launcher(int N, int M, int
                                                                const float *v, const float *table, const int *rel_idx,
                                                                float *grad_attn, float *grad_v, float *grad_table) {
     (void)N;
+    const hipStream_t st = begin_launch().stream;
     if (M <= 0) return;
-    hipLaunchKernelGGL(av_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, state().stream, M, h, hdim, grad_out, index0, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
+    hipLaunchKernelGGL(av_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, grad_out, index0, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
     check_launch();
 }
 
@@ -819,6 +824,7 @@ void attention_step2_with_rel_pos_value_backward_cuda_launcher(int N, int M, int
 // only drive the reference's work distribution.  index_q/index_k are pair-indexed (unsorted), so it
 // is served by two passes of the v1 single-table kernel (q-side + k-side), which is exactly the
 // identity the reference's own test checks (test_relative_pos_encoding_op_step1_v3.py:60-62).
+// (No begin_launch() here: each v1 call takes the stream and resets the launch options, of which it reads none.)
 void dot_prod_with_idx_forward_cuda_launcher_v2(int N, int M, int h, int hdim, int n_max, int T, const float *q,
                                                 const int *index_q, const float *k, const int *index_k,
                                                 const float *table_q, const float *table_k, const int *rel_idx,

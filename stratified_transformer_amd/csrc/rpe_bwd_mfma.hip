@@ -575,7 +575,7 @@ static void with_heads(int h, F f) {
 }
 
 template <int TA>
-static void launch_table_grad(int N, int h, int L, const float *w, const float *X, const int *offs, const int *pair_map,
+static void launch_table_grad(const Launch &ln, int N, int h, int L, const float *w, const float *X, const int *offs, const int *pair_map,
                               const int *rel, float *grad_table, hipStream_t st) {
     with_heads(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
@@ -583,36 +583,37 @@ static void launch_table_grad(int N, int h, int L, const float *w, const float *
         using G = TableGeo<HG, TA>;
         const size_t lds = G::lds_bytes();
         hipLaunchKernelGGL((table_grad_kernel<HG, TA>), dim3(walk_blocks(N, groups, TG_WAVES, 2), groups), dim3(TG_WAVES * 64), lds, st,
-                           N, h, L, w, X, offs, pair_map, rel, grad_table, rows_in_order(N));
+                           N, h, L, w, X, offs, pair_map, rel, grad_table, ln.rows_in_order(N));
     });
 }
 
 // entry points used by rpe.hip; return false when the shape is outside this file's fast path
-bool a2_bwd_mfma(int N, int NK, int M, int h, int hdim, int L, const float *go, const float *q, const int *offs, const float *k,
-                 const float *table_q, const float *table_k, const int *rel, const int *co, const int *cp,
-                 float *grad_q, float *grad_k, float *gtq, float *gtk) {
+bool a2_bwd_mfma(const Launch &ln, int N, int M, int h, int hdim, int L, const float *go, const float *q, const int *offs, const float *k,
+                 const float *table_q, const float *table_k, const int *rel, float *grad_q, float *grad_k, float *gtq, float *gtk) {
+    const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair;
+    const int NK = ln.key_rows(N);
     if (hdim != 16 || co == nullptr || L < 1 || L > 80) return false;
-    ForkJoin fj(state().stream, fork_worthwhile((int64_t)M * h));  // grad_q, grad_k and the two table gradients are independent
+    ForkJoin fj(ln.stream, fork_worthwhile((int64_t)M * h));  // grad_q, grad_k and the two table gradients are independent
     with_heads(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
         const int groups = div_up(h, HG);
         const size_t lds = (size_t)HG * 3 * L * 16 * sizeof(float);
         hipLaunchKernelGGL((rows_table_sum_kernel<HG, true>), dim3(walk_blocks(NK, groups, 8, 4), groups), dim3(512), lds, fj.lane(0),
-                           NK, h, L, go, co, cp, table_k, rel, grad_k, rows_in_order(NK));
+                           NK, h, L, go, co, cp, table_k, rel, grad_k, ln.rows_in_order(NK));
         hipLaunchKernelGGL((rows_table_sum_kernel<HG, false>), dim3(walk_blocks(N, groups, 8, 4), groups), dim3(512), lds, fj.lane(1),
-                           N, h, L, go, offs, (const int *)nullptr, table_q, rel, grad_q, rows_in_order(N));
+                           N, h, L, go, offs, (const int *)nullptr, table_q, rel, grad_q, ln.rows_in_order(N));
     });
     if (L <= 64) {
-        launch_table_grad<4>(NK, h, L, go, k, co, cp, rel, gtk, fj.lane(2));
-        launch_table_grad<4>(N, h, L, go, q, offs, nullptr, rel, gtq, fj.lane(3));
+        launch_table_grad<4>(ln, NK, h, L, go, k, co, cp, rel, gtk, fj.lane(2));
+        launch_table_grad<4>(ln, N, h, L, go, q, offs, nullptr, rel, gtq, fj.lane(3));
     } else {
-        launch_table_grad<5>(NK, h, L, go, k, co, cp, rel, gtk, fj.lane(2));
-        launch_table_grad<5>(N, h, L, go, q, offs, nullptr, rel, gtq, fj.lane(3));
+        launch_table_grad<5>(ln, NK, h, L, go, k, co, cp, rel, gtk, fj.lane(2));
+        launch_table_grad<5>(ln, N, h, L, go, q, offs, nullptr, rel, gtq, fj.lane(3));
     }
     return true;
 }
 
-bool a4_bwd_mfma(int N, int h, int hdim, int L, const float *go, const int *offs, const int *idx1, const float *attn,
+bool a4_bwd_mfma(const Launch &ln, int N, int h, int hdim, int L, const float *go, const int *offs, const int *idx1, const float *attn,
                  const float *v, const float *table, const int *rel, float *grad_attn, float *grad_table, ForkJoin &fj) {
     if (hdim != 16 || L < 1 || L > 80) return false;
     with_heads(h, [&](auto tag) {
@@ -620,27 +621,29 @@ bool a4_bwd_mfma(int N, int h, int hdim, int L, const float *go, const int *offs
         const int groups = div_up(h, HG);
         const size_t lds = (size_t)HG * 3 * L * 16 * sizeof(float);
         hipLaunchKernelGGL((a4_bwd_attn_kernel<HG>), dim3(walk_blocks(N, groups, 8, 4), groups), dim3(512), lds, fj.lane(0),
-                           N, h, L, go, offs, idx1, v, table, rel, grad_attn, rows_in_order(N));
+                           N, h, L, go, offs, idx1, v, table, rel, grad_attn, ln.rows_in_order(N));
     });
-    if (L <= 64) launch_table_grad<4>(N, h, L, attn, go, offs, nullptr, rel, grad_table, fj.lane(1));
-    else launch_table_grad<5>(N, h, L, attn, go, offs, nullptr, rel, grad_table, fj.lane(1));
+    if (L <= 64) launch_table_grad<4>(ln, N, h, L, attn, go, offs, nullptr, rel, grad_table, fj.lane(1));
+    else launch_table_grad<5>(ln, N, h, L, attn, go, offs, nullptr, rel, grad_table, fj.lane(1));
     return true;
 }
 
 // the optional fused backward; every output is fully written except the three table gradients (accumulated)
-bool wattn_bwd(int N, int NK, int M, int h, int hdim, int L, const float *go, const float *q, const float *k, const float *v,
+bool wattn_bwd(const Launch &ln, int N, int M, int h, int hdim, int L, const float *go, const float *q, const float *k, const float *v,
                const float *attn, const int *offs, const int *idx1, const float *table_q, const float *table_k,
-               const float *table_v, const int *rel, const int *co, const int *cp, const int *cq, float *grad_logit,
-               float *grad_q, float *grad_k, float *grad_v, float *gtq, float *gtk, float *gtv) {
+               const float *table_v, const int *rel, float *grad_logit, float *grad_q, float *grad_k, float *grad_v, float *gtq,
+               float *gtk, float *gtv) {
+    const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair, *cq = ln.opts.csc_query;
+    const int NK = ln.key_rows(N);
     if (hdim != 16 || co == nullptr || L < 1 || L > 80) return false;
-    hipStream_t st = state().stream;
+    const hipStream_t st = ln.stream;
     with_heads(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
         const int groups = div_up(h, HG);
         const size_t lds2 = (size_t)2 * HG * 3 * L * 16 * sizeof(float);
         allow_big_lds(wattn_bwd_query_kernel<HG>, lds2);
         hipLaunchKernelGGL((wattn_bwd_query_kernel<HG>), dim3(walk_blocks(N, groups, 8, 2), groups), dim3(512), lds2, st,
-                           N, h, L, go, offs, idx1, attn, v, k, table_v, table_q, rel, grad_logit, grad_q, rows_in_order(N));
+                           N, h, L, go, offs, idx1, attn, v, k, table_v, table_q, rel, grad_logit, grad_q, ln.rows_in_order(N));
     });
     // everything below only reads grad_logit: the key walk and the three table gradients are independent
     ForkJoin fj(st, fork_worthwhile((int64_t)M * h));
@@ -649,16 +652,16 @@ bool wattn_bwd(int N, int NK, int M, int h, int hdim, int L, const float *go, co
         const int groups = div_up(h, HG);
         const size_t lds1 = (size_t)HG * 3 * L * 16 * sizeof(float);
         hipLaunchKernelGGL((wattn_bwd_key_kernel<HG>), dim3(walk_blocks(NK, groups, 8, 2), groups), dim3(512), lds1, fj.lane(0),
-                           NK, h, L, grad_logit, attn, go, q, co, cp, cq, table_k, rel, grad_k, grad_v, rows_in_order(NK));
+                           NK, h, L, grad_logit, attn, go, q, co, cp, cq, table_k, rel, grad_k, grad_v, ln.rows_in_order(NK));
     });
     if (L <= 64) {
-        launch_table_grad<4>(NK, h, L, grad_logit, k, co, cp, rel, gtk, fj.lane(1));
-        launch_table_grad<4>(N, h, L, grad_logit, q, offs, nullptr, rel, gtq, fj.lane(2));
-        launch_table_grad<4>(N, h, L, attn, go, offs, nullptr, rel, gtv, fj.lane(3));
+        launch_table_grad<4>(ln, NK, h, L, grad_logit, k, co, cp, rel, gtk, fj.lane(1));
+        launch_table_grad<4>(ln, N, h, L, grad_logit, q, offs, nullptr, rel, gtq, fj.lane(2));
+        launch_table_grad<4>(ln, N, h, L, attn, go, offs, nullptr, rel, gtv, fj.lane(3));
     } else {
-        launch_table_grad<5>(NK, h, L, grad_logit, k, co, cp, rel, gtk, fj.lane(1));
-        launch_table_grad<5>(N, h, L, grad_logit, q, offs, nullptr, rel, gtq, fj.lane(2));
-        launch_table_grad<5>(N, h, L, attn, go, offs, nullptr, rel, gtv, fj.lane(3));
+        launch_table_grad<5>(ln, NK, h, L, grad_logit, k, co, cp, rel, gtk, fj.lane(1));
+        launch_table_grad<5>(ln, N, h, L, grad_logit, q, offs, nullptr, rel, gtq, fj.lane(2));
+        launch_table_grad<5>(ln, N, h, L, attn, go, offs, nullptr, rel, gtv, fj.lane(3));
     }
     return true;
 }

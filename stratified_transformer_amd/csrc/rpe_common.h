@@ -84,25 +84,24 @@ __device__ __forceinline__ PairIds load_pair_ids(const int *__restrict__ idx1, c
 }
 
 // rpe_fallback.hip: the rel-pos operators without a table length (global-memory tables, the reference's atomics)
-void a2_fwd_global(int N, int M, int h, int d, const float *q, const int *offs, const float *k, const int *idxk, const float *tq,
+void a2_fwd_global(hipStream_t st, int N, int M, int h, int d, const float *q, const int *offs, const float *k, const int *idxk, const float *tq,
                    const float *tk, const int *rel, float *out);
-void a2_bwd_global(int N, int M, int h, int d, const float *go, const float *q, const int *offs, const float *k, const int *idxk,
+void a2_bwd_global(hipStream_t st, int N, int M, int h, int d, const float *go, const float *q, const int *offs, const float *k, const int *idxk,
                    const float *tq, const float *tk, const int *rel, float *gq, float *gk, float *gtq, float *gtk);
-void a4_fwd_global(int N, int M, int h, int d, const float *attn, const float *v, const int *offs, const int *idx1, const float *tv,
+void a4_fwd_global(hipStream_t st, int N, int M, int h, int d, const float *attn, const float *v, const int *offs, const int *idx1, const float *tv,
                    const int *rel, float *out);
-void a4_bwd_global(int N, int M, int h, int d, const float *go, const int *offs, const int *idx1, const float *attn, const float *v,
+void a4_bwd_global(hipStream_t st, int N, int M, int h, int d, const float *go, const int *offs, const int *idx1, const float *attn, const float *v,
                    const float *tv, const int *rel, float *ga, float *gv, float *gt);
 
-// rpe_bwd_mfma.hip
-bool a2_bwd_mfma(int N, int NK, int M, int h, int hdim, int L, const float *go, const float *q, const int *offs, const float *k,
-                 const float *table_q, const float *table_k, const int *rel, const int *co, const int *cp,
-                 float *grad_q, float *grad_k, float *gtq, float *gtk);
-bool a4_bwd_mfma(int N, int h, int hdim, int L, const float *go, const int *offs, const int *idx1, const float *attn,
+// rpe_bwd_mfma.hip: stream, key rows, CSC view and row order come from the launch
+bool a2_bwd_mfma(const Launch &ln, int N, int M, int h, int hdim, int L, const float *go, const float *q, const int *offs, const float *k,
+                 const float *table_q, const float *table_k, const int *rel, float *grad_q, float *grad_k, float *gtq, float *gtk);
+bool a4_bwd_mfma(const Launch &ln, int N, int h, int hdim, int L, const float *go, const int *offs, const int *idx1, const float *attn,
                  const float *v, const float *table, const int *rel, float *grad_attn, float *grad_table, ForkJoin &fj);
 
-bool wattn_bwd(int N, int NK, int M, int h, int hdim, int L, const float *go, const float *q, const float *k, const float *v,
+bool wattn_bwd(const Launch &ln, int N, int M, int h, int hdim, int L, const float *go, const float *q, const float *k, const float *v,
                const float *attn, const int *offs, const int *idx1, const float *table_q, const float *table_k,
-               const float *table_v, const int *rel, const int *co, const int *cp, const int *cq, float *grad_logit,
-               float *grad_q, float *grad_k, float *grad_v, float *gtq, float *gtk, float *gtv);
+               const float *table_v, const int *rel, float *grad_logit, float *grad_q, float *grad_k, float *grad_v, float *gtq,
+               float *gtk, float *gtv);
 
 }  // namespace p2

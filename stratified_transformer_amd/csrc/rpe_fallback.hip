@@ -1,7 +1,7 @@
 // Rel-pos operators without the table length L.  The reference's *_v3 / *_v2 rel-pos launchers do not carry L
 // (relative_pos_encoding_cuda_kernel_v2.h:22-29) and its kernels read the tables straight from global memory;
-// this build's fast kernels stage a head group's table slice in LDS and need L (pointops2_set_table_rows).  When
-// a caller has not announced L - e.g. the reference's own C++ shims linked against this library unchanged - these
+// this build's fast kernels stage a head group's table slice in LDS and need L (launch_opts.table_rows).  When
+// a caller has not given L - e.g. the reference's own C++ shims linked against this library unchanged - these
 // kernels run instead: one thread per (pair, head), the query of a pair found by binary search in the CSR offsets,
 // tables read through L1/L2, the reference's accumulation by global atomics.  Same results, several times slower.
 #include "common.h"
@@ -91,24 +91,24 @@ __global__ void a4_bwd_global_kernel(int N, int M, int h, int d, const float *__
 static dim3 pair_grid(int M, int h) { return dim3((unsigned)div_up64((int64_t)M * h, 256)); }
 
 // grad_q of the rel-pos bias is "fully written" by the fast kernels; here it accumulates, so it is zeroed first
-void a2_fwd_global(int N, int M, int h, int d, const float *q, const int *offs, const float *k, const int *idxk, const float *tq,
+void a2_fwd_global(hipStream_t st, int N, int M, int h, int d, const float *q, const int *offs, const float *k, const int *idxk, const float *tq,
                    const float *tk, const int *rel, float *out) {
-    hipLaunchKernelGGL(a2_fwd_global_kernel, pair_grid(M, h), dim3(256), 0, state().stream, N, M, h, d, q, offs, k, idxk, tq, tk, rel, out);
+    hipLaunchKernelGGL(a2_fwd_global_kernel, pair_grid(M, h), dim3(256), 0, st, N, M, h, d, q, offs, k, idxk, tq, tk, rel, out);
 }
-void a2_bwd_global(int N, int M, int h, int d, const float *go, const float *q, const int *offs, const float *k, const int *idxk,
+void a2_bwd_global(hipStream_t st, int N, int M, int h, int d, const float *go, const float *q, const int *offs, const float *k, const int *idxk,
                    const float *tq, const float *tk, const int *rel, float *gq, float *gk, float *gtq, float *gtk) {
-    (void)hipMemsetAsync(gq, 0, (size_t)N * h * d * sizeof(float), state().stream);
-    hipLaunchKernelGGL(a2_bwd_global_kernel, pair_grid(M, h), dim3(256), 0, state().stream, N, M, h, d, go, q, offs, k, idxk, tq, tk, rel, gq, gk,
+    (void)hipMemsetAsync(gq, 0, (size_t)N * h * d * sizeof(float), st);
+    hipLaunchKernelGGL(a2_bwd_global_kernel, pair_grid(M, h), dim3(256), 0, st, N, M, h, d, go, q, offs, k, idxk, tq, tk, rel, gq, gk,
                        gtq, gtk);
 }
-void a4_fwd_global(int N, int M, int h, int d, const float *attn, const float *v, const int *offs, const int *idx1, const float *tv,
+void a4_fwd_global(hipStream_t st, int N, int M, int h, int d, const float *attn, const float *v, const int *offs, const int *idx1, const float *tv,
                    const int *rel, float *out) {
-    (void)hipMemsetAsync(out, 0, (size_t)N * h * d * sizeof(float), state().stream);
-    hipLaunchKernelGGL(a4_fwd_global_kernel, pair_grid(M, h), dim3(256), 0, state().stream, N, M, h, d, attn, v, offs, idx1, tv, rel, out);
+    (void)hipMemsetAsync(out, 0, (size_t)N * h * d * sizeof(float), st);
+    hipLaunchKernelGGL(a4_fwd_global_kernel, pair_grid(M, h), dim3(256), 0, st, N, M, h, d, attn, v, offs, idx1, tv, rel, out);
 }
-void a4_bwd_global(int N, int M, int h, int d, const float *go, const int *offs, const int *idx1, const float *attn, const float *v,
+void a4_bwd_global(hipStream_t st, int N, int M, int h, int d, const float *go, const int *offs, const int *idx1, const float *attn, const float *v,
                    const float *tv, const int *rel, float *ga, float *gv, float *gt) {
-    hipLaunchKernelGGL(a4_bwd_global_kernel, pair_grid(M, h), dim3(256), 0, state().stream, N, M, h, d, go, offs, idx1, attn, v, tv, rel, ga, gv, gt);
+    hipLaunchKernelGGL(a4_bwd_global_kernel, pair_grid(M, h), dim3(256), 0, st, N, M, h, d, go, offs, idx1, attn, v, tv, rel, ga, gv, gt);
 }
 
 }  // namespace p2
@@ -122,21 +122,25 @@ extern "C" {
 // reference's own shim sources link against this library; a call records an error and does nothing.
 void subtraction_forward_cuda_launcher(int n, int nsample, int c, const float *input1, const float *input2, const int *idx, float *output) {
     (void)n; (void)nsample; (void)c; (void)input1; (void)input2; (void)idx; (void)output;
+    (void)begin_launch();  // (a launch all the same: it resets the launch options)
     set_error("subtraction_forward: not part of the Stratified Transformer hot path, not implemented");
 }
 void subtraction_backward_cuda_launcher(int n, int nsample, int c, const int *idx, const float *grad_output, float *grad_input1, float *grad_input2) {
     (void)n; (void)nsample; (void)c; (void)idx; (void)grad_output; (void)grad_input1; (void)grad_input2;
+    (void)begin_launch();
     set_error("subtraction_backward: not part of the Stratified Transformer hot path, not implemented");
 }
 void aggregation_forward_cuda_launcher(int n, int nsample, int c, int w_c, const float *input, const float *position, const float *weight,
                                        const int *idx, float *output) {
     (void)n; (void)nsample; (void)c; (void)w_c; (void)input; (void)position; (void)weight; (void)idx; (void)output;
+    (void)begin_launch();
     set_error("aggregation_forward: not part of the Stratified Transformer hot path, not implemented");
 }
 void aggregation_backward_cuda_launcher(int n, int nsample, int c, int w_c, const float *input, const float *position, const float *weight,
                                         const int *idx, const float *grad_output, float *grad_input, float *grad_position, float *grad_weight) {
     (void)n; (void)nsample; (void)c; (void)w_c; (void)input; (void)position; (void)weight; (void)idx; (void)grad_output; (void)grad_input;
     (void)grad_position; (void)grad_weight;
+    (void)begin_launch();
     set_error("aggregation_backward: not part of the Stratified Transformer hot path, not implemented");
 }
 

@@ -105,15 +105,14 @@ extern "C" {
 
 void furthestsampling_cuda_launcher(int b, int n, const float *xyz, const int *offset,
                                     const int *new_offset, float *tmp, int *idx) {
+    const Launch ln = begin_launch();
     if (b <= 0) return;
     const int Bref = ref_block_size(n);
     int log2B = 0;
     while ((1 << log2B) < Bref) log2B++;
-    hipStream_t st = state().stream;
-    const int N_total = state().total_points;
-    state().total_points = 0;
+    const hipStream_t st = ln.stream;
     // bucketed exact FPS (fps_bucket.hip) needs a caller-provided workspace and the total point count
-    if (n >= 2048 && fps_bucket_launch(b, n, Bref, log2B, xyz, offset, new_offset, N_total, idx)) {
+    if (n >= 2048 && fps_bucket_launch(ln, b, n, Bref, log2B, xyz, offset, new_offset, idx)) {
         check_launch();
         return;
     }

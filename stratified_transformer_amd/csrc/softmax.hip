@@ -152,21 +152,23 @@ using namespace p2;
 extern "C" {
 
 void segment_softmax_forward_launcher(int N, int M, int h, const float *src, const int *offsets, float *out) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0 || M <= 0) return;
     if (few_rows_many_heads(N, h))
-        hipLaunchKernelGGL(seg_softmax_fwd_block_kernel, dim3(N), dim3(256), 0, state().stream, N, M, h, next_pow2_le64(h), src, offsets, out);
+        hipLaunchKernelGGL(seg_softmax_fwd_block_kernel, dim3(N), dim3(256), 0, st, N, M, h, next_pow2_le64(h), src, offsets, out);
     else
-        hipLaunchKernelGGL(seg_softmax_fwd_kernel, dim3(div_up(N, 4)), dim3(256), 0, state().stream, N, M, h, next_pow2_le64(h), src, offsets, out);
+        hipLaunchKernelGGL(seg_softmax_fwd_kernel, dim3(div_up(N, 4)), dim3(256), 0, st, N, M, h, next_pow2_le64(h), src, offsets, out);
     check_launch();
 }
 
 void segment_softmax_backward_launcher(int N, int M, int h, const float *out, const float *grad_out,
                                        const int *offsets, float *grad_src) {
+    const hipStream_t st = begin_launch().stream;
     if (N <= 0 || M <= 0) return;
     if (few_rows_many_heads(N, h))
-        hipLaunchKernelGGL(seg_softmax_bwd_block_kernel, dim3(N), dim3(256), 0, state().stream, N, M, h, next_pow2_le64(h), out, grad_out, offsets, grad_src);
+        hipLaunchKernelGGL(seg_softmax_bwd_block_kernel, dim3(N), dim3(256), 0, st, N, M, h, next_pow2_le64(h), out, grad_out, offsets, grad_src);
     else
-        hipLaunchKernelGGL(seg_softmax_bwd_kernel, dim3(div_up(N, 4)), dim3(256), 0, state().stream, N, M, h, next_pow2_le64(h), out, grad_out, offsets, grad_src);
+        hipLaunchKernelGGL(seg_softmax_bwd_kernel, dim3(div_up(N, 4)), dim3(256), 0, st, N, M, h, next_pow2_le64(h), out, grad_out, offsets, grad_src);
     check_launch();
 }
 

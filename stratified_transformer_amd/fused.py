@@ -42,12 +42,12 @@ class WindowAttention(Function):
                            (table_q, torch.float32, "table_q"), (table_k, torch.float32, "table_k"), (table_v, torch.float32, "table_v"),
                            (index0_offsets, torch.int32, "index0_offsets"), (index1, torch.int32, "index1"), (rel_idx, torch.int32, "rel_idx"))
         attn = torch.empty((M, h), dtype=torch.float32, device=q.device)
-        pointops_cuda._rows(table_q)
         out = torch.zeros((N, h, hdim), dtype=torch.float32, device=q.device)
-        with P._with_rows(P.row_order_of(index0_offsets, index1)):  # (the pair walkers take their rows in window order, csrc/common.h)
-            pointops_cuda._call("window_logits_softmax_forward_launcher", q, int(index0_offsets.shape[0]) - 1, M, h, hdim,
-                                ptr(q), ptr(index0_offsets), ptr(k), ptr(index1), ptr(table_q), ptr(table_k), ptr(rel_idx), ptr(attn))
-            pointops_cuda.attention_step2_with_rel_pos_value_forward_cuda_v2(N, M, h, hdim, 0, attn, v, index0_offsets, index1, table_v, rel_idx, out)
+        opts = _lib.with_table_rows(P.pair_opts(index0_offsets, index1), L)  # (the pair walkers take their rows in window order, csrc/common.h)
+        pointops_cuda._call("window_logits_softmax_forward_launcher", q, int(index0_offsets.shape[0]) - 1, M, h, hdim,
+                            ptr(q), ptr(index0_offsets), ptr(k), ptr(index1), ptr(table_q), ptr(table_k), ptr(rel_idx), ptr(attn), opts=opts)
+        pointops_cuda.attention_step2_with_rel_pos_value_forward_cuda_v2(N, M, h, hdim, 0, attn, v, index0_offsets, index1, table_v, rel_idx, out,
+                                                                         opts=opts)
         ctx.save_for_backward(q, k, v, table_q, table_k, table_v, index0_offsets, index1, rel_idx, attn)
         return out
 
@@ -63,32 +63,31 @@ class WindowAttention(Function):
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
         e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
         csc = P.csc_of(offs, index1, NK)
+        opts = _lib.with_table_rows(P.pair_opts(offs, index1, csc=csc), L)  # (the same options serve every launch below: one L, one pair list)
         if csc is not None and L <= 80:
             # two walks (by query, by key) + the three table gradients: DESIGN.md 4.5
             grad_logit, grad_q, grad_k, grad_v = e(M, h), e(N, h, hdim), e(NK, h, hdim), e(v.shape[0], h, hdim)
             grad_tq, grad_tk, grad_tv = z(L, h, hdim, 3), z(L, h, hdim, 3), z(L, h, hdim, 3)
             pointops_cuda._chk((grad_out, torch.float32, "grad_out"))
-            pointops_cuda._rows(table_q)
-            with P._with_csc(csc), P._with_rows(P.row_order_of(offs, index1)):
-                pointops_cuda._call("window_attention_backward_launcher", q, int(offs.shape[0]) - 1, M, h, hdim, ptr(grad_out), ptr(q), ptr(k),
-                                    ptr(v), ptr(attn), ptr(offs), ptr(index1), ptr(table_q), ptr(table_k), ptr(table_v), ptr(rel_idx),
-                                    ptr(grad_logit), ptr(grad_q), ptr(grad_k), ptr(grad_v), ptr(grad_tq), ptr(grad_tk), ptr(grad_tv))
+            pointops_cuda._call("window_attention_backward_launcher", q, int(offs.shape[0]) - 1, M, h, hdim, ptr(grad_out), ptr(q), ptr(k),
+                                ptr(v), ptr(attn), ptr(offs), ptr(index1), ptr(table_q), ptr(table_k), ptr(table_v), ptr(rel_idx),
+                                ptr(grad_logit), ptr(grad_q), ptr(grad_k), ptr(grad_v), ptr(grad_tq), ptr(grad_tk), ptr(grad_tv), opts=opts)
             return grad_q, grad_k, grad_v, grad_tq, grad_tk, grad_tv, None, None, None
-        with P._with_csc(csc), P._with_rows(P.row_order_of(offs, index1)):
-            # the operators' own backward launchers, in autograd's order
-            grad_attn = e(M, h)
-            grad_v, grad_tv = z(v.shape[0], h, hdim), z(L, h, hdim, 3)
-            pointops_cuda.attention_step2_with_rel_pos_value_backward_cuda_v2(N, M, h, hdim, 0, grad_out, offs, index1, attn, v, table_v, rel_idx,
-                                                                              grad_attn, grad_v, grad_tv)
-            grad_logit = e(M, h)
-            pointops_cuda._call("segment_softmax_backward_launcher", attn, int(offs.shape[0]) - 1, M, h, ptr(attn), ptr(grad_attn), ptr(offs), ptr(grad_logit))
-            # A1 and A2 receive the same gradient; grad_k is accumulated by both into one buffer
-            gq1, gq2 = e(N, h, hdim), e(N, h, hdim)
-            grad_k = z(NK, h, hdim)
-            grad_tq, grad_tk = z(L, h, hdim, 3), z(L, h, hdim, 3)
-            pointops_cuda.attention_step1_backward_cuda_v2(int(offs.shape[0]) - 1, M, h, h * hdim, 0, grad_logit, offs, index1, q, k, gq1, grad_k)
-            pointops_cuda.dot_prod_with_idx_backward_cuda_v3(N, M, h, hdim, 0, grad_logit, q, offs, k, index1, table_q, table_k, rel_idx,
-                                                             gq2, grad_k, grad_tq, grad_tk)
+        # the operators' own backward launchers, in autograd's order
+        grad_attn = e(M, h)
+        grad_v, grad_tv = z(v.shape[0], h, hdim), z(L, h, hdim, 3)
+        pointops_cuda.attention_step2_with_rel_pos_value_backward_cuda_v2(N, M, h, hdim, 0, grad_out, offs, index1, attn, v, table_v, rel_idx,
+                                                                          grad_attn, grad_v, grad_tv, opts=opts)
+        grad_logit = e(M, h)
+        pointops_cuda._call("segment_softmax_backward_launcher", attn, int(offs.shape[0]) - 1, M, h, ptr(attn), ptr(grad_attn), ptr(offs), ptr(grad_logit))
+        # A1 and A2 receive the same gradient; grad_k is accumulated by both into one buffer
+        gq1, gq2 = e(N, h, hdim), e(N, h, hdim)
+        grad_k = z(NK, h, hdim)
+        grad_tq, grad_tk = z(L, h, hdim, 3), z(L, h, hdim, 3)
+        pointops_cuda.attention_step1_backward_cuda_v2(int(offs.shape[0]) - 1, M, h, h * hdim, 0, grad_logit, offs, index1, q, k, gq1, grad_k,
+                                                       opts=opts)
+        pointops_cuda.dot_prod_with_idx_backward_cuda_v3(N, M, h, hdim, 0, grad_logit, q, offs, k, index1, table_q, table_k, rel_idx,
+                                                         gq2, grad_k, grad_tq, grad_tk, opts=opts)
         return gq1.add_(gq2), grad_k, grad_v, grad_tq, grad_tk, grad_tv, None, None, None
 
 

@@ -103,9 +103,8 @@ def csc_of(index0_offsets, index1, n_keys, alias=None):
         nbytes = int(l.pointops2_csc_workspace_bytes(max(N, n_keys), M))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            l.pointops2_set_key_rows(int(n_keys))
             _lib.call("pointops2_csc_build", N, M, ptr(index0_offsets), ptr(index1), ptr(offsets), ptr(pair), ptr(query),
-                      ptr(ws), nbytes, device=dev)
+                      ptr(ws), nbytes, device=dev, opts=_lib.LaunchOpts(key_rows=int(n_keys)))
     else:
         offsets.zero_()
     csc = _CSC(offsets, pair, query, (index0_offsets, index1, alias))
@@ -217,19 +216,20 @@ def seed_row_order(index0_offsets, index1, order, alias=None):
         _ROW_ORDER_CACHE.popitem(last=False)
 
 
-class _with_rows:
-    """the pair walkers of the launchers called inside take their rows in `order` (None: by index)"""
-
-    def __init__(self, order):
-        self.order = order
-
-    def __enter__(self):
-        if self.order is not None:
-            _lib.lib().pointops2_set_row_order(ptr(self.order), int(self.order.shape[0]))
-
-    def __exit__(self, *exc):
-        if self.order is not None:
-            _lib.lib().pointops2_set_row_order(None, 0)
+def pair_opts(index0_offsets, index1, alias=None, csc=None):
+    """The launch options (_lib.LaunchOpts) of one operator call on the pair list (index0_offsets, index1): its rows in window
+    order (row_order_of; the pair walkers take their rows in that order) and, for a backward, its key-major view `csc`
+    (csc_of) with the key rows.  None when there is nothing to pass.  The rel-pos shims add the tables' row count."""
+    order = row_order_of(index0_offsets, index1, alias)
+    if order is None and csc is None:
+        return None
+    opts = _lib.LaunchOpts()
+    if order is not None:
+        opts.row_order, opts.row_order_rows = ptr(order), int(order.shape[0])
+    if csc is not None:
+        opts.csc_offsets, opts.csc_pair, opts.csc_query = ptr(csc.offsets), ptr(csc.pair), ptr(csc.query)
+        opts.key_rows = csc.n_keys  # rows of k / v (may differ from the CSR's query rows)
+    return opts
 
 
 def clear_caches():
@@ -238,24 +238,6 @@ def clear_caches():
     _ROW_ORDER_CACHE.clear()
     _FPS_CACHE.clear()
     _HOST_OFFSETS.clear()
-
-
-class _with_csc:
-    def __init__(self, csc):
-        self.csc = csc
-
-    def __enter__(self):
-        if self.csc is not None:
-            l = _lib.lib()
-            l.pointops2_set_csc(ptr(self.csc.offsets), ptr(self.csc.pair), ptr(self.csc.query))
-            l.pointops2_set_key_rows(self.csc.n_keys)  # rows of k / v (may differ from the CSR's query rows)
-
-    def __exit__(self, *exc):
-        # always undone: a launcher called later through the plain reference API must not see a stale view
-        if self.csc is not None:
-            l = _lib.lib()
-            l.pointops2_set_csc(None, None, None)
-            l.pointops2_set_key_rows(0)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -329,25 +311,16 @@ class FurthestSampling(Function):
                 return torch.cat([ent["idx"][s: s + w] for s, w in zip(starts, want)])
             if not all(w >= h for w, h in zip(want, have)):
                 ent = None  # neither a prefix nor a pure extension of the kept state: start over
-        l = _lib.lib()
         idx = _zeros(new_offs[b - 1], xyz, torch.int32)
         tmp = torch.full((n,), 1e10, dtype=torch.float32, device=xyz.device)
         # lend the library scratch memory for the bucketed exact FPS (csrc/fps_bucket.hip); the
         # reference signature carries neither a workspace nor the total point count
+        ws = ent["ws"] if ent is not None else \
+            torch.empty(int(_lib.lib().pointops2_fps_workspace_bytes(b, n)), dtype=torch.uint8, device=xyz.device)
+        opts = _lib.LaunchOpts(workspace=ptr(ws), workspace_bytes=ws.numel(), point_count=n, fps_unordered=1 if _is_unordered(xyz) else 0)
         if ent is not None:
-            ws = ent["ws"]
-            l.pointops2_set_fps_resume(ptr(ent["idx"]), ptr(ent["new_offset"]))
-        else:
-            ws = torch.empty(int(l.pointops2_fps_workspace_bytes(b, n)), dtype=torch.uint8, device=xyz.device)
-        l.pointops2_set_workspace(ptr(ws), ws.numel())
-        l.pointops2_set_point_count(n)
-        l.pointops2_set_fps_hint(1 if _is_unordered(xyz) else 0)
-        try:
-            pointops_cuda.furthestsampling_cuda(b, n_max, xyz, offset, new_offset, tmp, idx)
-        finally:
-            l.pointops2_set_workspace(None, 0)
-            l.pointops2_set_fps_resume(None, None)
-            l.pointops2_set_fps_hint(0)
+            opts.fps_prev_idx, opts.fps_prev_new_offset = ptr(ent["idx"]), ptr(ent["new_offset"])
+        pointops_cuda.furthestsampling_cuda(b, n_max, xyz, offset, new_offset, tmp, idx, opts=opts)
         del tmp
         if n_max >= 2048:  # the bucketed kernel ran: its state can serve / resume later requests
             done = torch.cuda.Event()
@@ -372,16 +345,10 @@ def knn_squared(nsample, xyz, new_xyz, offset, new_offset):
     idx = _zeros((m, nsample), xyz, torch.int32)
     dist2 = _zeros((m, nsample), xyz)
     # lend scratch memory for the grid-accelerated exact search (csrc/knn_grid.hip)
-    l = _lib.lib()
     n, b = xyz.shape[0], offset.shape[0]
-    ws = torch.empty(int(l.pointops2_knn_workspace_bytes(n, m, b)), dtype=torch.uint8, device=xyz.device)
-    l.pointops2_set_workspace(ptr(ws), ws.numel())
-    l.pointops2_set_point_count(n)
-    l.pointops2_set_batch_count(b)
-    try:
-        pointops_cuda.knnquery_cuda(m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2)
-    finally:
-        l.pointops2_set_workspace(None, 0)
+    ws = torch.empty(int(_lib.lib().pointops2_knn_workspace_bytes(n, m, b)), dtype=torch.uint8, device=xyz.device)
+    opts = _lib.LaunchOpts(workspace=ptr(ws), workspace_bytes=ws.numel(), point_count=n, batch_count=b)
+    pointops_cuda.knnquery_cuda(m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2, opts=opts)
     return idx, dist2
 
 
@@ -482,8 +449,8 @@ class AttentionStep1_v2(Function):
         output = torch.empty((M, h), dtype=torch.float32, device=q.device)
         # the launcher's N is the number of CSR rows (queries); the reference passes N_k, which is the same
         # number in the model and would be wrong anywhere else (its kernel grid is one block per query)
-        with _with_rows(row_order_of(index0_offsets, index1, n_max)):
-            pointops_cuda.attention_step1_forward_cuda_v2(int(index0_offsets.shape[0]) - 1, M, h, C, _nmax(n_max), q, k, index0_offsets, index1, output)
+        pointops_cuda.attention_step1_forward_cuda_v2(int(index0_offsets.shape[0]) - 1, M, h, C, _nmax(n_max), q, k, index0_offsets, index1, output,
+                                                      opts=pair_opts(index0_offsets, index1, n_max))
         remember_csr(index0_offsets, M)
         ctx.N_q, ctx.N_k, ctx.C, ctx.n_max = N_q, N_k, C, n_max
         ctx.save_for_backward(q, k, index0_offsets, index1)
@@ -498,8 +465,9 @@ class AttentionStep1_v2(Function):
         grad_output = grad_output.contiguous()
         grad_q = torch.empty((N_q, h, C // h), dtype=torch.float32, device=q.device)
         grad_k = _zeros((N_k, h, C // h), q)
-        with _with_csc(csc_of(index0_offsets, index1, N_k, ctx.n_max)), _with_rows(row_order_of(index0_offsets, index1, ctx.n_max)):
-            pointops_cuda.attention_step1_backward_cuda_v2(int(index0_offsets.shape[0]) - 1, M, h, C, _nmax(ctx.n_max), grad_output, index0_offsets, index1, q, k, grad_q, grad_k)
+        csc = csc_of(index0_offsets, index1, N_k, ctx.n_max)
+        pointops_cuda.attention_step1_backward_cuda_v2(int(index0_offsets.shape[0]) - 1, M, h, C, _nmax(ctx.n_max), grad_output, index0_offsets, index1, q, k, grad_q, grad_k,
+                                                       opts=pair_opts(index0_offsets, index1, ctx.n_max, csc))
         return grad_q, grad_k, None, None, None
 
 
@@ -632,8 +600,8 @@ class DotProdWithIdx_v3(Function):
         assert table_k.shape[0] == L
         _check_pair_list("dot_prod_with_idx_v3", N, index_q_offsets, index_k, rel_idx)
         output = torch.empty((M, h), dtype=torch.float32, device=q.device)
-        with _with_rows(row_order_of(index_q_offsets, index_k, n_max)):
-            pointops_cuda.dot_prod_with_idx_forward_cuda_v3(N, M, h, hdim, _nmax(n_max), q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output)
+        pointops_cuda.dot_prod_with_idx_forward_cuda_v3(N, M, h, hdim, _nmax(n_max), q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output,
+                                                        opts=pair_opts(index_q_offsets, index_k, n_max))
         remember_csr(index_q_offsets, M)
         ctx.n_max = n_max
         ctx.save_for_backward(q, index_q_offsets, k, index_k, table_q, table_k, rel_idx)
@@ -650,9 +618,10 @@ class DotProdWithIdx_v3(Function):
         grad_q = torch.empty((N, h, hdim), dtype=torch.float32, device=q.device)
         grad_k = _zeros((k.shape[0], h, hdim), q)
         grad_table_q, grad_table_k = _zeros((L, h, hdim, 3), q), _zeros((L, h, hdim, 3), q)
-        with _with_csc(csc_of(index_q_offsets, index_k, k.shape[0], ctx.n_max)), _with_rows(row_order_of(index_q_offsets, index_k, ctx.n_max)):
-            pointops_cuda.dot_prod_with_idx_backward_cuda_v3(N, M, h, hdim, _nmax(ctx.n_max), grad_output, q, index_q_offsets, k, index_k,
-                                                             table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q, grad_table_k)
+        csc = csc_of(index_q_offsets, index_k, k.shape[0], ctx.n_max)
+        pointops_cuda.dot_prod_with_idx_backward_cuda_v3(N, M, h, hdim, _nmax(ctx.n_max), grad_output, q, index_q_offsets, k, index_k,
+                                                         table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q, grad_table_k,
+                                                         opts=pair_opts(index_q_offsets, index_k, ctx.n_max, csc))
         return grad_q, None, None, grad_k, None, grad_table_q, grad_table_k, None
 
 
@@ -702,8 +671,8 @@ class AttentionStep2WithRelPosValue_v2(Function):
         N = int(index0_offsets.shape[0]) - 1  # CSR rows = queries (== N_v in the model, :594-597)
         _check_pair_list("attention_step2_with_rel_pos_value_v2", N, index0_offsets, index1, rel_idx, attn)
         output = torch.empty((N, h, hdim), dtype=torch.float32, device=v.device)
-        with _with_rows(row_order_of(index0_offsets, index1, n_max)):
-            pointops_cuda.attention_step2_with_rel_pos_value_forward_cuda_v2(N, M, h, hdim, _nmax(n_max), attn, v, index0_offsets, index1, table, rel_idx, output)
+        pointops_cuda.attention_step2_with_rel_pos_value_forward_cuda_v2(N, M, h, hdim, _nmax(n_max), attn, v, index0_offsets, index1, table, rel_idx, output,
+                                                                         opts=pair_opts(index0_offsets, index1, n_max))
         ctx.n_max = n_max
         ctx.save_for_backward(attn, v, index0_offsets, index1, table, rel_idx)
         return output
@@ -718,9 +687,10 @@ class AttentionStep2WithRelPosValue_v2(Function):
         assert grad_output.is_contiguous()
         grad_attn = torch.empty((M, h), dtype=torch.float32, device=v.device)
         grad_v, grad_table = _zeros((N_v, h, hdim), v), _zeros((L, h, hdim, 3), v)
-        with _with_csc(csc_of(index0_offsets, index1, N_v, ctx.n_max)), _with_rows(row_order_of(index0_offsets, index1, ctx.n_max)):
-            pointops_cuda.attention_step2_with_rel_pos_value_backward_cuda_v2(N, M, h, hdim, _nmax(ctx.n_max), grad_output, index0_offsets, index1,
-                                                                              attn, v, table, rel_idx, grad_attn, grad_v, grad_table)
+        csc = csc_of(index0_offsets, index1, N_v, ctx.n_max)
+        pointops_cuda.attention_step2_with_rel_pos_value_backward_cuda_v2(N, M, h, hdim, _nmax(ctx.n_max), grad_output, index0_offsets, index1,
+                                                                          attn, v, table, rel_idx, grad_attn, grad_v, grad_table,
+                                                                          opts=pair_opts(index0_offsets, index1, ctx.n_max, csc))
         return grad_attn, grad_v, None, None, None, grad_table, None
 
 

@@ -284,16 +284,15 @@ def test_fps_bit_exact_with_exact_ties(P):
         assert np.array_equal(got, ref.furthestsampling(g, np.asarray(offset, np.int32), np.asarray(new_offset, np.int32))), offset
 
 
-def test_fps_block_kernel_fallback_matches_bucketed(P):
-    """Without a lent workspace the launcher runs the single-workgroup scan: same indices."""
-    from stratified_transformer_amd import _lib, pointops2_cuda
+def test_fps_block_kernel_without_launch_options_matches_bucketed(P):
+    """Without launch options (no lent workspace) the launcher runs the single-workgroup scan: same indices."""
+    from stratified_transformer_amd import pointops2_cuda
     rng = np.random.default_rng(8)
     xyz = rng.random((5000, 3), dtype=np.float32)
     off, noff = dev(np.array([5000], np.int32)), dev(np.array([626], np.int32))
     idx = torch.zeros(626, dtype=torch.int32, device="cuda")
     tmp = torch.full((5000,), 1e10, device="cuda")
-    _lib.lib().pointops2_set_workspace(None, 0)
-    pointops2_cuda.furthestsampling_cuda(1, 5000, dev(xyz), off, noff, tmp, idx)
+    pointops2_cuda.furthestsampling_cuda(1, 5000, dev(xyz), off, noff, tmp, idx)  # (no launch options)
     assert np.array_equal(_np(idx), _fps(P, xyz, [5000], [626]))
     assert np.array_equal(_np(idx), ref.furthestsampling(xyz, np.array([5000], np.int32), np.array([626], np.int32)))
 
@@ -525,7 +524,7 @@ def test_fps_prefix_reuse_and_resume(P):
     assert np.array_equal(_np(P.furthestsampling(x, off, dev(np.array([751, 1752], np.int32)))), full)
 
 
-def test_knn_grid_path_ties_outliers_and_scan_agree(P):
+def test_knn_grid_path_ties_outliers_and_option_free_scan_agree(P):
     """Sizes above the grid threshold (m*n >= 2^22): exact ties go through the replay list, queries far
     outside the cloud walk the whole grid, and the lent-workspace path equals the plain scan."""
     from stratified_transformer_amd import _lib, pointops2_cuda
@@ -546,8 +545,7 @@ def test_knn_grid_path_ties_outliers_and_scan_agree(P):
     off, noff = dev(np.array([8000], np.int32)), dev(np.array([2000], np.int32))
     idx = torch.zeros((2000, 16), dtype=torch.int32, device="cuda")
     d2 = torch.zeros((2000, 16), device="cuda")
-    _lib.lib().pointops2_set_workspace(None, 0)
-    pointops2_cuda.knnquery_cuda(2000, 16, dev(xyz), dev(nq), off, noff, idx, d2)
+    pointops2_cuda.knnquery_cuda(2000, 16, dev(xyz), dev(nq), off, noff, idx, d2)  # (no launch options)
     i_got, d_got = _knn(P, 16, xyz, nq, [8000], [2000])
     assert np.array_equal(_np(idx), i_got) and np.array_equal(np.sqrt(_np(d2)), d_got)
     i_ref, d_ref = ref.knnquery(16, xyz, nq, np.array([8000], np.int32), np.array([2000], np.int32))
@@ -717,7 +715,7 @@ def test_index_build_of_a_scene_wider_than_the_fixed_key():
 
 
 def test_operators_with_rows_in_window_order_equal_rows_by_index(P):
-    """The operators' pair walkers take their rows in window order (pointops.row_order_of / pointops2_set_row_order: neighbouring
+    """The operators' pair walkers take their rows in window order (pointops.row_order_of / launch_opts.row_order: neighbouring
     waves share their partners' rows in L2) - the sums of a row do not change: logits, softmax, output and the row gradients are
     bit-identical to the walk by index, the table gradients (float atomics) to 1e-5.  Also: the order is a permutation that keeps
     the rows of a window together, and it is built once per pair list (three forward + three backward operators: one build)."""
@@ -1173,7 +1171,7 @@ def test_cell_attention_rejects_tables_the_plan_was_not_built_for():
 
 
 # ---- the C ABI with the reference's arguments and allocation pattern alone (SURVEY 8b seam B2) ----------------------
-def test_every_part1_launcher_with_the_references_allocation_pattern(P):
+def test_every_part1_launcher_with_the_references_allocation_pattern_and_no_reset(P):
     """All 24 in-scope launchers of include/pointops2_hip.h PART 1, called through pointops2_cuda.* the way
     lib/pointops2/functions/pointops.py does: the caller allocates every output and zero-fills it
     (pointops.py:157-158, :477, :598 `torch.cuda.FloatTensor(...).zero_()`), nothing else is set up.  Results vs the oracle.
@@ -1276,11 +1274,9 @@ def test_every_part1_launcher_with_the_references_allocation_pattern(P):
     ga, gv, gt = z(M, h), z(N, h, d), z(L, h, d, 3)
     C.attention_step2_with_rel_pos_value_backward_cuda_v2(N, M, h, d, p["n_max"], gr, offs, i1, attn, v, tv, rel, ga, gv, gt)
     close(ga, wga, rtol=1e-4, atol=1e-4); close(gv, wgv, rtol=1e-4, atol=1e-4); close(gt, wgt, **TTOL)
-    # ---- the rel-pos launchers WITHOUT pointops2_set_table_rows: the reference's arguments alone (generic kernels) ----
+    # ---- the rel-pos launchers WITHOUT launch options: the reference's arguments alone (generic kernels), right after the
+    # accelerated calls above and with nothing reset in between (the options of a call apply to that call only) ----
     ptr = _lib.ptr
-    l = _lib.lib()
-    l.pointops2_set_table_rows(0)
-    l.pointops2_set_csc(None, None, None)
     o = z(M, h)
     _lib.call("dot_prod_with_idx_forward_cuda_launcher_v3", N, M, h, d, p["n_max"], ptr(q), ptr(offs), ptr(k), ptr(i1), ptr(tq), ptr(tk), ptr(rel), ptr(o), device=q.device)
     close(o, want_b, rtol=1e-4, atol=1e-4)

@@ -159,7 +159,27 @@ def test_library_exports_every_symbol_of_the_header():
     abi = {n for n in abi if n.startswith("pointops2_") or n.endswith("_launcher")}
     assert len(abi) >= 30
     assert abi <= set(names), f"exported but not declared in include/pointops2_hip.h: {sorted(abi - set(names))}"
-    assert _lib.lib().pointops2_abi_version() >= 2
+    assert _lib.lib().pointops2_abi_version() >= 3
+
+
+def test_launch_opts_struct_matches_the_header(tmp_path):
+    """_lib.LaunchOpts mirrors pointops2_launch_opts field by field: a layout mismatch would hand the library misplaced
+    pointers without any error.  The host C compiler reports sizeof and every offsetof of the header's struct."""
+    fields = [name for name, _ in _lib.LaunchOpts._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pointops2_hip.h"\nint main(void) {\n'
+                   + "".join(f'printf("{f} %zu\\n", offsetof(pointops2_launch_opts, {f}));\n' for f in fields)
+                   + 'printf("sizeof %zu\\n", sizeof(pointops2_launch_opts));\nreturn 0;\n}\n')
+    exe = tmp_path / "layout"
+    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                   check=True)
+    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(got.pop("sizeof")) == ctypes.sizeof(_lib.LaunchOpts)
+    assert {f: int(v) for f, v in got.items()} == {f: getattr(_lib.LaunchOpts, f).offset for f in fields}
+    # and the header declares no field the ctypes mirror lacks
+    text = open(os.path.join(ROOT, "include", "pointops2_hip.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", text[text.index("typedef struct pointops2_launch_opts"):text.index("} pointops2_launch_opts;")], flags=re.S)
+    assert re.findall(r"(\w+);", body) == fields
 
 
 def test_product_path_fails_loudly_without_gpu_tensors():
