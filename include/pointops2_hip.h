@@ -165,7 +165,8 @@ void aggregation_backward_cuda_launcher(int n, int nsample, int c, int w_c, cons
  * ONE RULE: the options set with pointops2_set_launch_opts() apply to the next library launch on this thread, and that
  * launch resets them, whether or not it used them (the stream is not an option: it stays until set again).  0 / NULL = not
  * given; all-zero = the reference's arguments alone (same results, in places slower generic kernels).  The *_workspace_bytes
- * queries, pointops2_last_error, pointops2_get_stream and pointops2_abi_version are no launches: they leave the options. */
+ * queries, pointops2_cell_forward_variant, pointops2_last_error, pointops2_get_stream and pointops2_abi_version are no launches:
+ * they leave the options. */
 typedef struct pointops2_launch_opts {
     /* L of the [L,h,hdim,3] tables of a *_v3 bias, *_v2 rel-pos-value or window_* call: the fast kernels stage them in LDS.
      * Without it the rel-pos launchers read the tables from global memory (several times slower), window_* record an error. */
@@ -351,6 +352,17 @@ void cell_attention_backward_launcher(const pointops2_cell_plan *plan, int h, in
                                       const float *k, const float *v, const float *out, const float *table_q, const float *table_k,
                                       const float *table_v, const float *pbuf, float *gsbuf, float *grad_q, float *grad_k,
                                       float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v);
+/* Which forward kernel cell_attention_forward_launcher (bf16 = 0) or cell_attention_forward_bf16_launcher (bf16 != 0) runs for these
+ * arguments: the launchers take their decision from this function.  Reads the plan's host fields only (n_points, n_pairs,
+ * n_keyslots, table_rows); not a launch.  fp32 with L <= 80 runs on the matrix cores unless n_points * h >= 96000 and the cells
+ * average fewer than 15 queries (n_pairs / n_keyslots < 15); bf16 storage always takes the VALU kernels. */
+#define POINTOPS2_CELL_FWD_ERROR   (-1) /* the launcher records an error (d != 16, L < 1, L != plan->table_rows, L > 160) */
+#define POINTOPS2_CELL_FWD_NONE    0    /* no plan or no points: the launcher does nothing */
+#define POINTOPS2_CELL_FWD_MFMA64  1    /* matrix-core forward, table image of 64 rows (fp32, L <= 64) */
+#define POINTOPS2_CELL_FWD_MFMA80  2    /* matrix-core forward, table image of 80 rows (fp32, 64 < L <= 80) */
+#define POINTOPS2_CELL_FWD_VALU80  3    /* VALU forward, table image of 80 rows (L <= 80) */
+#define POINTOPS2_CELL_FWD_VALU160 4    /* VALU forward, table image of 160 rows (80 < L <= 160, forward only) */
+int pointops2_cell_forward_variant(const pointops2_cell_plan *plan, int h, int hdim, int L, int bf16);
 
 /* ---- the data-side step in front of the path ----
  * voxel keys of util/voxelize.py:46-59,79-84 (floor(coord / voxel), the FNV-style 64-bit hash of the three cells) and the

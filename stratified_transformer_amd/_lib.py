@@ -103,7 +103,19 @@ RESULTS = {
     "pointops2_partitions4_workspace_bytes": ([I], Z),
     "pointops2_row_order_workspace_bytes": ([I], Z),
     "pointops2_cell_plan_workspace_bytes": ([I], Z),
+    "pointops2_cell_forward_variant": ([P, I, I, I, I], I),
 }
+
+# codes of pointops2_cell_forward_variant (POINTOPS2_CELL_FWD_* of include/pointops2_hip.h): the forward kernel a cell launch runs
+CELL_FWD = {"error": -1, "none": 0, "mfma64": 1, "mfma80": 2, "valu80": 3, "valu160": 4}
+
+
+def cell_forward_variant(plan, h, L, bf16=False, hdim=16):
+    """Name (a key of CELL_FWD) of the forward kernel cell_attention runs on `plan` (index_build.CellPlan, or a bare
+    index_build.CellPlanStruct, or None) for h heads, tables of L rows and fp32 / bf16 storage.  Reads host fields only."""
+    arg = None if plan is None else plan.c_arg() if hasattr(plan, "c_arg") else ctypes.byref(plan)
+    code = lib().pointops2_cell_forward_variant(arg, int(h), int(hdim), int(L), int(bool(bf16)))
+    return {v: k for k, v in CELL_FWD.items()}[code]
 
 
 def exported_symbols():

@@ -729,38 +729,56 @@ __global__ __launch_bounds__(CT_WAVES * 64) void cell_table_grad3_kernel(pointop
     else cell_table_grad_body<TA, false, float>(pl, h, L, pbuf, plane, grad_out, gtv);
 }
 
+// The forward kernel a launch runs (codes of pointops2_cell_forward_variant): launch_cell_fwd takes its decision from here alone,
+// so the table the tests pin is the one that runs.  *why = the error a refusal records (NULL otherwise).
+static int cell_fwd_variant(const pointops2_cell_plan *plan, int h, int hdim, int L, bool bf16, const char **why) {
+    *why = nullptr;
+    if (plan == nullptr || plan->n_points <= 0) return POINTOPS2_CELL_FWD_NONE;
+    if (hdim != 16) { *why = "cell_attention: d != 16"; return POINTOPS2_CELL_FWD_ERROR; }
+    if (L < 1) { *why = "cell_attention: no table rows"; return POINTOPS2_CELL_FWD_ERROR; }
+    // relp's indices were clamped to [0, plan->table_rows) and L is the axis stride of the LDS table image
+    if (L != plan->table_rows) { *why = "cell_attention: the tables' row count differs from the plan's table_rows"; return POINTOPS2_CELL_FWD_ERROR; }
+    if (L > 160) { *why = "cell_attention: more than 160 table rows (use the operators)"; return POINTOPS2_CELL_FWD_ERROR; }
+    if (L > 80) return POINTOPS2_CELL_FWD_VALU160;
+    if (!bf16) {
+        // The matrix-core forward (cell_attn_mfma.hip) where it was measured faster than the VALU walkers (tools/bench_cell.py, MI355X,
+        // the four stages of the S3DIS scene, even / odd pattern, us MFMA : VALU): 292:321 / 372:300, 163:193 / 190:180,
+        // 114:152 / 117:120, 103:150 / 92:96.  The matrix-core tiles are 16 queries wide: the shifted pattern of the two large stages
+        // cuts the cloud into many cells of ~9 queries (n_pairs / n_keyslots), whose tiles stay half empty.
+        const double avg_queries = (double)plan->n_pairs / (double)(plan->n_keyslots > 0 ? plan->n_keyslots : 1);
+        if (!((long long)plan->n_points * h >= 96000 && avg_queries < 15.0)) return L <= 64 ? POINTOPS2_CELL_FWD_MFMA64 : POINTOPS2_CELL_FWD_MFMA80;
+    }
+    return POINTOPS2_CELL_FWD_VALU80;
+}
+
 template <typename T>
 static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const T *q, const T *k, const T *v, const T *table_q,
                             const T *table_k, const T *table_v, float *out, float *ml, float *pbuf) {
-    if (plan == nullptr || plan->n_points <= 0) return;
-    if (hdim != 16) { set_error("cell_attention: d != 16"); return; }
-    if (L < 1) { set_error("cell_attention: no table rows"); return; }
-    // relp's indices were clamped to [0, plan->table_rows) and L is the axis stride of the LDS table image
-    if (L != plan->table_rows) { set_error("cell_attention: the tables' row count differs from the plan's table_rows"); return; }
+    const char *why;
+    const int variant = cell_fwd_variant(plan, h, hdim, L, !std::is_same<T, float>::value, &why);
+    if (why != nullptr) { set_error(why); return; }
+    if (variant == POINTOPS2_CELL_FWD_NONE) return;
     if constexpr (std::is_same<T, float>::value) {
-        // the matrix-core forward (cell_attn_mfma.hip) where it was measured faster than the VALU walkers below
-        if (cell_fwd_mfma_launch(st, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf)) {
+        if (variant == POINTOPS2_CELL_FWD_MFMA64 || variant == POINTOPS2_CELL_FWD_MFMA80) {
+            cell_fwd_mfma_launch(st, variant, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf);
             check_launch();
             return;
         }
     }
     const dim3 block(CA_WAVES * 64);
     const size_t plane = (size_t)plan->n_pairs;
-    if (L <= 80) {
+    if (variant == POINTOPS2_CELL_FWD_VALU80) {
         const size_t lds = TabGeo<80>::bytes(sizeof(T));
         allow_big_lds(cell_fwd_kernel<CA_NP, 80, T>, lds);
         const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
         hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 80, T>), grid, block, lds, st, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
                            pbuf, plane);
-    } else if (L <= 160) {
+    } else {  // POINTOPS2_CELL_FWD_VALU160
         const size_t lds = TabGeo<160>::bytes(sizeof(T));
         allow_big_lds(cell_fwd_kernel<CA_NP, 160, T>, lds);
         const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
         hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 160, T>), grid, block, lds, st, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
                            pbuf, plane);
-    } else {
-        set_error("cell_attention: more than 160 table rows (use the operators)");
-        return;
     }
     check_launch();
 }
@@ -801,6 +819,11 @@ static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int
 using namespace p2;
 
 extern "C" {
+
+int pointops2_cell_forward_variant(const pointops2_cell_plan *plan, int h, int hdim, int L, int bf16) {
+    const char *why;
+    return cell_fwd_variant(plan, h, hdim, L, bf16 != 0, &why);
+}
 
 void cell_attention_forward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *q, const float *k,
                                      const float *v, const float *table_q, const float *table_k, const float *table_v, float *out,

@@ -316,18 +316,12 @@ static void launch_mfma_fwd(hipStream_t st, const pointops2_cell_plan *plan, int
                        pbuf, (size_t)plan->n_pairs);
 }
 
-// fp32 operands, d = 16, L <= 80.  Returns false when the matrix-core forward does not apply (the caller then runs cell_attn.hip's).
-bool cell_fwd_mfma_launch(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v, const float *table_q,
-                          const float *table_k, const float *table_v, float *out, float *pbuf) {
-    // Where it was measured faster than cell_attn.hip's VALU forward (tools/bench_cell.py, MI355X, the four stages of the S3DIS scene, even / odd pattern, us MFMA : VALU): 292:321 / 372:300,
-    // 163:193 / 190:180, 114:152 / 117:120, 103:150 / 92:96.  The matrix-core tiles are 16 queries wide: the shifted pattern of the
-    // two large stages cuts the cloud into many cells of ~9 queries (n_pairs / n_keyslots), whose tiles stay half empty.
-    if (L > 80) return false;
-    const double avg_queries = (double)plan->n_pairs / (double)(plan->n_keyslots > 0 ? plan->n_keyslots : 1);
-    if ((long long)plan->n_points * h >= 96000 && avg_queries < 15.0) return false;
-    if (L <= 64) launch_mfma_fwd<64>(st, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf);
+// fp32 operands, d = 16; variant = POINTOPS2_CELL_FWD_MFMA64 (L <= 64) or POINTOPS2_CELL_FWD_MFMA80 (L <= 80), as
+// pointops2_cell_forward_variant (cell_attn.hip) chose it.
+void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v,
+                          const float *table_q, const float *table_k, const float *table_v, float *out, float *pbuf) {
+    if (variant == POINTOPS2_CELL_FWD_MFMA64) launch_mfma_fwd<64>(st, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf);
     else launch_mfma_fwd<80>(st, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf);
-    return true;
 }
 
 }  // namespace p2

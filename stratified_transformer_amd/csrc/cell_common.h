@@ -159,8 +159,9 @@ static int cell_grid_x(int per_cu, int tasks, int h, int waves) {
     return max(1, min(cap, div_up(tasks, waves)));
 }
 
-// cell_attn_mfma.hip: the forward on the matrix cores (fp32 operands, L <= 80); false = does not apply
-bool cell_fwd_mfma_launch(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v, const float *table_q,
-                          const float *table_k, const float *table_v, float *out, float *pbuf);
+// cell_attn_mfma.hip: the forward on the matrix cores (fp32 operands), variant POINTOPS2_CELL_FWD_MFMA64 or _MFMA80 of
+// pointops2_cell_forward_variant (cell_attn.hip decides)
+void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v,
+                          const float *table_q, const float *table_k, const float *table_v, float *out, float *pbuf);
 
 }  // namespace p2

@@ -1038,13 +1038,21 @@ def test_fused_window_attention_matches_the_operator_chain(P, case):
 
 # ---- window-centric ("cell") attention: csrc/index.hip cells + csrc/cell_attn.hip ----------------------
 def _cell_scene(n, nbatch, w, quant, seed, L, cap=0):
-    from stratified_transformer_amd import index_build, scene
+    from stratified_transformer_amd import scene
     sizes = [n // nbatch + (1 if i < n % nbatch else 0) for i in range(nbatch)]
     xyz_np, offset = scene.make_batch(sizes, seed=seed)
+    even, odd = _cell_plans(xyz_np, offset, w, quant, seed, L, cap)
+    return xyz_np, offset, even, odd
+
+
+def _cell_plans(xyz_np, offset, w, quant, seed, L, cap=0):
+    """even and odd block index (with their cell plans) of a cloud, on a seeded random downsample of n // 8 + b points"""
+    from stratified_transformer_amd import index_build
+    n, nbatch = xyz_np.shape[0], offset.shape[0]
     rng = np.random.default_rng(seed)
     ds = np.sort(rng.permutation(n)[: n // 8 + nbatch]).astype(np.int32)
     even, odd, _ = index_build.stage_index_hip(dev(xyz_np), dev(offset), w, quant, dev(ds), cell_table_rows=L, cell_max_queries=cap)
-    return xyz_np, offset, even, odd
+    return even, odd
 
 
 def _expand_cells(plan):
@@ -1168,6 +1176,162 @@ def test_cell_attention_rejects_tables_the_plan_was_not_built_for():
     fused.cell_attention(*mk(L, True), plan).sum().backward()   # the matching size still runs
     torch.cuda.synchronize()
     assert dataclasses.replace(plan, struct=None).c_arg() is not None
+
+
+# ---- each forward instance of the cell attention (pointops2_cell_forward_variant) against the oracle ---------------------
+_CELL_GRADS = ("q", "k", "v", "table_q", "table_k", "table_v")
+
+
+def _cell_operands(n, h, L, seed):
+    rng = np.random.default_rng(seed)
+    p = {x: rng.standard_normal((n, h, 16), dtype=np.float32) for x in ("q", "k", "v")}
+    for t in ("table_q", "table_k", "table_v"):
+        p[t] = rng.standard_normal((L, h, 16, 3), dtype=np.float32) * 0.5
+    return p, rng.standard_normal((n, h, 16), dtype=np.float32)
+
+
+def _cell_launch(plan, ops, L, go=None):
+    """The cell forward (and with grad_out `go` its backward) through the C ABI, fp32 or bf16 storage by the operands' dtype:
+    out, and the six gradients in fp32 as the kernels wrote them (fused.cell_attention casts a bf16 operand's to bf16)."""
+    from stratified_transformer_amd import _lib
+    n, h, _ = ops[0].shape
+    sfx = "_bf16" if ops[0].dtype == torch.bfloat16 else ""
+    f32 = dict(dtype=torch.float32, device="cuda")
+    out, ml, pbuf = torch.empty(n, h, 16, **f32), torch.empty(n, h, 2, **f32), torch.empty(h, max(plan.n_pairs, 1), **f32)
+    ptrs = [_lib.ptr(t) for t in ops]
+    _lib.call(f"cell_attention_forward{sfx}_launcher", plan.c_arg(), h, 16, L, *ptrs, _lib.ptr(out), _lib.ptr(ml), _lib.ptr(pbuf), device=out.device)
+    if go is None:
+        return out, None
+    gsbuf = torch.empty_like(pbuf)
+    grads = [torch.empty(n, h, 16, **f32)] + [torch.zeros(t.shape, **f32) for t in ops[1:]]  # grad_q fully written, the rest accumulated
+    _lib.call(f"cell_attention_backward{sfx}_launcher", plan.c_arg(), h, 16, L, _lib.ptr(dev(go)), *ptrs[:3], _lib.ptr(out), *ptrs[3:], _lib.ptr(pbuf),
+              _lib.ptr(gsbuf), *[_lib.ptr(g) for g in grads], device=out.device)
+    return out, dict(zip(_CELL_GRADS, grads))
+
+
+def _cell_variant_vs_oracle(blk, L, h, bf16, expect, seed, backward=True):
+    """Asserts that the forward launcher picks `expect` for this pattern, then runs it (and the backward) on random operands and
+    compares with the oracle's operator chain on the pattern's CSR pair list.  bf16: the oracle runs on the bf16-rounded operands
+    widened back to fp32 - the kernels' arithmetic is fp32, so the bars are those of the fp32 kernels."""
+    from stratified_transformer_amd import _lib
+    got = _lib.cell_forward_variant(blk.cells, h, L, bf16=bf16)
+    assert got == expect, (got, expect, blk.cells.n_points * h, blk.cells.n_pairs / max(blk.cells.n_keyslots, 1))
+    p, go = _cell_operands(blk.cells.n_points, h, L, seed)
+    ops = [dev(p[x]) for x in _CELL_GRADS]
+    if bf16:
+        ops = [t.bfloat16() for t in ops]
+        p = {x: _np(t.float()) for x, t in zip(_CELL_GRADS, ops)}
+    out, grads = _cell_launch(blk.cells, ops, L, go if backward else None)
+    i1, offs, rel = _np(blk.index_1), _np(blk.offsets), np.clip(_np(blk.rel_idx), 0, L - 1).astype(np.int32)
+    if not backward:
+        sm = ref.segment_softmax(ref.attention_step1_v2(p["q"], p["k"], i1, offs) + ref.dot_prod_with_idx_v3(p["q"], offs, p["k"], i1, p["table_q"], p["table_k"], rel), offs)
+        np.testing.assert_allclose(_np(out), ref.attention_step2_with_rel_pos_value_v2(sm, p["v"], offs, i1, p["table_v"], rel), rtol=2e-5, atol=1e-4,
+                                   err_msg=f"{expect} forward")
+        return
+    want, wgrads = _oracle_attention(p, i1, offs, rel, go)
+    np.testing.assert_allclose(_np(out), want, rtol=2e-5, atol=1e-4, err_msg=f"{expect} forward")
+    for name in _CELL_GRADS:
+        tol = TTOL if name.startswith("table") else dict(rtol=2e-5, atol=2e-4)
+        scale = max(1.0, float(np.abs(wgrads[name]).max())) if name.startswith("table") else 1.0
+        np.testing.assert_allclose(_np(grads[name]) / scale, wgrads[name] / scale, err_msg=f"{expect} grad {name}", **tol)
+
+
+def _cell_nk(plan):
+    return np.diff(_np(plan.cell_kbase)[: plan.n_cells + 1])
+
+
+# name: (points per batch element, w, quant, h, cap (None: index_build.cell_query_cap, as the production pass), fp32 variant of the
+# (even, odd) pattern, least keys of the largest cell).  L = 2 * int(2w / quant): 64, or 80 at w / quant = 20.
+_CELL_VARIANT_SCENES = {
+    "mfma64_h1": ([3000], 0.16, 0.01, 1, 16, ("mfma64", "mfma64"), 0),
+    "mfma80_h3": ([4000], 0.1, 0.005, 3, 32, ("mfma80", "mfma80"), 0),
+    # S3DIS stage 0 at n * h = 96000 with the production cut: the shifted pattern's small cells take the VALU forward
+    "stage0_h12_production_cap": ([8000], 0.16, 0.01, 12, None, ("mfma64", "valu80"), 0),
+    "stage0_h3_cap8": ([32000], 0.16, 0.01, 3, 8, ("valu80", "valu80"), 0),
+    # big cells cut into pieces of 8 queries (each with the whole key list): n * h >= 96000 at an average below 15 queries, cells of
+    # more than 128 keys (two or more register chunks: running max / sum in `ml`, logits parked in pbuf) ...
+    "two_chunks_L80_h8_cap8": ([6000, 6000], 0.3, 0.015, 8, 8, ("valu80", "valu80"), 129),
+    # ... and of more than 256 (three or more)
+    "three_chunks_h12_cap8": ([8000], 0.32, 0.02, 12, 8, ("valu80", "valu80"), 257),
+}
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+@pytest.mark.parametrize("case", list(_CELL_VARIANT_SCENES))
+def test_cell_forward_variant_matches_the_oracle(case, dtype):
+    """Forward and all six gradients of each forward instance of the cell attention (fp32: matrix cores at L <= 64 / 80, VALU at
+    n * h >= 96000 with small cells, single- and multi-chunk; bf16 storage: the VALU forward always, with the bf16 backward and both
+    table-gradient instances, TA = 4 at L <= 64 and TA = 5 at L = 80) against the oracle, even and odd pattern, at the bars of
+    test_cell_attention_matches_the_oracle.  Multi-chunk cases also hold a cell with more than 128 keys whose last chunk is not a
+    whole number of 16-key passes."""
+    from stratified_transformer_amd import index_build, scene
+    sizes, w, quant, h, cap, variants, nk_least = _CELL_VARIANT_SCENES[case]
+    L = 2 * int((2 * w + 1e-4) // quant)
+    n = sum(sizes)
+    cap = index_build.cell_query_cap(n, h) if cap is None else cap
+    xyz_np, offset = scene.make_batch(sizes, seed=n + h)
+    bf16 = dtype == "bfloat16"
+    for blk, variant in zip(_cell_plans(xyz_np, offset, w, quant, n + h, L, cap), variants):
+        plan = blk.cells
+        if nk_least:
+            nk = _cell_nk(plan)
+            assert plan.nk_max >= nk_least, plan.nk_max
+            assert ((nk > 128) & (nk % 16 != 0)).any(), plan.nk_max
+        _cell_variant_vs_oracle(blk, L, h, bf16, ("valu80" if bf16 else variant), seed=h)
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+@pytest.mark.parametrize("L", [96, 160])
+def test_cell_forward_with_more_than_80_table_rows_matches_the_oracle(L, dtype):
+    """The forward-only instance for 80 < L <= 160 (inference), fp32 and bf16 storage, against the oracle's forward chain; the
+    L = 96 scene holds cells of more than 128 keys (more than one register chunk)."""
+    n, h, w, quant = dict([(96, (4000, 3, 0.24, 0.01)), (160, (3000, 2, 0.2, 0.005))])[L]
+    assert 2 * int((2 * w + 1e-4) // quant) == L
+    _, _, even, odd = _cell_scene(n, 1, w, quant, seed=L, L=L, cap=16)
+    if L == 96:
+        assert even.cells.nk_max > 128, even.cells.nk_max
+    with torch.no_grad():
+        for blk in (even, odd):
+            _cell_variant_vs_oracle(blk, L, h, dtype == "bfloat16", "valu160", seed=L, backward=False)
+
+
+def _degenerate_cloud(case):
+    """the clouds of test_partitions_by_one_sort_on_degenerate_clouds"""
+    rng = np.random.default_rng(5)
+    if case == "one_point":
+        return np.array([[0.3, 0.2, 0.1]], np.float32), np.array([1], np.int32)
+    if case == "five_coincident_points":
+        return np.tile(np.array([[1.0, 2.0, 3.0]], np.float32), (5, 1)), np.array([5], np.int32)
+    xyz_np = np.concatenate([rng.random((1, 3)), rng.random((2, 3)) * 0.1, rng.random((700, 3)) * 2.0]).astype(np.float32)
+    return xyz_np, np.array([1, 3, 703], np.int32)
+
+
+@pytest.mark.parametrize("case", ["one_point", "five_coincident_points", "tiny_batch_elements"])
+def test_cell_attention_on_degenerate_clouds_matches_the_oracle(case):
+    """One point, coincident points (one cell holding every key) and batch elements of 1 and 2 points beside a larger one, through
+    the cell kernels against the oracle, forward and backward.  These clouds are far below n * h = 96000, so fp32 reaches the
+    matrix-core forward (mfma64); bf16 storage reaches the VALU forward (valu80) and the bf16 backward; the fp32 VALU kernel code is
+    reached with tables of 96 rows (valu160, forward only)."""
+    xyz_np, offset = _degenerate_cloud(case)
+    h = 3
+    for blk in _cell_plans(xyz_np, offset, 0.16, 0.01, 5, 64, 16):
+        _cell_variant_vs_oracle(blk, 64, h, False, "mfma64", seed=1)
+        _cell_variant_vs_oracle(blk, 64, h, True, "valu80", seed=2)
+    with torch.no_grad():
+        for blk in _cell_plans(xyz_np, offset, 0.24, 0.01, 5, 96, 16):
+            _cell_variant_vs_oracle(blk, 96, h, False, "valu160", seed=3, backward=False)
+
+
+def test_cell_attention_on_tiny_batch_elements_in_a_large_scene_matches_the_oracle():
+    """Batch elements of 1 and 2 points in front of an 8000-point room at h = 12 (n * h >= 96000) with pieces of 8 queries: the fp32
+    VALU forward (valu80, both patterns) and the bf16 path on cells of one and two points, forward and backward, against the oracle."""
+    from stratified_transformer_amd import scene
+    rng = np.random.default_rng(6)
+    xyz_np = np.concatenate([rng.random((1, 3)), rng.random((2, 3)) * 0.1, scene.make_room(8000, 6)]).astype(np.float32)
+    offset = np.array([1, 3, 8003], np.int32)
+    for blk in _cell_plans(xyz_np, offset, 0.16, 0.01, 6, 64, 8):
+        _cell_variant_vs_oracle(blk, 64, 12, False, "valu80", seed=4)
+        _cell_variant_vs_oracle(blk, 64, 12, True, "valu80", seed=5)
 
 
 # ---- the C ABI with the reference's arguments and allocation pattern alone (SURVEY 8b seam B2) ----------------------

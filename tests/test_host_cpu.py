@@ -162,6 +162,46 @@ def test_library_exports_every_symbol_of_the_header():
     assert _lib.lib().pointops2_abi_version() >= 3
 
 
+def _cell_plan_struct(n_points, n_pairs, n_keyslots, table_rows):
+    """a pointops2_cell_plan with the host fields the forward dispatch reads and no device arrays"""
+    return index_build.CellPlanStruct(n_points=n_points, n_cells=1, n_parents=1, n_pairs=n_pairs, n_keyslots=n_keyslots, table_rows=table_rows)
+
+
+def test_cell_forward_dispatch_table():
+    """pointops2_cell_forward_variant, from which the cell forward launchers take their decision, on each side of every boundary:
+    fp32 with L <= 80 runs on the matrix cores unless n_points * h >= 96000 and the cells average fewer than 15 queries
+    (n_pairs / n_keyslots); L in 81..160 and bf16 storage run the VALU kernels; d != 16, L > 160 and tables the plan was not
+    built for are errors."""
+    text = open(os.path.join(ROOT, "include", "pointops2_hip.h")).read()
+    codes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define POINTOPS2_CELL_FWD_(\w+)\s+\(?(-?\d+)\)?", text)}
+    assert codes == _lib.CELL_FWD
+    v = _lib.cell_forward_variant
+    small, big = 15 * 10, 149  # n_pairs over 10 key slots: an average of 15.0 / 14.9 queries per cell
+    for L, mfma in ((1, "mfma64"), (64, "mfma64"), (65, "mfma80"), (80, "mfma80")):
+        for n, h in ((95999, 1), (96000, 1), (31999, 3), (32000, 3), (7999, 12), (8000, 12)):
+            wide = n * h >= 96000
+            assert v(_cell_plan_struct(n, small, 10, L), h, L) == mfma, (L, n, h)
+            assert v(_cell_plan_struct(n, big, 10, L), h, L) == ("valu80" if wide else mfma), (L, n, h)
+            for pairs in (small, big):
+                assert v(_cell_plan_struct(n, pairs, 10, L), h, L, bf16=True) == "valu80", (L, n, h, pairs)
+        # no key slots at all: the average is taken over one
+        assert v(_cell_plan_struct(96000, 14, 0, L), 1, L) == "valu80"
+        assert v(_cell_plan_struct(96000, 15, 0, L), 1, L) == mfma
+    for L in (81, 96, 160):
+        for n, pairs, bf16 in ((100, 10, False), (96000, big, False), (96000, small, True), (100, 10, True)):
+            assert v(_cell_plan_struct(n, pairs, 10, L), 1, L, bf16=bf16) == "valu160", (L, n, bf16)
+    for bf16 in (False, True):
+        assert v(_cell_plan_struct(100, 10, 10, 161), 1, 161, bf16=bf16) == "error"
+        assert v(_cell_plan_struct(100, 10, 10, 0), 1, 0, bf16=bf16) == "error"
+        for hdim in (8, 15, 17, 32):
+            assert v(_cell_plan_struct(100, 10, 10, 64), 1, 64, bf16=bf16, hdim=hdim) == "error", hdim
+        for L in (63, 65, 96):  # tables of another row count than the plan's table_rows
+            assert v(_cell_plan_struct(100, 10, 10, 64), 1, L, bf16=bf16) == "error", L
+        # nothing to launch: no plan, no points
+        assert v(None, 1, 64, bf16=bf16) == "none"
+        assert v(_cell_plan_struct(0, 0, 0, 64), 1, 64, bf16=bf16) == "none"
+
+
 def test_launch_opts_struct_matches_the_header(tmp_path):
     """_lib.LaunchOpts mirrors pointops2_launch_opts field by field: a layout mismatch would hand the library misplaced
     pointers without any error.  The host C compiler reports sizeof and every offsetof of the header's struct."""
