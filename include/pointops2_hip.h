@@ -38,7 +38,8 @@ void pointops2_set_stream(void *hip_stream);
 void *pointops2_get_stream(void);
 /* NULL when the last call on this thread succeeded; otherwise a static message.  Reading clears. */
 const char *pointops2_last_error(void);
-/* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters) */
+/* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
+ * cell_attention_qkv_*_launcher pair) */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -382,6 +383,23 @@ void cell_attention_backward_bf16_launcher(const pointops2_cell_plan *plan, int 
                                            const uint16_t *k, const uint16_t *v, const float *out, const uint16_t *table_q,
                                            const uint16_t *table_k, const uint16_t *table_v, const float *pbuf, float *gsbuf, float *grad_q,
                                            float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v);
+/* The same on the PACKED projection (ABI version 5): qkv [N, 3, h, 16] contiguous as the model's qkv Linear returns it (:180), read in
+ * place - point i's q, k, v rows of head t start at element i * 3 * h * 16 + {0, 1, 2} * h * 16 + t * 16.  row_type is the storage
+ * type of qkv: fp32, IEEE half or bf16 (raw 16-bit patterns; what the Linear yields under autocast); the tables are fp32 and so are
+ * the arithmetic (on exactly widened operands), out, ml, pbuf and every gradient.  q is scaled as it is loaded:
+ * q' = round_to_row_type(float(q) * scale), which is `query * self.scale` (:181) bit for bit.  The forward kernel is the one
+ * pointops2_cell_forward_variant(plan, h, hdim, L, 0) names.  Backward: grad_qkv [N, 3, h, 16] fp32 receives scale * dL/dq' (written
+ * for every query of the launch's cells) and dL/dk, dL/dv (ACCUMULATED); zero-fill it and the three table gradients.
+ * Errors as the unpacked launchers record them, and for a row_type that is none of the three. */
+#define POINTOPS2_ROWS_F32  0
+#define POINTOPS2_ROWS_F16  1
+#define POINTOPS2_ROWS_BF16 2
+void cell_attention_qkv_forward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const void *qkv, int row_type, float scale,
+                                         const float *table_q, const float *table_k, const float *table_v, float *out, float *ml, float *pbuf);
+void cell_attention_qkv_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const void *qkv, int row_type,
+                                          float scale, const float *out, const float *table_q, const float *table_k, const float *table_v,
+                                          const float *pbuf, float *gsbuf, float *grad_qkv, float *grad_table_q, float *grad_table_k,
+                                          float *grad_table_v);
 
 #ifdef __cplusplus
 }

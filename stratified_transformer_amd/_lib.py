@@ -90,6 +90,8 @@ SIGNATURES = {
     "cell_attention_backward_launcher": [P, I, I, I] + [P] * 16,
     "cell_attention_forward_bf16_launcher": [P, I, I, I] + [P] * 9,
     "cell_attention_backward_bf16_launcher": [P, I, I, I] + [P] * 16,
+    "cell_attention_qkv_forward_launcher": [P, I, I, I, P, I, F] + [P] * 6,
+    "cell_attention_qkv_backward_launcher": [P, I, I, I, P, P, I, F] + [P] * 10,
 }
 # entry points with a non-void result
 RESULTS = {
@@ -108,6 +110,8 @@ RESULTS = {
 
 # codes of pointops2_cell_forward_variant (POINTOPS2_CELL_FWD_* of include/pointops2_hip.h): the forward kernel a cell launch runs
 CELL_FWD = {"error": -1, "none": 0, "mfma64": 1, "mfma80": 2, "valu80": 3, "valu160": 4}
+# storage type of the rows of a packed qkv (POINTOPS2_ROWS_*): cell_attention_qkv_*_launcher
+ROW_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 def cell_forward_variant(plan, h, L, bf16=False, hdim=16):

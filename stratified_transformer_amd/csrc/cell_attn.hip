@@ -28,16 +28,6 @@
 namespace p2 {
 
 
-// ---- storage type of q / k / v / tables: fp32, or bf16 (BASELINE config 3's second leg: bf16 storage, fp32 arithmetic;
-// the reference's operators are fp32-only, stratified_transformer.py:183,194,208 `.float()`) ----
-typedef unsigned short bf16_t;  // raw bits
-__device__ __forceinline__ float4 ld_row4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 ld_row4(const bf16_t *p) {
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);  // four bf16: widening to fp32 is a shift
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-}
-__device__ __forceinline__ float ld_elem(const float *p) { return *p; }
-__device__ __forceinline__ float ld_elem(const bf16_t *p) { return __uint_as_float((unsigned)*p << 16); }
 // image of one head's table: [axis][row][16] elements of T (global layout [L, h, 16, 3])
 template <typename T>
 __device__ __forceinline__ void stage_table_t(T *lds, const T *__restrict__ tab, int L, int h, int head) {
@@ -123,10 +113,20 @@ __device__ __forceinline__ void dispatch_passes(int np, F f) {
     }
 }
 
-template <typename T>
+// TT: storage type of the tables.  PK: the rows are those of a packed projection - rs (elements from one point's q / k / v row to the
+// next, gradients laid out alike) and qscale (q is scaled as it is loaded, round_rows) come from the launch.  Otherwise the rows are
+// [N, h, 16] tensors: rs = C, q is taken as it stands, and the instances are the ones the unpacked launchers always ran.
+template <typename TT, bool PK>
 struct LaneCtx {
-    const T *lds;
-    int L, lane, p, c, head, h, C, hoff;
+    const TT *lds;
+    int L, lane, p, c, head, h, C, hoff, rs_packed;
+    float qscale;
+    __device__ __forceinline__ int rs() const { return PK ? rs_packed : C; }
+    template <typename RT>
+    __device__ __forceinline__ float4 q_row4(const RT *q, int i) const {
+        if constexpr (PK) return scaled_row4<RT>(q + (size_t)i * rs_packed + hoff, qscale);
+        else return ld_row4(q + (size_t)i * C + hoff);
+    }
 };
 struct CellBufs {
     rsrc_t rel, key, qid;
@@ -138,26 +138,26 @@ struct CellBufs {
 // Key slots: lane (p, c) of an NPA-pass instance owns the NPA CONSECUTIVE keys j0 + p * NPA + t, t < NPA, of the chunk, so
 // that its rel-pos words, softmax weights and logit gradients of one query are NPA consecutive dwords = one wide load.
 // Query ids: 64 at a time, one per lane; a query's id is then a v_readlane away (a scalar: the q row address is uniform).
-template <int NPA, typename T>
-__device__ __forceinline__ void load_key_rows(const LaneCtx<T> &x, const CellBufs &cb, const T *__restrict__ rows, int j0, float4 (&r4)[NPA]) {
+template <int NPA, typename RT, typename T, bool PK>
+__device__ __forceinline__ void load_key_rows(const LaneCtx<T, PK> &x, const CellBufs &cb, const RT *__restrict__ rows, int j0, float4 (&r4)[NPA]) {
     unsigned keys[NPA];
     bload_words<NPA>(cb.key, (j0 + x.p * NPA) * 4, keys);  // (past the end: key 0, never used)
 #pragma unroll
-    for (int t = 0; t < NPA; t++) r4[t] = ld_row4(rows + (size_t)keys[t] * x.C + x.hoff);
+    for (int t = 0; t < NPA; t++) r4[t] = ld_row4(rows + (size_t)keys[t] * x.rs() + x.hoff);
 }
 
-template <int NPA, int TS, typename T>
-__device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_p,
-                                                 const T *__restrict__ q, const T *__restrict__ k, float *__restrict__ ml,
+template <int NPA, int TS, typename RT, typename T, bool PK>
+__device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T, PK> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_p,
+                                                 const RT *__restrict__ q, const RT *__restrict__ k, float *__restrict__ ml,
                                                  int ch, bool single, int j0, int nkc) {
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);  // this lane's slots inside the chunk
     float4 k4[NPA];
-    load_key_rows<NPA, T>(x, cb, k, j0, k4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, k, j0, k4);
     // the inputs of query il+1 are requested while query il is worked on
     int ids = (int)bload_u32(cb.qid, x.lane * 4);
     int i_nx = __builtin_amdgcn_readlane(ids, 0);
-    float4 q4_nx = ld_row4(q + (size_t)i_nx * x.C + x.hoff);
+    float4 q4_nx = x.q_row4(q, i_nx);
     unsigned w_nx[NPA];
     bload_words<NPA>(cb.rel, (j0 + p * NPA) * 4, w_nx);
     for (int il = 0; il < ct.nq; il++) {
@@ -169,7 +169,7 @@ __device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T> &x, const Cell
         const int roff = (il * ct.nk + j0 + p * NPA) * 4;
         if (((il + 1) & 63) == 0) ids = (int)bload_u32(cb.qid, (il + 1 + x.lane) * 4);
         i_nx = __builtin_amdgcn_readlane(ids, (il + 1) & 63);  // (past the end: query 0, never used)
-        q4_nx = ld_row4(q + (size_t)i_nx * x.C + x.hoff);
+        q4_nx = x.q_row4(q, i_nx);
         bload_words<NPA>(cb.rel, roff + ct.nk * 4, w_nx);
         float lg[NPA];
         float mx = -INFINITY;
@@ -220,14 +220,14 @@ __device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T> &x, const Cell
     }
 }
 
-template <int NPA, int TS, typename T>
-__device__ __forceinline__ void fwd_sweep_values(const LaneCtx<T> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_p,
-                                                 const T *__restrict__ v, const float *__restrict__ ml, float *__restrict__ out,
+template <int NPA, int TS, typename RT, typename T, bool PK>
+__device__ __forceinline__ void fwd_sweep_values(const LaneCtx<T, PK> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_p,
+                                                 const RT *__restrict__ v, const float *__restrict__ ml, float *__restrict__ out,
                                                  int ch, bool single, int j0, int nkc) {
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);
     float4 v4[NPA];
-    load_key_rows<NPA, T>(x, cb, v, j0, v4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, v, j0, v4);
     unsigned w_nx[NPA];
     float a_nx[NPA];
     bload_words<NPA>(cb.rel, (j0 + p * NPA) * 4, w_nx);
@@ -272,21 +272,23 @@ __device__ __forceinline__ void fwd_sweep_values(const LaneCtx<T> &x, const Cell
     }
 }
 
-template <int NP, int LCAP, typename T>
-__global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_plan pl, int h, int L, const T *__restrict__ q,
-                                                                 const T *__restrict__ k, const T *__restrict__ v,
+template <int NP, int LCAP, typename RT, typename T, bool PK>
+__global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_plan pl, int h, int L, const RT *__restrict__ q,
+                                                                 const RT *__restrict__ k, const RT *__restrict__ v, int rs, float qscale,
                                                                  const T *__restrict__ table_q, const T *__restrict__ table_k,
                                                                  const T *__restrict__ table_v, float *__restrict__ out,
                                                                  float *__restrict__ ml, float *__restrict__ pbuf, size_t plane) {
     constexpr int D = 16, TS = TabGeo<LCAP>::TS;
     extern __shared__ float lds_raw[];
     T *lds = reinterpret_cast<T *>(lds_raw);
-    LaneCtx<T> x;
+    LaneCtx<T, PK> x;
     x.lds = lds;
     x.L = L;
     x.h = h;
     x.head = blockIdx.y;
     x.C = h * D;
+    x.rs_packed = rs;
+    x.qscale = qscale;
     x.lane = threadIdx.x & 63;
     x.p = x.lane >> 2;
     x.c = x.lane & 3;
@@ -313,13 +315,13 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
         for (int ch = 0; ch < nch; ch++) {  // sweep 1: logits and softmax
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
-                fwd_sweep_logits<decltype(tag)::value, TS, T>(x, ct, cb, rs_p, q, k, ml, ch, nch == 1, j0, nkc);
+                fwd_sweep_logits<decltype(tag)::value, TS, RT, T, PK>(x, ct, cb, rs_p, q, k, ml, ch, nch == 1, j0, nkc);
             });
         }
         for (int ch = 0; ch < nch; ch++) {  // sweep 2: out = sum p (v + Tv)
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
-                fwd_sweep_values<decltype(tag)::value, TS, T>(x, ct, cb, rs_p, v, ml, out, ch, nch == 1, j0, nkc);
+                fwd_sweep_values<decltype(tag)::value, TS, RT, T, PK>(x, ct, cb, rs_p, v, ml, out, ch, nch == 1, j0, nkc);
             });
         }
     }
@@ -330,9 +332,9 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
 // ------------------------------------------------------------------------------------------------
 // adds the key-side accumulators of pass t (lane (p, c): floats 4c..4c+3 of the key j0 + p * NPA + t) to grad[key, head, :]:
 // through a wave-private LDS tile, so that one atomic instruction covers four whole 64-byte head rows
-template <int NPA, typename T>
+template <int NPA, typename T, bool PK>
 __device__ __forceinline__ void flush_key_pass(float *scr, float4 acc, rsrc_t rs_key, int j0, int t, int nkc, float *__restrict__ grad,
-                                               const LaneCtx<T> &x) {
+                                               const LaneCtx<T, PK> &x) {
     *reinterpret_cast<float4 *>(scr + x.p * 16 + 4 * x.c) = acc;
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
@@ -341,21 +343,21 @@ __device__ __forceinline__ void flush_key_pass(float *scr, float4 acc, rsrc_t rs
         const int s = (x.lane >> 4) + 4 * kk;
         const int jl = s * NPA + t;
         const int key = (int)bload_u32(rs_key, (j0 + jl) * 4);
-        if (jl < nkc) unsafeAtomicAdd(grad + (size_t)key * x.C + x.head * 16 + (x.lane & 15), scr[s * 16 + (x.lane & 15)]);
+        if (jl < nkc) unsafeAtomicAdd(grad + (size_t)key * x.rs() + x.head * 16 + (x.lane & 15), scr[s * 16 + (x.lane & 15)]);
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
 }
 
 // sweep A: grad_attn = <go, v + Tv>, gs = p (grad_attn - <go, out>) stored, dV += p go
-template <int NPA, int TS, typename T>
-__device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_p, rsrc_t rs_g,
+template <int NPA, int TS, typename RT, typename T, bool PK>
+__device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T, PK> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_p, rsrc_t rs_g,
                                                  float *scr, const float *__restrict__ go, const float *__restrict__ out,
-                                                 const T *__restrict__ v, float *__restrict__ grad_v, int j0, int nkc) {
+                                                 const RT *__restrict__ v, float *__restrict__ grad_v, int j0, int nkc) {
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);
     float4 v4[NPA], dv4[NPA];
-    load_key_rows<NPA, T>(x, cb, v, j0, v4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, v, j0, v4);
 #pragma unroll
     for (int t = 0; t < NPA; t++) dv4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
     unsigned w_nx[NPA];
@@ -397,18 +399,18 @@ __device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T> &x, const Cell
         if (c == 0) bstore_floats<NPA>(rs_g, roff, gs, nvalid);
     }
 #pragma unroll
-    for (int t = 0; t < NPA; t++) flush_key_pass<NPA, T>(scr, dv4[t], cb.key, j0, t, nkc, grad_v, x);
+    for (int t = 0; t < NPA; t++) flush_key_pass<NPA, T, PK>(scr, dv4[t], cb.key, j0, t, nkc, grad_v, x);
 }
 
 // sweep B: dQ = sum gs (k + Tq), dK += gs (q + Tk)
-template <int NPA, int TS, typename T>
-__device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_g, float *scr,
-                                               const T *__restrict__ q, const T *__restrict__ k, float *__restrict__ grad_q,
+template <int NPA, int TS, typename RT, typename T, bool PK>
+__device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T, PK> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_g, float *scr,
+                                               const RT *__restrict__ q, const RT *__restrict__ k, float *__restrict__ grad_q,
                                                float *__restrict__ grad_k, int ch, int j0, int nkc) {
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);
     float4 k4[NPA], dk4[NPA];
-    load_key_rows<NPA, T>(x, cb, k, j0, k4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, k, j0, k4);
 #pragma unroll
     for (int t = 0; t < NPA; t++) dk4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
     unsigned w_nx[NPA];
@@ -417,7 +419,7 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T> &x, const CellTa
     bload_floats<NPA>(rs_g, (j0 + p * NPA) * 4, g_nx);
     int ids = (int)bload_u32(cb.qid, x.lane * 4);
     int i_nx = __builtin_amdgcn_readlane(ids, 0);
-    float4 q_nx = ld_row4(q + (size_t)i_nx * x.C + x.hoff);
+    float4 q_nx = x.q_row4(q, i_nx);
     for (int il = 0; il < ct.nq; il++) {
         const int i = i_nx;
         const int roff = (il * ct.nk + j0 + p * NPA) * 4;
@@ -431,7 +433,7 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T> &x, const CellTa
         }
         if (((il + 1) & 63) == 0) ids = (int)bload_u32(cb.qid, (il + 1 + x.lane) * 4);
         i_nx = __builtin_amdgcn_readlane(ids, (il + 1) & 63);
-        q_nx = ld_row4(q + (size_t)i_nx * x.C + x.hoff);
+        q_nx = x.q_row4(q, i_nx);
         bload_words<NPA>(cb.rel, roff + ct.nk * 4, w_nx);
         bload_floats<NPA>(rs_g, roff + ct.nk * 4, g_nx);
         float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -451,20 +453,21 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T> &x, const CellTa
             rk = rk1;
             __builtin_amdgcn_sched_barrier(0);
         }
-        const float4 tot = slots_sum16_4(dq);
+        float4 tot = slots_sum16_4(dq);
+        if constexpr (PK) tot = make_float4(tot.x * x.qscale, tot.y * x.qscale, tot.z * x.qscale, tot.w * x.qscale);  // dL/dq = scale * dL/dq'
         if (p == 0) {
-            float *o = grad_q + (size_t)i * x.C + x.hoff;
+            float *o = grad_q + (size_t)i * x.rs() + x.hoff;
             stg4(o, ch ? add4(tot, ldg4(o)) : tot);
         }
     }
 #pragma unroll
-    for (int t = 0; t < NPA; t++) flush_key_pass<NPA, T>(scr, dk4[t], cb.key, j0, t, nkc, grad_k, x);
+    for (int t = 0; t < NPA; t++) flush_key_pass<NPA, T, PK>(scr, dk4[t], cb.key, j0, t, nkc, grad_k, x);
 }
 
-template <int NP, int LCAP, typename T>
+template <int NP, int LCAP, typename RT, typename T, bool PK>
 __global__ __launch_bounds__(CA_WAVES_BWD * 64) void cell_bwd_kernel(pointops2_cell_plan pl, int h, int L, const float *__restrict__ go,
-                                                                 const T *__restrict__ q, const T *__restrict__ k,
-                                                                 const T *__restrict__ v, const float *__restrict__ out,
+                                                                 const RT *__restrict__ q, const RT *__restrict__ k,
+                                                                 const RT *__restrict__ v, int rs, float qscale, const float *__restrict__ out,
                                                                  const T *__restrict__ table_q, const T *__restrict__ table_k,
                                                                  const T *__restrict__ table_v, const float *__restrict__ pbuf,
                                                                  float *__restrict__ gsbuf, size_t plane, float *__restrict__ grad_q,
@@ -472,12 +475,14 @@ __global__ __launch_bounds__(CA_WAVES_BWD * 64) void cell_bwd_kernel(pointops2_c
     constexpr int D = 16, TS = TabGeo<LCAP>::TS;
     extern __shared__ float lds_raw[];
     T *lds = reinterpret_cast<T *>(lds_raw);
-    LaneCtx<T> x;
+    LaneCtx<T, PK> x;
     x.lds = lds;
     x.L = L;
     x.h = h;
     x.head = blockIdx.y;
     x.C = h * D;
+    x.rs_packed = rs;
+    x.qscale = qscale;
     x.lane = threadIdx.x & 63;
     x.p = x.lane >> 2;
     x.c = x.lane & 3;
@@ -507,13 +512,13 @@ __global__ __launch_bounds__(CA_WAVES_BWD * 64) void cell_bwd_kernel(pointops2_c
         for (int ch = 0; ch < nch; ch++) {
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
-                bwd_sweep_values<decltype(tag)::value, TS, T>(x, ct, cb, rs_p, rs_g, scr, go, out, v, grad_v, j0, nkc);
+                bwd_sweep_values<decltype(tag)::value, TS, RT, T, PK>(x, ct, cb, rs_p, rs_g, scr, go, out, v, grad_v, j0, nkc);
             });
         }
         for (int ch = 0; ch < nch; ch++) {
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
-                bwd_sweep_keys<decltype(tag)::value, TS, T>(x, ct, cb, rs_g, scr, q, k, grad_q, grad_k, ch, j0, nkc);
+                bwd_sweep_keys<decltype(tag)::value, TS, RT, T, PK>(x, ct, cb, rs_g, scr, q, k, grad_q, grad_k, ch, j0, nkc);
             });
         }
     }
@@ -561,15 +566,16 @@ struct CellTableGeo {
     static constexpr size_t lds_bytes() { return walk_bytes() > sum_bytes() ? walk_bytes() : sum_bytes(); }
 };
 
-template <int TA, bool BYKEY, typename XT>
+// X: rows of XT, xs elements apart; SC: taken times xscale as the forward took q (round_rows)
+template <int TA, bool BYKEY, bool SC, typename XT>
 __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &pl, int h, int L, const float *__restrict__ wbuf, size_t plane,
-                                                     const XT *__restrict__ X, float *__restrict__ grad_table) {
+                                                     const XT *__restrict__ X, int xs, float xscale, float *__restrict__ grad_table) {
     constexpr int D = 16;
     constexpr int MAXP = BYKEY ? 4 : 8;  // passes of 16 entries per row a segment holds in registers (a key's column is short)
     using G = CellTableGeo<TA>;
     extern __shared__ float lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int C = h * D, head = blockIdx.y;
+    const int head = blockIdx.y;
     const int p = lane >> 2, c = lane & 3;     // entry of a pass, row of the four
     const int kq = lane >> 4, col = lane & 15;  // MFMA operand coordinates: row of the four, bin / feature
     int *hist = reinterpret_cast<int *>(lds) + wave * 4 * G::ROW;  // [4][ROW], private to the wave
@@ -661,7 +667,7 @@ __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &
             }
         }
         int pt_n = (int)bload_u32(rs_row, kq * 4);
-        float xv_n = ld_elem(X + (size_t)pt_n * C + head * D + col);  // B operand: X[point of row r0 + kq, head, col]
+        float xv_n = SC ? scaled_elem<XT>(X + (size_t)pt_n * xs + head * D + col, xscale) : ld_elem(X + (size_t)pt_n * xs + head * D + col);  // B operand: X[point of row r0 + kq, head, col]
         pt_n = (int)bload_u32(rs_row, (4 + kq) * 4);
         for (int r0 = 0; r0 < nrows; r0 += 4) {
             unsigned wr[MAXP];
@@ -672,7 +678,7 @@ __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &
                 wt[t] = wt_n[t];
             }
             const float xv = r0 + kq < nrows ? xv_n : 0.f;
-            xv_n = ld_elem(X + (size_t)pt_n * C + head * D + col);
+            xv_n = SC ? scaled_elem<XT>(X + (size_t)pt_n * xs + head * D + col, xscale) : ld_elem(X + (size_t)pt_n * xs + head * D + col);
             pt_n = (int)bload_u32(rs_row, (r0 + 8 + kq) * 4);
 #pragma unroll
             for (int t = 0; t < MAXP; t++)
@@ -718,15 +724,16 @@ __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &
 
 // the three table gradients of a block as ONE grid (blockIdx.z: 0 = key side, the longest, first in dispatch order; 1 = query side;
 // 2 = value side): each of them alone is short of independent work on the small stages, together they overlap
-template <int TA, typename T>
+template <int TA, typename T, bool PK>
 __global__ __launch_bounds__(CT_WAVES * 64) void cell_table_grad3_kernel(pointops2_cell_plan pl, int h, int L, const float *__restrict__ gsbuf,
                                                                          const float *__restrict__ pbuf, size_t plane,
                                                                          const T *__restrict__ q, const T *__restrict__ k,
                                                                          const float *__restrict__ grad_out, float *__restrict__ gtq,
-                                                                         float *__restrict__ gtk, float *__restrict__ gtv) {
-    if (blockIdx.z == 0) cell_table_grad_body<TA, true, T>(pl, h, L, gsbuf, plane, k, gtk);
-    else if (blockIdx.z == 1) cell_table_grad_body<TA, false, T>(pl, h, L, gsbuf, plane, q, gtq);
-    else cell_table_grad_body<TA, false, float>(pl, h, L, pbuf, plane, grad_out, gtv);
+                                                                         float *__restrict__ gtk, float *__restrict__ gtv, int rs, float qscale) {
+    const int xs = PK ? rs : h * 16;
+    if (blockIdx.z == 0) cell_table_grad_body<TA, true, false, T>(pl, h, L, gsbuf, plane, k, xs, 1.0f, gtk);
+    else if (blockIdx.z == 1) cell_table_grad_body<TA, false, PK, T>(pl, h, L, gsbuf, plane, q, xs, qscale, gtq);
+    else cell_table_grad_body<TA, false, false, float>(pl, h, L, pbuf, plane, grad_out, h * 16, 1.0f, gtv);
 }
 
 // The forward kernel a launch runs (codes of pointops2_cell_forward_variant): launch_cell_fwd takes its decision from here alone,
@@ -751,16 +758,19 @@ static int cell_fwd_variant(const pointops2_cell_plan *plan, int h, int hdim, in
     return POINTOPS2_CELL_FWD_VALU80;
 }
 
-template <typename T>
-static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const T *q, const T *k, const T *v, const T *table_q,
-                            const T *table_k, const T *table_v, float *out, float *ml, float *pbuf) {
+// RT / TT: storage types of the rows and of the tables.  q, k, v: the first point's row of each.  PK (the packed entry points): rs
+// elements to the next point's, q scaled as it is loaded; otherwise rs = h * 16 and scale = 1 are what the kernels assume.
+template <typename RT, typename TT, bool PK>
+static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const RT *q, const RT *k, const RT *v, int rs, float scale,
+                            const TT *table_q, const TT *table_k, const TT *table_v, float *out, float *ml, float *pbuf) {
     const char *why;
-    const int variant = cell_fwd_variant(plan, h, hdim, L, !std::is_same<T, float>::value, &why);
+    const int variant = cell_fwd_variant(plan, h, hdim, L, !std::is_same<TT, float>::value, &why);
     if (why != nullptr) { set_error(why); return; }
     if (variant == POINTOPS2_CELL_FWD_NONE) return;
-    if constexpr (std::is_same<T, float>::value) {
+    if constexpr (std::is_same<TT, float>::value) {
         if (variant == POINTOPS2_CELL_FWD_MFMA64 || variant == POINTOPS2_CELL_FWD_MFMA80) {
-            cell_fwd_mfma_launch(st, variant, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf);
+            constexpr int row_type = std::is_same<RT, float>::value ? POINTOPS2_ROWS_F32 : std::is_same<RT, f16_t>::value ? POINTOPS2_ROWS_F16 : POINTOPS2_ROWS_BF16;
+            cell_fwd_mfma_launch(st, variant, plan, h, L, row_type, PK, q, k, v, rs, scale, table_q, table_k, table_v, out, pbuf);
             check_launch();
             return;
         }
@@ -768,34 +778,35 @@ static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int
     const dim3 block(CA_WAVES * 64);
     const size_t plane = (size_t)plan->n_pairs;
     if (variant == POINTOPS2_CELL_FWD_VALU80) {
-        const size_t lds = TabGeo<80>::bytes(sizeof(T));
-        allow_big_lds(cell_fwd_kernel<CA_NP, 80, T>, lds);
+        const size_t lds = TabGeo<80>::bytes(sizeof(TT));
+        allow_big_lds(cell_fwd_kernel<CA_NP, 80, RT, TT, PK>, lds);
         const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
-        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 80, T>), grid, block, lds, st, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
+        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 80, RT, TT, PK>), grid, block, lds, st, *plan, h, L, q, k, v, rs, scale, table_q, table_k, table_v, out, ml,
                            pbuf, plane);
     } else {  // POINTOPS2_CELL_FWD_VALU160
-        const size_t lds = TabGeo<160>::bytes(sizeof(T));
-        allow_big_lds(cell_fwd_kernel<CA_NP, 160, T>, lds);
+        const size_t lds = TabGeo<160>::bytes(sizeof(TT));
+        allow_big_lds(cell_fwd_kernel<CA_NP, 160, RT, TT, PK>, lds);
         const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
-        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 160, T>), grid, block, lds, st, *plan, h, L, q, k, v, table_q, table_k, table_v, out, ml,
+        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 160, RT, TT, PK>), grid, block, lds, st, *plan, h, L, q, k, v, rs, scale, table_q, table_k, table_v, out, ml,
                            pbuf, plane);
     }
     check_launch();
 }
 
-template <typename T>
-static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const T *q, const T *k, const T *v,
-                            const float *out, const T *table_q, const T *table_k, const T *table_v, const float *pbuf, float *gsbuf, float *grad_q,
-                            float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
+// grad_q / grad_k / grad_v: the first point's row of each, laid out as the rows they belong to
+template <typename RT, typename TT, bool PK>
+static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const RT *q, const RT *k, const RT *v,
+                            int rs, float scale, const float *out, const TT *table_q, const TT *table_k, const TT *table_v, const float *pbuf, float *gsbuf,
+                            float *grad_q, float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
     if (plan == nullptr || plan->n_points <= 0) return;
     if (hdim != 16) { set_error("cell_attention: d != 16"); return; }
     if (L < 1 || L > 80) { set_error("cell_attention backward: table rows L must be in 1..80"); return; }
     if (L != plan->table_rows) { set_error("cell_attention backward: the tables' row count differs from the plan's table_rows"); return; }
-    const size_t lds = TabGeo<80>::bytes(sizeof(T)) + (size_t)CA_WAVES_BWD * 256 * sizeof(float);
-    allow_big_lds(cell_bwd_kernel<CA_NP_BWD, 80, T>, lds);
+    const size_t lds = TabGeo<80>::bytes(sizeof(TT)) + (size_t)CA_WAVES_BWD * 256 * sizeof(float);
+    allow_big_lds(cell_bwd_kernel<CA_NP_BWD, 80, RT, TT, PK>, lds);
     const size_t plane = (size_t)plan->n_pairs;
-    hipLaunchKernelGGL((cell_bwd_kernel<CA_NP_BWD, 80, T>), dim3(cell_grid_x(1, plan->n_cells, h, CA_WAVES_BWD), h),
-                       dim3(CA_WAVES_BWD * 64), lds, st, *plan, h, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, plane, grad_q,
+    hipLaunchKernelGGL((cell_bwd_kernel<CA_NP_BWD, 80, RT, TT, PK>), dim3(cell_grid_x(1, plan->n_cells, h, CA_WAVES_BWD), h),
+                       dim3(CA_WAVES_BWD * 64), lds, st, *plan, h, L, grad_out, q, k, v, rs, scale, out, table_q, table_k, table_v, pbuf, gsbuf, plane, grad_q,
                        grad_k, grad_v);
     // the three table gradients read p / gs only
     // Grid of the table-gradient bodies: ONE workgroup of 8 waves per free CU and body (round 2: two of 12).
@@ -807,10 +818,10 @@ static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int
     // it does not.)  The three as ONE grid rather than three launches in a row: backward of a block 10-120 us shorter, most on the small
     // stages.
     const dim3 grid3(cell_grid_x(1, plan->n_cells, h, CT_WAVES), h, 3), tblock(CT_WAVES * 64);
-    if (L <= 64) hipLaunchKernelGGL((cell_table_grad3_kernel<4, T>), grid3, tblock, CellTableGeo<4>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
-                                    grad_table_q, grad_table_k, grad_table_v);
-    else hipLaunchKernelGGL((cell_table_grad3_kernel<5, T>), grid3, tblock, CellTableGeo<5>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
-                            grad_table_q, grad_table_k, grad_table_v);
+    if (L <= 64) hipLaunchKernelGGL((cell_table_grad3_kernel<4, RT, PK>), grid3, tblock, CellTableGeo<4>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
+                                    grad_table_q, grad_table_k, grad_table_v, rs, scale);
+    else hipLaunchKernelGGL((cell_table_grad3_kernel<5, RT, PK>), grid3, tblock, CellTableGeo<5>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
+                            grad_table_q, grad_table_k, grad_table_v, rs, scale);
     check_launch();
 }
 
@@ -828,27 +839,70 @@ int pointops2_cell_forward_variant(const pointops2_cell_plan *plan, int h, int h
 void cell_attention_forward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *q, const float *k,
                                      const float *v, const float *table_q, const float *table_k, const float *table_v, float *out,
                                      float *ml, float *pbuf) {
-    launch_cell_fwd<float>(begin_launch().stream, plan, h, hdim, L, q, k, v, table_q, table_k, table_v, out, ml, pbuf);
+    launch_cell_fwd<float, float, false>(begin_launch().stream, plan, h, hdim, L, q, k, v, h * 16, 1.0f, table_q, table_k, table_v, out, ml, pbuf);
 }
 void cell_attention_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const float *q,
                                       const float *k, const float *v, const float *out, const float *table_q, const float *table_k,
                                       const float *table_v, const float *pbuf, float *gsbuf, float *grad_q, float *grad_k,
                                       float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
-    launch_cell_bwd<float>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
+    launch_cell_bwd<float, float, false>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, h * 16, 1.0f, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
                            grad_table_k, grad_table_v);
 }
 // bf16 storage of q / k / v / tables (raw 16-bit patterns), fp32 arithmetic, fp32 outputs and gradients
 void cell_attention_forward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const uint16_t *q, const uint16_t *k,
                                           const uint16_t *v, const uint16_t *table_q, const uint16_t *table_k, const uint16_t *table_v,
                                           float *out, float *ml, float *pbuf) {
-    launch_cell_fwd<bf16_t>(begin_launch().stream, plan, h, hdim, L, q, k, v, table_q, table_k, table_v, out, ml, pbuf);
+    launch_cell_fwd<bf16_t, bf16_t, false>(begin_launch().stream, plan, h, hdim, L, q, k, v, h * 16, 1.0f, table_q, table_k, table_v, out, ml, pbuf);
 }
 void cell_attention_backward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const uint16_t *q,
                                            const uint16_t *k, const uint16_t *v, const float *out, const uint16_t *table_q,
                                            const uint16_t *table_k, const uint16_t *table_v, const float *pbuf, float *gsbuf, float *grad_q,
                                            float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
-    launch_cell_bwd<bf16_t>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
+    launch_cell_bwd<bf16_t, bf16_t, false>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, h * 16, 1.0f, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
                             grad_table_k, grad_table_v);
+}
+
+// The rows of the packed projection qkv [N, 3, h, 16] read in place (fp32, half or bf16: what the model's qkv Linear returns, under
+// autocast too); fp32 tables, arithmetic, outputs and gradients.  q is scaled as it is loaded; grad_qkv receives scale * dL/dq'.
+void cell_attention_qkv_forward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const void *qkv, int row_type, float scale,
+                                         const float *table_q, const float *table_k, const float *table_v, float *out, float *ml, float *pbuf) {
+    const hipStream_t st = begin_launch().stream;
+    const int C = h * 16;
+    if (row_type == POINTOPS2_ROWS_F32) {
+        const float *r = static_cast<const float *>(qkv);
+        launch_cell_fwd<float, float, true>(st, plan, h, hdim, L, r, r + C, r + 2 * C, 3 * C, scale, table_q, table_k, table_v, out, ml, pbuf);
+    } else if (row_type == POINTOPS2_ROWS_F16) {
+        const f16_t *r = static_cast<const f16_t *>(qkv);
+        launch_cell_fwd<f16_t, float, true>(st, plan, h, hdim, L, r, r + C, r + 2 * C, 3 * C, scale, table_q, table_k, table_v, out, ml, pbuf);
+    } else if (row_type == POINTOPS2_ROWS_BF16) {
+        const bf16_t *r = static_cast<const bf16_t *>(qkv);
+        launch_cell_fwd<bf16_t, float, true>(st, plan, h, hdim, L, r, r + C, r + 2 * C, 3 * C, scale, table_q, table_k, table_v, out, ml, pbuf);
+    } else {
+        set_error("cell_attention_qkv: unknown row_type");
+    }
+}
+void cell_attention_qkv_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const void *qkv, int row_type,
+                                          float scale, const float *out, const float *table_q, const float *table_k, const float *table_v,
+                                          const float *pbuf, float *gsbuf, float *grad_qkv, float *grad_table_q, float *grad_table_k,
+                                          float *grad_table_v) {
+    const hipStream_t st = begin_launch().stream;
+    const int C = h * 16;
+    float *g = grad_qkv;
+    if (row_type == POINTOPS2_ROWS_F32) {
+        const float *r = static_cast<const float *>(qkv);
+        launch_cell_bwd<float, float, true>(st, plan, h, hdim, L, grad_out, r, r + C, r + 2 * C, 3 * C, scale, out, table_q, table_k, table_v, pbuf, gsbuf, g, g + C,
+                                      g + 2 * C, grad_table_q, grad_table_k, grad_table_v);
+    } else if (row_type == POINTOPS2_ROWS_F16) {
+        const f16_t *r = static_cast<const f16_t *>(qkv);
+        launch_cell_bwd<f16_t, float, true>(st, plan, h, hdim, L, grad_out, r, r + C, r + 2 * C, 3 * C, scale, out, table_q, table_k, table_v, pbuf, gsbuf, g, g + C,
+                                      g + 2 * C, grad_table_q, grad_table_k, grad_table_v);
+    } else if (row_type == POINTOPS2_ROWS_BF16) {
+        const bf16_t *r = static_cast<const bf16_t *>(qkv);
+        launch_cell_bwd<bf16_t, float, true>(st, plan, h, hdim, L, grad_out, r, r + C, r + 2 * C, 3 * C, scale, out, table_q, table_k, table_v, pbuf, gsbuf, g, g + C,
+                                       g + 2 * C, grad_table_q, grad_table_k, grad_table_v);
+    } else {
+        set_error("cell_attention_qkv backward: unknown row_type");
+    }
 }
 
 }  // extern "C"

@@ -79,10 +79,12 @@ __device__ __forceinline__ void stage_fragments(float *img, const float *__restr
 // One wave, one (cell piece, head), 16 queries at a time.  The sweeps over a chunk's key tiles are pipelined by hand: what a step
 // (axis, key tile) needs from memory - the tile's key rows, its packed rel-pos words - is requested one step ahead, so that only
 // the logits of the chunk (4 registers per key tile) live across steps.
-template <int LP>
-__global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(pointops2_cell_plan pl, int h, int L, const float *__restrict__ q,
-                                                                                const float *__restrict__ k, const float *__restrict__ v,
-                                                                                const float *__restrict__ table_q, const float *__restrict__ table_k,
+// RT: storage type of the q / k / v rows.  PK: rows of a packed projection, row_stride elements from one point's row to the next, q
+// scaled as it is loaded (cell_common.h); otherwise [N, h, 16] tensors taken as they stand.
+template <int LP, typename RT, bool PK>
+__global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(pointops2_cell_plan pl, int h, int L, const RT *__restrict__ q,
+                                                                                const RT *__restrict__ k, const RT *__restrict__ v, int row_stride,
+                                                                                float qscale, const float *__restrict__ table_q, const float *__restrict__ table_k,
                                                                                 const float *__restrict__ table_v, float *__restrict__ out,
                                                                                 float *__restrict__ pbuf, size_t plane) {
     using G = CmGeo<LP>;
@@ -91,7 +93,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
     float *img_q = lds, *img_k = lds + G::TAB, *img_v = lds + 2 * G::TAB;
     const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int head = blockIdx.y, C = h * 16;
+    const int head = blockIdx.y, C = h * 16, rs = PK ? row_stride : C;
     float *qtb = lds + 3 * G::TAB + wave * G::WAVE_FLOATS;  // [16][RS]: QT of one axis, later the weight histogram H (ints)
     float *ktb = qtb + TILE;                                // [16][RS]: KT of one axis for one key tile
     stage_fragments<LP, true>(img_q, table_q, L, h, head);
@@ -117,7 +119,11 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
         for (int i0 = 0; i0 < ct.nq; i0 += 16) {
             const bool qok = i0 + n < ct.nq;
             const int qid = (int)bload_u32(rs_qid, (i0 + n) * 4);  // (past the end: 0, never used)
-            const float4 qf = qok ? ldg4(q + (size_t)qid * C + hoff) : make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 qf = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (qok) {
+                if constexpr (PK) qf = scaled_row4<RT>(q + (size_t)qid * rs + hoff, qscale);
+                else qf = ld_row4(q + (size_t)qid * rs + hoff);
+            }
             const int row_off = (i0 + n) * ct.nk * 4;  // byte offset of this lane's query row in the tile
             f32x4c acc = zero4;                         // out^T: D[feature 4g + t][query n]
             float run_m = -INFINITY, run_l = 0.f;
@@ -128,7 +134,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                 int keyid[NKT];
 #pragma unroll
                 for (int kt = 0; kt < NKT; kt++) keyid[kt] = (int)bload_u32(rs_key, (j0 + 16 * kt + n) * 4);  // (past the end: 0, masked below)
-                float4 kf_nx = ldg4(k + (size_t)keyid[0] * C + hoff);
+                float4 kf_nx = ld_row4(k + (size_t)keyid[0] * rs + hoff);
                 unsigned w_nx[4];
                 bload_words<4>(rs_rel, row_off + (j0 + 4 * g) * 4, w_nx);
 #pragma unroll 1
@@ -149,7 +155,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                             {   // the next step's inputs: the next key tile of this axis, or the first one of the next axis
                                 const int kn = kt + 1 < nkt ? kt + 1 : 0;
                                 const int key_n = kt + 1 < nkt ? keyid[kt + 1 < NKT ? kt + 1 : 0] : keyid[0];
-                                kf_nx = ldg4(k + (size_t)key_n * C + hoff);
+                                kf_nx = ld_row4(k + (size_t)key_n * rs + hoff);
                                 bload_words<4>(rs_rel, row_off + (j0 + 16 * kn + 4 * g) * 4, w_nx);
                             }
                             if (ax == 0) {
@@ -191,10 +197,10 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                 for (int kt = 0; kt < NKT; kt++)
                     if (kt < nkt) {
                         float4 vf;  // A[feature n][k-slot (s, g) <-> key 4g + s]
-                        vf.x = v[(size_t)kid_nx[0] * C + head * 16 + n];
-                        vf.y = v[(size_t)kid_nx[1] * C + head * 16 + n];
-                        vf.z = v[(size_t)kid_nx[2] * C + head * 16 + n];
-                        vf.w = v[(size_t)kid_nx[3] * C + head * 16 + n];
+                        vf.x = ld_elem(v + (size_t)kid_nx[0] * rs + head * 16 + n);
+                        vf.y = ld_elem(v + (size_t)kid_nx[1] * rs + head * 16 + n);
+                        vf.z = ld_elem(v + (size_t)kid_nx[2] * rs + head * 16 + n);
+                        vf.w = ld_elem(v + (size_t)kid_nx[3] * rs + head * 16 + n);
                         if (kt + 1 < nkt) bload_words<4>(rs_key, (j0 + 16 * (kt + 1) + 4 * g) * 4, kid_nx);
                         acc = mfma4(vf, make_float4(lg[kt][0], lg[kt][1], lg[kt][2], lg[kt][3]), acc);  // D[feature 4g + t][query n]
                     }
@@ -305,23 +311,34 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
     }
 }
 
-template <int LP>
-static void launch_mfma_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v, const float *table_q,
-                            const float *table_k, const float *table_v, float *out, float *pbuf) {
+template <int LP, typename RT, bool PK>
+static void launch_mfma_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const RT *q, const RT *k, const RT *v, int rs, float scale,
+                            const float *table_q, const float *table_k, const float *table_v, float *out, float *pbuf) {
     using G = CmGeo<LP>;
     const size_t lds = G::lds_bytes();
-    allow_big_lds(cell_fwd_mfma_kernel<LP>, lds);
+    allow_big_lds(cell_fwd_mfma_kernel<LP, RT, PK>, lds);
     const dim3 grid(cell_grid_x(1, plan->n_cells, h, G::WAVES), h);
-    hipLaunchKernelGGL((cell_fwd_mfma_kernel<LP>), grid, dim3(G::WAVES * 64), lds, st, *plan, h, L, q, k, v, table_q, table_k, table_v, out,
+    hipLaunchKernelGGL((cell_fwd_mfma_kernel<LP, RT, PK>), grid, dim3(G::WAVES * 64), lds, st, *plan, h, L, q, k, v, rs, scale, table_q, table_k, table_v, out,
                        pbuf, (size_t)plan->n_pairs);
 }
+template <typename RT, bool PK>
+static void launch_mfma_rows(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, const void *q, const void *k, const void *v, int rs,
+                             float scale, const float *table_q, const float *table_k, const float *table_v, float *out, float *pbuf) {
+    const RT *qr = static_cast<const RT *>(q), *kr = static_cast<const RT *>(k), *vr = static_cast<const RT *>(v);
+    if (variant == POINTOPS2_CELL_FWD_MFMA64) launch_mfma_fwd<64, RT, PK>(st, plan, h, L, qr, kr, vr, rs, scale, table_q, table_k, table_v, out, pbuf);
+    else launch_mfma_fwd<80, RT, PK>(st, plan, h, L, qr, kr, vr, rs, scale, table_q, table_k, table_v, out, pbuf);
+}
 
-// fp32 operands, d = 16; variant = POINTOPS2_CELL_FWD_MFMA64 (L <= 64) or POINTOPS2_CELL_FWD_MFMA80 (L <= 80), as
-// pointops2_cell_forward_variant (cell_attn.hip) chose it.
-void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, const float *q, const float *k, const float *v,
-                          const float *table_q, const float *table_k, const float *table_v, float *out, float *pbuf) {
-    if (variant == POINTOPS2_CELL_FWD_MFMA64) launch_mfma_fwd<64>(st, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf);
-    else launch_mfma_fwd<80>(st, plan, h, L, q, k, v, table_q, table_k, table_v, out, pbuf);
+// fp32 tables, d = 16; variant = POINTOPS2_CELL_FWD_MFMA64 (L <= 64) or POINTOPS2_CELL_FWD_MFMA80 (L <= 80), as
+// pointops2_cell_forward_variant (cell_attn.hip) chose it; row_type = POINTOPS2_ROWS_* (the caller passes no other).  Not packed: fp32
+// rows [N, h, 16] as they stand (row_stride and scale are not read).
+void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, int row_type, bool packed, const void *q,
+                          const void *k, const void *v, int row_stride, float scale, const float *table_q, const float *table_k, const float *table_v,
+                          float *out, float *pbuf) {
+    if (!packed) launch_mfma_rows<float, false>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
+    else if (row_type == POINTOPS2_ROWS_F16) launch_mfma_rows<f16_t, true>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
+    else if (row_type == POINTOPS2_ROWS_BF16) launch_mfma_rows<bf16_t, true>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
+    else launch_mfma_rows<float, true>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
 }
 
 }  // namespace p2

@@ -220,8 +220,8 @@ const char *pointops2_last_error(void) {
     return e;
 }
 void pointops2_diag_set_fps_patience(unsigned long long ticks_100mhz) { g_fps_patience = ticks_100mhz; }
-int pointops2_abi_version(void) { return 4; }  // 2: pointops2_cell_plan.table_rows, pointops2_csr_matches_launcher; 3: pointops2_launch_opts;
-                                               // 4: pointops2_cell_forward_variant
+int pointops2_abi_version(void) { return 5; }  // 2: pointops2_cell_plan.table_rows, pointops2_csr_matches_launcher; 3: pointops2_launch_opts;
+                                               // 4: pointops2_cell_forward_variant; 5: cell_attention_qkv_*_launcher
 void pointops2_set_launch_opts(const pointops2_launch_opts *opts) { state().opts = opts != nullptr ? *opts : pointops2_launch_opts{}; }
 
 void grouping_forward_cuda_launcher(int m, int nsample, int c, const float *input, const int *idx, float *output) {

@@ -166,3 +166,68 @@ def cell_attention(q, k, v, table_q, table_k, table_v, plan):
     pattern (index_build.stage_index_hip(..., cell_table_rows=L))  ->  [N, h, 16], same numbers as the five operators
     up to the order of the sums."""
     return CellAttention.apply(q, k, v, table_q, table_k, table_v, plan)
+
+
+class CellAttentionQKV(Function):
+    """CellAttention on the packed projection: the kernels read q, k, v rows out of qkv [N, 3, h, 16] where the model's qkv Linear
+    left them (fp32, or fp16 / bf16 under autocast), scale q as they load it and write one fp32 gradient buffer of qkv's shape.
+    Saved for the backward: qkv itself, the tables, out and pbuf - no [N, h, 16] copy of q, k or v."""
+
+    @staticmethod
+    def forward(ctx, qkv, scale, table_q, table_k, table_v, plan):
+        if qkv.dim() != 4 or qkv.shape[1] != 3:
+            raise RuntimeError("cell_attention_qkv: qkv must be [N, 3, h, 16], got %s" % (tuple(qkv.shape),))
+        N, _, h, hdim = qkv.shape
+        if hdim != 16:
+            raise RuntimeError("cell_attention: d != 16 (use the operators of pointops for other head dims)")
+        L = table_q.shape[0]
+        if plan.n_points != N:
+            raise RuntimeError("cell_attention: the plan was built for %d points, q/k/v have %d/%d/%d rows" % (plan.n_points, N, N, N))
+        if L != plan.table_rows:
+            raise RuntimeError("cell_attention: the plan was built for tables of %d rows (cell_table_rows), the tables have %d" % (plan.table_rows, L))
+        if L > 80 and any(ctx.needs_input_grad[:5]):
+            raise RuntimeError("cell_attention: the backward supports at most 80 table rows (L = %d): use the operators of pointops, "
+                               "or run the forward under torch.no_grad()" % L)
+        if qkv.dtype not in _lib.ROW_TYPES:
+            raise TypeError("cell_attention_qkv: qkv must be float32, float16 or bfloat16, got %s" % qkv.dtype)
+        f32 = torch.float32
+        pointops_cuda._chk((qkv, qkv.dtype, "qkv"), (table_q, f32, "table_q"), (table_k, f32, "table_k"), (table_v, f32, "table_v"))
+        assert table_k.shape == table_q.shape and table_v.shape == table_q.shape
+        dev = qkv.device
+        alloc = torch.zeros if plan.partial else torch.empty  # (a share of the cells: CellAttention.forward)
+        out = alloc((N, h, hdim), dtype=f32, device=dev)
+        ml = torch.empty((N, h, 2), dtype=f32, device=dev)
+        pbuf = alloc((h, max(plan.n_pairs, 1)), dtype=f32, device=dev)
+        _lib.call("cell_attention_qkv_forward_launcher", plan.c_arg(), h, hdim, L, ptr(qkv), _lib.ROW_TYPES[qkv.dtype], float(scale), ptr(table_q),
+                  ptr(table_k), ptr(table_v), ptr(out), ptr(ml), ptr(pbuf), device=dev)
+        ctx.plan, ctx.scale = plan, float(scale)
+        ctx.save_for_backward(qkv, table_q, table_k, table_v, out, pbuf)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qkv, table_q, table_k, table_v, out, pbuf = ctx.saved_tensors
+        plan = ctx.plan
+        N, _, h, hdim = qkv.shape
+        L = table_q.shape[0]
+        dev = qkv.device
+        grad_out = grad_out.contiguous()
+        pointops_cuda._chk((grad_out, torch.float32, "grad_out"))
+        gsbuf = torch.zeros_like(pbuf) if plan.partial else torch.empty_like(pbuf)
+        # the gradient of qkv and the three table gradients are views of ONE zero-filled buffer
+        nqkv, ntab = qkv.numel(), table_q.numel()
+        acc = torch.zeros(nqkv + 3 * ntab, dtype=torch.float32, device=dev)
+        grad_qkv = acc[:nqkv].view(qkv.shape)
+        gtq, gtk, gtv = (acc[nqkv + i * ntab:nqkv + (i + 1) * ntab].view(table_q.shape) for i in range(3))
+        _lib.call("cell_attention_qkv_backward_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(qkv), _lib.ROW_TYPES[qkv.dtype], ctx.scale,
+                  ptr(out), ptr(table_q), ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_qkv), ptr(gtq), ptr(gtk), ptr(gtv), device=dev)
+        if qkv.dtype != torch.float32:  # autograd wants a gradient of the operand's dtype; the sums above were taken in fp32
+            grad_qkv = grad_qkv.to(qkv.dtype)
+        return grad_qkv, None, gtq, gtk, gtv, None
+
+
+def cell_attention_qkv(qkv, scale, table_q, table_k, table_v, plan):
+    """qkv [N, 3, h, 16] contiguous, f32 / f16 / bf16: the qkv Linear's output as it stands (`self.qkv(feats).view(N, 3, h, 16)`, under
+    autocast too), q NOT yet scaled; scale: the model's `self.scale`; tables [L, h, 16, 3] f32; plan as for cell_attention
+    ->  [N, h, 16] f32: what cell_attention returns for (qkv[:, 0] * scale).float(), qkv[:, 1].float(), qkv[:, 2].float()."""
+    return CellAttentionQKV.apply(qkv, scale, table_q, table_k, table_v, plan)

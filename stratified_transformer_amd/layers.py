@@ -18,7 +18,8 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
     attention module (`_sta_block`).
   * WindowAttention.forward computes qkv / scale / proj exactly as :180-182,212-215 and replaces :183-208 (three operators, the
     `+`, scatter_softmax, two range asserts) by ONE autograd function: `fused.cell_attention` on the plan when BasicLayer handed
-    one over (d = 16, L <= 80 - every shipped config), else `fused.window_attention` on the pair list it was given (d = 16),
+    one over (d = 16, L <= 80 - every shipped config; under autocast `fused.cell_attention_qkv`, which reads the half qkv where
+    the Linear left it), else `fused.window_attention` on the pair list it was given (d = 16),
     else the five operators in the reference's order.  Called on its own (no plan), it needs nothing but the reference's
     arguments.
 
@@ -133,15 +134,22 @@ def window_attention_forward(self, feats, xyz, index_0, index_1, index_0_offsets
     assert index_0.shape[0] == index_1.shape[0]
     if not (self.rel_query and self.rel_key and self.rel_value) or not feats.is_cuda:
         return _original(self)(self, feats, xyz, index_0, index_1, index_0_offsets, n_max)
-    qkv = self.qkv(feats).reshape(N, 3, h, d).permute(1, 0, 2, 3).contiguous()          # :180
-    query, key, value = qkv[0], qkv[1], qkv[2]
-    query = (query * self.scale).float()                                                  # :182-183 (`.float()`: autocast)
-    key, value = key.float(), value.float()
     tq, tk, tv = (t.float().contiguous() for t in (self.relative_pos_query_table, self.relative_pos_key_table, self.relative_pos_value_table))
     L = int(tq.shape[0])
     blk = getattr(self, "_sta_block", None)
     plan = getattr(blk, "cells", None) if blk is not None else None
-    if plan is not None and d == 16 and L <= 80 and plan.table_rows == L and plan.n_points == N:
+    on_cells = plan is not None and d == 16 and L <= 80 and plan.table_rows == L and plan.n_points == N
+    qkv = self.qkv(feats)
+    if on_cells and qkv.dtype in (torch.float16, torch.bfloat16):
+        # autocast: the kernels read the half rows where the Linear left them, scale q as they load it (:181) and widen (:183):
+        # no permute copy, no multiply, no casts, and the half qkv is what the backward keeps
+        x = fused.cell_attention_qkv(qkv.contiguous().view(N, 3, h, d), self.scale, tq, tk, tv, plan)
+        return self.proj_drop(self.proj(x.view(N, C)))                                    # :212-215
+    qkv = qkv.reshape(N, 3, h, d).permute(1, 0, 2, 3).contiguous()                       # :180
+    query, key, value = qkv[0], qkv[1], qkv[2]
+    query = (query * self.scale).float()                                                  # :182-183 (`.float()`: autocast)
+    key, value = key.float(), value.float()
+    if on_cells:
         x = fused.cell_attention(query, key, value, tq, tk, tv, plan)
     else:
         offs, i1 = index_0_offsets.int().contiguous(), index_1.int().contiguous()

@@ -808,11 +808,19 @@ def _inverse_distance_weights(dist):
     return dist_recip / torch.sum(dist_recip, dim=1, keepdim=True)
 
 
+def _gather_operands(feat, idx, weight):
+    """A half `feat` (Upsample under autocast, model/stratified_transformer.py:341): the reference's loop multiplies it by fp32 weights,
+    which promotes every term to fp32 (:767-769), so the kernel gets fp32 copies and autograd casts the gradient back.  fp32: as given."""
+    if feat.dtype in (torch.float16, torch.bfloat16):
+        return feat.float(), idx, weight.float()
+    return feat, idx, weight
+
+
 def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
     """:756-770  inverse-distance weighted k-NN interpolation of feat (m, c) onto new_xyz (n, 3) -> (n, c); differentiable w.r.t. feat"""
     assert xyz.is_contiguous() and new_xyz.is_contiguous() and feat.is_contiguous()
     idx, dist = knnquery(k, xyz, new_xyz, offset, new_offset)
-    return _WeightedGather.apply(feat, idx, _inverse_distance_weights(dist))
+    return _WeightedGather.apply(*_gather_operands(feat, idx, _inverse_distance_weights(dist)))
 
 
 def interpolation_v2(xyz, new_xyz, feat, offset, new_offset, k=3):
@@ -820,7 +828,7 @@ def interpolation_v2(xyz, new_xyz, feat, offset, new_offset, k=3):
     assert xyz.is_contiguous() and new_xyz.is_contiguous() and feat.is_contiguous()
     idx, _ = knnquery(k, xyz, new_xyz, offset, new_offset)
     dist = torch.sqrt(((new_xyz.unsqueeze(1) - xyz[idx.long()]) ** 2).sum(-1) + 1e-8)
-    return _WeightedGather.apply(feat, idx, _inverse_distance_weights(dist))
+    return _WeightedGather.apply(*_gather_operands(feat, idx, _inverse_distance_weights(dist)))
 
 
 class Interpolation(Function):
