@@ -138,12 +138,18 @@ struct CellBufs {
 // Key slots: lane (p, c) of an NPA-pass instance owns the NPA CONSECUTIVE keys j0 + p * NPA + t, t < NPA, of the chunk, so
 // that its rel-pos words, softmax weights and logit gradients of one query are NPA consecutive dwords = one wide load.
 // Query ids: 64 at a time, one per lane; a query's id is then a v_readlane away (a scalar: the q row address is uniform).
+// A slot past the chunk's end reads key 0 from the bounds-checked list: its row is replaced by zeros, not left to a weight of 0 to
+// cancel (0 * inf = NaN: a non-finite row 0 would reach every cell with a partial last pass).
 template <int NPA, typename RT, typename T, bool PK>
-__device__ __forceinline__ void load_key_rows(const LaneCtx<T, PK> &x, const CellBufs &cb, const RT *__restrict__ rows, int j0, float4 (&r4)[NPA]) {
+__device__ __forceinline__ void load_key_rows(const LaneCtx<T, PK> &x, const CellBufs &cb, const RT *__restrict__ rows, int j0, int nvalid,
+                                              float4 (&r4)[NPA]) {
     unsigned keys[NPA];
-    bload_words<NPA>(cb.key, (j0 + x.p * NPA) * 4, keys);  // (past the end: key 0, never used)
+    bload_words<NPA>(cb.key, (j0 + x.p * NPA) * 4, keys);  // (past the end: key 0)
 #pragma unroll
-    for (int t = 0; t < NPA; t++) r4[t] = ld_row4(rows + (size_t)keys[t] * x.rs() + x.hoff);
+    for (int t = 0; t < NPA; t++) {
+        const float4 r = ld_row4(rows + (size_t)keys[t] * x.rs() + x.hoff);
+        r4[t] = t < nvalid ? r : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
 }
 
 template <int NPA, int TS, typename RT, typename T, bool PK>
@@ -153,7 +159,7 @@ __device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T, PK> &x, const 
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);  // this lane's slots inside the chunk
     float4 k4[NPA];
-    load_key_rows<NPA, RT, T, PK>(x, cb, k, j0, k4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, k, j0, nvalid, k4);
     // the inputs of query il+1 are requested while query il is worked on
     int ids = (int)bload_u32(cb.qid, x.lane * 4);
     int i_nx = __builtin_amdgcn_readlane(ids, 0);
@@ -227,7 +233,7 @@ __device__ __forceinline__ void fwd_sweep_values(const LaneCtx<T, PK> &x, const 
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);
     float4 v4[NPA];
-    load_key_rows<NPA, RT, T, PK>(x, cb, v, j0, v4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, v, j0, nvalid, v4);
     unsigned w_nx[NPA];
     float a_nx[NPA];
     bload_words<NPA>(cb.rel, (j0 + p * NPA) * 4, w_nx);
@@ -357,7 +363,7 @@ __device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T, PK> &x, const 
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);
     float4 v4[NPA], dv4[NPA];
-    load_key_rows<NPA, RT, T, PK>(x, cb, v, j0, v4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, v, j0, nvalid, v4);
 #pragma unroll
     for (int t = 0; t < NPA; t++) dv4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
     unsigned w_nx[NPA];
@@ -410,7 +416,7 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T, PK> &x, const Ce
     const int p = x.p, c = x.c;
     const int nvalid = min(max(nkc - p * NPA, 0), NPA);
     float4 k4[NPA], dk4[NPA];
-    load_key_rows<NPA, RT, T, PK>(x, cb, k, j0, k4);
+    load_key_rows<NPA, RT, T, PK>(x, cb, k, j0, nvalid, k4);
 #pragma unroll
     for (int t = 0; t < NPA; t++) dk4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
     unsigned w_nx[NPA];

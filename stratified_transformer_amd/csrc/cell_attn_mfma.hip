@@ -192,7 +192,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
             // ---- sweep 2 of a chunk: lg holds the softmax weights; out += P V + H Tv ----
             auto values_chunk = [&](int j0, int nkt) {
                 unsigned kid_nx[4];
-                bload_words<4>(rs_key, (j0 + 4 * g) * 4, kid_nx);  // keys 4g .. 4g + 3 of the tile (past the end: 0, weight 0)
+                bload_words<4>(rs_key, (j0 + 4 * g) * 4, kid_nx);  // keys 4g .. 4g + 3 of the tile (past the end: 0, masked below)
 #pragma unroll
                 for (int kt = 0; kt < NKT; kt++)
                     if (kt < nkt) {
@@ -201,6 +201,12 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                         vf.y = ld_elem(v + (size_t)kid_nx[1] * rs + head * 16 + n);
                         vf.z = ld_elem(v + (size_t)kid_nx[2] * rs + head * 16 + n);
                         vf.w = ld_elem(v + (size_t)kid_nx[3] * rs + head * 16 + n);
+                        // a slot past the end read v[key 0]: zeros instead, its weight of 0 does not cancel a non-finite row (0 * inf)
+                        const int left = ct.nk - (j0 + 16 * kt + 4 * g);
+                        vf.x = left > 0 ? vf.x : 0.f;
+                        vf.y = left > 1 ? vf.y : 0.f;
+                        vf.z = left > 2 ? vf.z : 0.f;
+                        vf.w = left > 3 ? vf.w : 0.f;
                         if (kt + 1 < nkt) bload_words<4>(rs_key, (j0 + 16 * (kt + 1) + 4 * g) * 4, kid_nx);
                         acc = mfma4(vf, make_float4(lg[kt][0], lg[kt][1], lg[kt][2], lg[kt][3]), acc);  // D[feature 4g + t][query n]
                     }
@@ -250,7 +256,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
 #pragma unroll 1
             for (int pass = 0; pass < npass; pass++) {
                 const float m_fin = run_m == -INFINITY ? 0.f : run_m;
-                const float inv_fin = run_l > 0.f ? 1.0f / run_l : 0.f;
+                const float inv_fin = run_l == 0.f ? 0.f : 1.0f / run_l;  // (0: an unused query slot; a NaN sum gives a NaN row, as the operators)
 #pragma unroll 1
                 for (int ch = 0; ch < nch; ch++) {
                     const int j0 = ch * 16 * NKT, nkt = (min(16 * NKT, ct.nk - j0) + 15) >> 4;
@@ -274,7 +280,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                                     sum += lg[kt][t];
                                 }
                             sum = col_sum(sum);
-                            const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+                            const float inv = sum == 0.f ? 0.f : 1.0f / sum;  // (0: an unused query slot; a NaN sum gives a NaN row, as the operators)
 #pragma unroll
                             for (int kt = 0; kt < NKT; kt++)
 #pragma unroll

@@ -5,7 +5,7 @@ autocast, and pointops.interpolation / interpolation_v2 on a half `feat`.
 The kernels widen the rows exactly and compute in fp32, and q is scaled as torch scales it (`query * self.scale` in q's dtype), so the
 oracle is fed q' = (qkv[:, 0] * scale) computed by torch in the row dtype and widened, k and v widened, and the bars are those of the
 fp32 kernels (tests/test_hip_parity.py::_cell_variant_vs_oracle): forward rtol 2e-5 / atol 1e-4, row gradients rtol 2e-5 / atol 2e-4,
-TTOL on the table gradients over their scale.  (Helpers copied from tests/test_hip_parity.py.)
+TTOL on the table gradients over their scale.  (Scene builders and launch helpers: tests/cell_edges.py.)
 """
 import os
 
@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import pointops_ref as ref
+from tests.cell_edges import (_CELL_VARIANT_SCENES, _SCALES, _cell_scene, _np, _oracle_attention, _oracle_operands, _packed_operands, _qkv_launch,
+                              _variant_scene)
 from tests.util import dev
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +24,6 @@ FTOL = dict(rtol=2e-5, atol=1e-4)
 GTOL = dict(rtol=2e-5, atol=2e-4)
 _TABLES = ("table_q", "table_k", "table_v")
 _DTYPES = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}
-# q's scale per row type: the model's 16 ** -0.5 for fp32 rows; for the half types values that are no powers of two, so that the
-# product q * scale is rounded (a `qk_scale` of the model's constructor)
-_SCALES = {"float32": 0.25, "float16": 0.3, "bfloat16": 0.19}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -33,82 +31,6 @@ def _gpu():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     from stratified_transformer_amd import pointops
     pointops.clear_caches()
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _cell_plans(xyz_np, offset, w, quant, seed, L, cap=0):
-    """even and odd block index (with their cell plans) of a cloud, on a seeded random downsample of n // 8 + b points"""
-    from stratified_transformer_amd import index_build
-    n, nbatch = xyz_np.shape[0], offset.shape[0]
-    rng = np.random.default_rng(seed)
-    ds = np.sort(rng.permutation(n)[: n // 8 + nbatch]).astype(np.int32)
-    even, odd, _ = index_build.stage_index_hip(dev(xyz_np), dev(offset), w, quant, dev(ds), cell_table_rows=L, cell_max_queries=cap)
-    return even, odd
-
-
-def _cell_scene(n, nbatch, w, quant, seed, L, cap=0):
-    from stratified_transformer_amd import scene
-    sizes = [n // nbatch + (1 if i < n % nbatch else 0) for i in range(nbatch)]
-    xyz_np, offset = scene.make_batch(sizes, seed=seed)
-    even, odd = _cell_plans(xyz_np, offset, w, quant, seed, L, cap)
-    return xyz_np, offset, even, odd
-
-
-def _cell_nk(plan):
-    return np.diff(_np(plan.cell_kbase)[: plan.n_cells + 1])
-
-
-def _oracle_attention(p, i1, offs, rel, go):
-    sm = ref.segment_softmax(ref.attention_step1_v2(p["q"], p["k"], i1, offs)
-                             + ref.dot_prod_with_idx_v3(p["q"], offs, p["k"], i1, p["table_q"], p["table_k"], rel), offs)
-    out = ref.attention_step2_with_rel_pos_value_v2(sm, p["v"], offs, i1, p["table_v"], rel)
-    if go is None:
-        return out, None
-    ga, gv, gtv = ref.attention_step2_with_rel_pos_value_v2_backward(go, sm, p["v"], offs, i1, p["table_v"], rel)
-    gs = ref.segment_softmax_backward(sm, ga, offs)
-    gq1, gk1 = ref.attention_step1_v2_backward(gs, p["q"], p["k"], i1, offs)
-    gq2, gk2, gtq, gtk = ref.dot_prod_with_idx_v3_backward(gs, p["q"], offs, p["k"], i1, p["table_q"], p["table_k"], rel)
-    return out, dict(q=gq1 + gq2, k=gk1 + gk2, v=gv, table_q=gtq, table_k=gtk, table_v=gtv)
-
-
-def _packed_operands(n, h, L, seed, dtype):
-    """qkv [n, 3, h, 16] of `dtype` on the device, the three fp32 tables, grad_out (numpy)"""
-    rng = np.random.default_rng(seed)
-    qkv = dev(rng.standard_normal((n, 3, h, 16), dtype=np.float32)).to(dtype).contiguous()
-    tabs = [dev(rng.standard_normal((L, h, 16, 3), dtype=np.float32) * np.float32(0.5)) for _ in _TABLES]
-    return qkv, tabs, rng.standard_normal((n, h, 16), dtype=np.float32)
-
-
-def _oracle_operands(qkv, scale, tabs):
-    """what the model hands its operators: (query * scale).float(), key.float(), value.float() (:181-183), the product taken by torch
-    in qkv's dtype"""
-    p = dict(q=_np((qkv[:, 0] * scale).float().contiguous()), k=_np(qkv[:, 1].float().contiguous()), v=_np(qkv[:, 2].float().contiguous()))
-    p.update({name: _np(t) for name, t in zip(_TABLES, tabs)})
-    return p
-
-
-def _qkv_launch(plan, qkv, scale, tabs, L, go=None):
-    """The packed forward (and with grad_out `go` its backward) through the C ABI: out, pbuf, and the fp32 gradient buffers as the
-    kernels wrote them (grad_qkv [n, 3, h, 16] and the three table gradients)."""
-    from stratified_transformer_amd import _lib
-    n, _, h, _ = qkv.shape
-    f32 = dict(dtype=torch.float32, device="cuda")
-    out, ml, pbuf = torch.empty(n, h, 16, **f32), torch.empty(n, h, 2, **f32), torch.zeros(h, max(plan.n_pairs, 1), **f32)
-    rt = _lib.ROW_TYPES[qkv.dtype]
-    tp = [_lib.ptr(t) for t in tabs]
-    _lib.call("cell_attention_qkv_forward_launcher", plan.c_arg(), h, 16, L, _lib.ptr(qkv), rt, float(scale), *tp, _lib.ptr(out), _lib.ptr(ml),
-              _lib.ptr(pbuf), device=out.device)
-    if go is None:
-        return out, pbuf, None
-    gsbuf = torch.empty_like(pbuf)
-    g_qkv = torch.zeros(n, 3, h, 16, **f32)
-    g_tabs = [torch.zeros(t.shape, **f32) for t in tabs]
-    _lib.call("cell_attention_qkv_backward_launcher", plan.c_arg(), h, 16, L, _lib.ptr(dev(go)), _lib.ptr(qkv), rt, float(scale), _lib.ptr(out), *tp,
-              _lib.ptr(pbuf), _lib.ptr(gsbuf), _lib.ptr(g_qkv), *[_lib.ptr(g) for g in g_tabs], device=out.device)
-    return out, pbuf, dict(qkv=g_qkv, table_q=g_tabs[0], table_k=g_tabs[1], table_v=g_tabs[2])
 
 
 def _unpacked_launch(plan, ops, L, go=None):
@@ -153,33 +75,6 @@ def _qkv_vs_oracle(blk, L, h, dtype, expect, seed, backward=True):
     if backward:
         _check_grads(_np(grads["qkv"]), {t: _np(grads[t]) for t in _TABLES}, wgrads, scale, f"{expect} {dtype}")
 
-
-# the scenes of tests/test_hip_parity.py::_CELL_VARIANT_SCENES: (points per batch element, w, quant, h, cap (None: the production cut),
-# fp32 variant of the (even, odd) pattern, least keys of the largest cell)
-_CELL_VARIANT_SCENES = {
-    "mfma64_h1": ([3000], 0.16, 0.01, 1, 16, ("mfma64", "mfma64"), 0),
-    "mfma80_h3": ([4000], 0.1, 0.005, 3, 32, ("mfma80", "mfma80"), 0),
-    "stage0_h12_production_cap": ([8000], 0.16, 0.01, 12, None, ("mfma64", "valu80"), 0),
-    "stage0_h3_cap8": ([32000], 0.16, 0.01, 3, 8, ("valu80", "valu80"), 0),
-    "two_chunks_L80_h8_cap8": ([6000, 6000], 0.3, 0.015, 8, 8, ("valu80", "valu80"), 129),
-    "three_chunks_h12_cap8": ([8000], 0.32, 0.02, 12, 8, ("valu80", "valu80"), 257),
-}
-
-
-def _variant_scene(case):
-    from stratified_transformer_amd import index_build, scene
-    sizes, w, quant, h, cap, variants, nk_least = _CELL_VARIANT_SCENES[case]
-    L = 2 * int((2 * w + 1e-4) // quant)
-    n = sum(sizes)
-    cap = index_build.cell_query_cap(n, h) if cap is None else cap
-    xyz_np, offset = scene.make_batch(sizes, seed=n + h)
-    blocks = _cell_plans(xyz_np, offset, w, quant, n + h, L, cap)
-    for blk in blocks:
-        if nk_least:
-            nk = _cell_nk(blk.cells)
-            assert blk.cells.nk_max >= nk_least, blk.cells.nk_max
-            assert ((nk > 128) & (nk % 16 != 0)).any(), blk.cells.nk_max
-    return blocks, variants, L, h
 
 
 @pytest.mark.parametrize("dtype", list(_DTYPES))

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import pointops_ref as ref
+from tests.cell_edges import _CELL_GRADS, _CELL_VARIANT_SCENES, _cell_launch, _cell_nk, _cell_operands, _cell_plans, _cell_scene, _oracle_attention
 from tests.util import dev, random_csr_problem, window_problem
 
 pytestmark = pytest.mark.gpu
@@ -1037,24 +1038,6 @@ def test_fused_window_attention_matches_the_operator_chain(P, case):
 
 
 # ---- window-centric ("cell") attention: csrc/index.hip cells + csrc/cell_attn.hip ----------------------
-def _cell_scene(n, nbatch, w, quant, seed, L, cap=0):
-    from stratified_transformer_amd import scene
-    sizes = [n // nbatch + (1 if i < n % nbatch else 0) for i in range(nbatch)]
-    xyz_np, offset = scene.make_batch(sizes, seed=seed)
-    even, odd = _cell_plans(xyz_np, offset, w, quant, seed, L, cap)
-    return xyz_np, offset, even, odd
-
-
-def _cell_plans(xyz_np, offset, w, quant, seed, L, cap=0):
-    """even and odd block index (with their cell plans) of a cloud, on a seeded random downsample of n // 8 + b points"""
-    from stratified_transformer_amd import index_build
-    n, nbatch = xyz_np.shape[0], offset.shape[0]
-    rng = np.random.default_rng(seed)
-    ds = np.sort(rng.permutation(n)[: n // 8 + nbatch]).astype(np.int32)
-    even, odd, _ = index_build.stage_index_hip(dev(xyz_np), dev(offset), w, quant, dev(ds), cell_table_rows=L, cell_max_queries=cap)
-    return even, odd
-
-
 def _expand_cells(plan):
     """the pair list a cell plan stands for, in (query, tile order): arrays (query, key, r0, r1, r2)"""
     nC = plan.n_cells
@@ -1101,17 +1084,6 @@ def test_cell_plan_is_the_pair_list(n, nbatch, w, quant, cap):
         for a, b in zip(pf[:-1], pf[1:]):
             for piece in range(a + 1, b):
                 assert np.array_equal(keys[kb[piece]: kb[piece + 1]], keys[kb[a]: kb[a + 1]])
-
-
-def _oracle_attention(p, i1, offs, rel, go):
-    sm = ref.segment_softmax(ref.attention_step1_v2(p["q"], p["k"], i1, offs)
-                             + ref.dot_prod_with_idx_v3(p["q"], offs, p["k"], i1, p["table_q"], p["table_k"], rel), offs)
-    out = ref.attention_step2_with_rel_pos_value_v2(sm, p["v"], offs, i1, p["table_v"], rel)
-    ga, gv, gtv = ref.attention_step2_with_rel_pos_value_v2_backward(go, sm, p["v"], offs, i1, p["table_v"], rel)
-    gs = ref.segment_softmax_backward(sm, ga, offs)
-    gq1, gk1 = ref.attention_step1_v2_backward(gs, p["q"], p["k"], i1, offs)
-    gq2, gk2, gtq, gtk = ref.dot_prod_with_idx_v3_backward(gs, p["q"], offs, p["k"], i1, p["table_q"], p["table_k"], rel)
-    return out, dict(q=gq1 + gq2, k=gk1 + gk2, v=gv, table_q=gtq, table_k=gtk, table_v=gtv)
 
 
 @pytest.mark.parametrize("case", ["s3dis_stage0_h3", "batch3_h6_L64", "scannet_L80_h3", "big_cells_two_chunks_h2", "coarse_h12"])
@@ -1179,36 +1151,6 @@ def test_cell_attention_rejects_tables_the_plan_was_not_built_for():
 
 
 # ---- each forward instance of the cell attention (pointops2_cell_forward_variant) against the oracle ---------------------
-_CELL_GRADS = ("q", "k", "v", "table_q", "table_k", "table_v")
-
-
-def _cell_operands(n, h, L, seed):
-    rng = np.random.default_rng(seed)
-    p = {x: rng.standard_normal((n, h, 16), dtype=np.float32) for x in ("q", "k", "v")}
-    for t in ("table_q", "table_k", "table_v"):
-        p[t] = rng.standard_normal((L, h, 16, 3), dtype=np.float32) * 0.5
-    return p, rng.standard_normal((n, h, 16), dtype=np.float32)
-
-
-def _cell_launch(plan, ops, L, go=None):
-    """The cell forward (and with grad_out `go` its backward) through the C ABI, fp32 or bf16 storage by the operands' dtype:
-    out, and the six gradients in fp32 as the kernels wrote them (fused.cell_attention casts a bf16 operand's to bf16)."""
-    from stratified_transformer_amd import _lib
-    n, h, _ = ops[0].shape
-    sfx = "_bf16" if ops[0].dtype == torch.bfloat16 else ""
-    f32 = dict(dtype=torch.float32, device="cuda")
-    out, ml, pbuf = torch.empty(n, h, 16, **f32), torch.empty(n, h, 2, **f32), torch.empty(h, max(plan.n_pairs, 1), **f32)
-    ptrs = [_lib.ptr(t) for t in ops]
-    _lib.call(f"cell_attention_forward{sfx}_launcher", plan.c_arg(), h, 16, L, *ptrs, _lib.ptr(out), _lib.ptr(ml), _lib.ptr(pbuf), device=out.device)
-    if go is None:
-        return out, None
-    gsbuf = torch.empty_like(pbuf)
-    grads = [torch.empty(n, h, 16, **f32)] + [torch.zeros(t.shape, **f32) for t in ops[1:]]  # grad_q fully written, the rest accumulated
-    _lib.call(f"cell_attention_backward{sfx}_launcher", plan.c_arg(), h, 16, L, _lib.ptr(dev(go)), *ptrs[:3], _lib.ptr(out), *ptrs[3:], _lib.ptr(pbuf),
-              _lib.ptr(gsbuf), *[_lib.ptr(g) for g in grads], device=out.device)
-    return out, dict(zip(_CELL_GRADS, grads))
-
-
 def _cell_variant_vs_oracle(blk, L, h, bf16, expect, seed, backward=True):
     """Asserts that the forward launcher picks `expect` for this pattern, then runs it (and the backward) on random operands and
     compares with the oracle's operator chain on the pattern's CSR pair list.  bf16: the oracle runs on the bf16-rounded operands
@@ -1234,26 +1176,6 @@ def _cell_variant_vs_oracle(blk, L, h, bf16, expect, seed, backward=True):
         tol = TTOL if name.startswith("table") else dict(rtol=2e-5, atol=2e-4)
         scale = max(1.0, float(np.abs(wgrads[name]).max())) if name.startswith("table") else 1.0
         np.testing.assert_allclose(_np(grads[name]) / scale, wgrads[name] / scale, err_msg=f"{expect} grad {name}", **tol)
-
-
-def _cell_nk(plan):
-    return np.diff(_np(plan.cell_kbase)[: plan.n_cells + 1])
-
-
-# name: (points per batch element, w, quant, h, cap (None: index_build.cell_query_cap, as the production pass), fp32 variant of the
-# (even, odd) pattern, least keys of the largest cell).  L = 2 * int(2w / quant): 64, or 80 at w / quant = 20.
-_CELL_VARIANT_SCENES = {
-    "mfma64_h1": ([3000], 0.16, 0.01, 1, 16, ("mfma64", "mfma64"), 0),
-    "mfma80_h3": ([4000], 0.1, 0.005, 3, 32, ("mfma80", "mfma80"), 0),
-    # S3DIS stage 0 at n * h = 96000 with the production cut: the shifted pattern's small cells take the VALU forward
-    "stage0_h12_production_cap": ([8000], 0.16, 0.01, 12, None, ("mfma64", "valu80"), 0),
-    "stage0_h3_cap8": ([32000], 0.16, 0.01, 3, 8, ("valu80", "valu80"), 0),
-    # big cells cut into pieces of 8 queries (each with the whole key list): n * h >= 96000 at an average below 15 queries, cells of
-    # more than 128 keys (two or more register chunks: running max / sum in `ml`, logits parked in pbuf) ...
-    "two_chunks_L80_h8_cap8": ([6000, 6000], 0.3, 0.015, 8, 8, ("valu80", "valu80"), 129),
-    # ... and of more than 256 (three or more)
-    "three_chunks_h12_cap8": ([8000], 0.32, 0.02, 12, 8, ("valu80", "valu80"), 257),
-}
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
