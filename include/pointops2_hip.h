@@ -39,7 +39,8 @@ void *pointops2_get_stream(void);
 /* NULL when the last call on this thread succeeded; otherwise a static message.  Reading clears. */
 const char *pointops2_last_error(void);
 /* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
- * cell_attention_qkv_*_launcher pair) */
+ * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
+ * version 5 - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -400,6 +401,21 @@ void cell_attention_qkv_backward_launcher(const pointops2_cell_plan *plan, int h
                                           float scale, const float *out, const float *table_q, const float *table_k, const float *table_v,
                                           const float *pbuf, float *gsbuf, float *grad_qkv, float *grad_table_q, float *grad_table_k,
                                           float *grad_table_v);
+
+/* ---- KPConv stem (model/stratified_transformer.py:344-392: KPConvLayer of torch_points3d 1.3.0, rigid kernel points, linear
+ * influence, sum aggregation; third party, not under the reference: PARITY UNPINNED) ----
+ * With j = neighbors[i, n] (a j outside [0, n_s) - the -1 padding of a ball query, or n_s, the original's shadow point - is skipped):
+ *   w[i,k,n]  = max(0, 1 - |(support_xyz[j] - query_xyz[i]) - k_points[k]| / extent)
+ *   forward:  wf[i,k,:]      = sum_n w[i,k,n] * feat[j,:]              wf [n_q, n_kp, c] fully written, no atomics (bitwise reproducible)
+ *   backward: grad_feat[j,:] += sum_k w[i,k,n] * grad_wf[i,k,:]        grad_feat [n_s, c] ACCUMULATES (zero-fill it); w is recomputed
+ * query_xyz [n_q,3], support_xyz [n_s,3], neighbors [n_q,n_nb] int32, feat [n_s,c], k_points [n_kp,3].  The layer's output is
+ * wf [n_q, n_kp*c] @ weight [n_kp*c, out]: a matrix product the caller does.  1 <= c <= 64, 1 <= n_nb <= 64, 1 <= n_kp <= 32 and
+ * extent > 0, otherwise an error is recorded and nothing is launched. */
+void kpconv_aggregate_forward_launcher(int n_q, int n_s, int n_nb, int c, int n_kp, const float *query_xyz, const float *support_xyz,
+                                       const int *neighbors, const float *feat, const float *k_points, float extent, float *wf);
+void kpconv_aggregate_backward_launcher(int n_q, int n_s, int n_nb, int c, int n_kp, const float *query_xyz, const float *support_xyz,
+                                        const int *neighbors, const float *k_points, float extent, const float *grad_wf,
+                                        float *grad_feat);
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,8 @@ SIGNATURES = {
     "cell_attention_backward_bf16_launcher": [P, I, I, I] + [P] * 16,
     "cell_attention_qkv_forward_launcher": [P, I, I, I, P, I, F] + [P] * 6,
     "cell_attention_qkv_backward_launcher": [P, I, I, I, P, P, I, F] + [P] * 10,
+    "kpconv_aggregate_forward_launcher": [I, I, I, I, I, P, P, P, P, P, F, P],
+    "kpconv_aggregate_backward_launcher": [I, I, I, I, I, P, P, P, P, F, P, P],
 }
 # entry points with a non-void result
 RESULTS = {

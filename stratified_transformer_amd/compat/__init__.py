@@ -9,8 +9,13 @@ the hot path, so the build supplies them:
   torch_geometric.nn.voxel_grid   -> the torch_cluster grid_cluster arithmetic, evaluated with torch
                                      ops on the tensor's device
   timm.models.layers              -> DropPath, trunc_normal_
-  torch_points3d ... KPConvLayer / FastBatchNorm1d -> import-only placeholders: the KPConv stem is
-                                     outside the hot path; using them raises.
+  torch_points3d ... KPConvLayer  -> the stem's kernel-point convolution on the HIP aggregation kernels
+                                     (stratified_transformer_amd/csrc/kpconv.hip through pointops.kpconv): rigid kernel
+                                     points, linear influence, sum aggregation - the options the model uses; any other
+                                     raises NotImplementedError in the constructor.  Third party, not under the
+                                     reference: PARITY UNPINNED (restated from torch_points3d 1.3.0).  The kernel points
+                                     are a fixed documented disposition, not the original's cached random optimisation.
+  torch_points3d ... FastBatchNorm1d -> nn.BatchNorm1d behind the original's 2-D / 3-D input handling (plain torch)
 
 `install()` only fills names that are NOT importable, so a real installation always wins.
 """
@@ -133,20 +138,76 @@ def trunc_normal_(tensor, mean=0., std=1., a=-2., b=2.):
     return torch.nn.init.trunc_normal_(tensor, mean=mean, std=std, a=a, b=b)
 
 
-class _OffPath(torch.nn.Module):
-    def __init__(self, *a, **k):
+def kpconv_kernel_points(point_influence):
+    """The shim's kernel-point disposition, [15, 3] fp32: the origin, the six axis points (+x, -x, +y, -y, +z, -z) and the eight cube
+    corners (+-1, +-1, +-1) / sqrt(3), the fourteen at distance `point_influence` (= kernel_radius / 1.5) from the origin.  Computed in
+    float64 and rounded once, so two constructions agree bit for bit.  (torch_points3d optimises a random repulsion problem, caches the
+    result on disk and rotates it randomly: not reproducible across installations; a trained checkpoint carries its own K_points.)"""
+    pts = [[0.0, 0.0, 0.0]]
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            pts.append([sign if a == axis else 0.0 for a in range(3)])
+    r = 3.0 ** -0.5
+    for sx in (1.0, -1.0):
+        for sy in (1.0, -1.0):
+            for sz in (1.0, -1.0):
+                pts.append([sx * r, sy * r, sz * r])
+    return (torch.tensor(pts, dtype=torch.float64) * float(point_influence)).to(torch.float32)
+
+
+class KPConvLayer(torch.nn.Module):
+    """torch_points3d.modules.KPConv.kernels.KPConvLayer (1.3.0) for the options the model uses (model/stratified_transformer.py:347,
+    369: `KPConvLayer(in, out, point_influence=prev_grid_size * sigma, add_one=False)`); same constructor signature, attributes,
+    state-dict keys (`K_points`, `weight`) and forward signature.  Third party, not under the reference: PARITY UNPINNED.
+
+    forward(query_points [n_q,3], support_points [n_s,3], neighbors [n_q,n_nb] int, x [n_s,c]) -> [n_q, num_outputs] fp32:
+        w[i,k,n] = max(0, 1 - |(support[j] - query[i]) - K_points[k]| / point_influence),  j = neighbors[i,n]
+        out[i]   = sum_k (sum_n w[i,k,n] * x[j]) @ weight[k]
+    A j outside [0, n_s) (-1, or n_s: the original's shadow point at 1e6 with a zero feature row) contributes nothing.  Runs on
+    pointops.kpconv (HIP, GPU tensors only); gradients flow to x and weight.  K_points: see kpconv_kernel_points."""
+    _INFLUENCE_TO_RADIUS = 1.5
+
+    def __init__(self, num_inputs, num_outputs, point_influence, n_kernel_points=15, fixed="center", KP_influence="linear",
+                 aggregation_mode="sum", dimension=3, add_one=False, **kwargs):
         super().__init__()
+        for option, value, supported in (("n_kernel_points", n_kernel_points, 15), ("fixed", fixed, "center"), ("KP_influence", KP_influence, "linear"),
+                                         ("aggregation_mode", aggregation_mode, "sum"), ("dimension", dimension, 3)):
+            if value != supported:
+                raise NotImplementedError(f"KPConvLayer: {option}={value!r} is not supported by this build (only {option}={supported!r})")
+        self.kernel_radius = self._INFLUENCE_TO_RADIUS * point_influence
+        self.point_influence = point_influence
+        self.add_one = add_one
+        self.num_inputs = num_inputs + self.add_one * 1
+        self.num_outputs = num_outputs
+        self.KP_influence = KP_influence
+        self.n_kernel_points = n_kernel_points
+        self.aggregation_mode = aggregation_mode
+        self.K_points = torch.nn.Parameter(kpconv_kernel_points(point_influence), requires_grad=False)
+        weight = torch.empty([n_kernel_points, self.num_inputs, num_outputs], dtype=torch.float)
+        torch.nn.init.xavier_normal_(weight)
+        self.weight = torch.nn.Parameter(weight)
 
-    def forward(self, *a, **k):
-        raise NotImplementedError(f"{type(self).__name__}: KPConv stem is outside the hot path (SURVEY.md §8); install torch_points3d to use it")
+    def forward(self, query_points, support_points, neighbors, x):
+        from ..pointops import kpconv
+        if self.add_one:
+            x = torch.cat([x, torch.ones_like(x[:, :1])], dim=1)
+        return kpconv(query_points, support_points, neighbors, x, self.K_points, self.weight, self.point_influence)
 
 
-class KPConvLayer(_OffPath):
-    pass
+class FastBatchNorm1d(torch.nn.Module):
+    """torch_points3d.core.common_modules.FastBatchNorm1d (1.3.0): nn.BatchNorm1d over the last dimension of a [N, C] or [B, N, C]
+    input.  Plain torch."""
 
+    def __init__(self, num_features, momentum=0.1, **kwargs):
+        super().__init__()
+        self.batch_norm = torch.nn.BatchNorm1d(num_features, momentum=momentum, **kwargs)
 
-class FastBatchNorm1d(_OffPath):
-    pass
+    def forward(self, x):
+        if x.dim() == 2:
+            return self.batch_norm(x)
+        if x.dim() == 3:
+            return self.batch_norm(x.transpose(1, 2)).transpose(1, 2)
+        raise ValueError("Non supported number of dimensions {}".format(x.dim()))
 
 
 def _importable(name):

@@ -860,6 +860,81 @@ class Interpolation(Function):
 interpolation2 = Interpolation.apply
 
 
+# ---------------------------------------------------------------------------------------------
+# KPConv stem (model/stratified_transformer.py:344-392; torch_points3d 1.3.0 KPConvLayer - third party: PARITY UNPINNED)
+# ---------------------------------------------------------------------------------------------
+class KPConv(Function):
+    """out = sum_k (sum_n w[i,k,n] * feat[neighbors[i,n], :]) @ weight[k] with the linear influence
+    w = max(0, 1 - |(support[j] - query[i]) - k_points[k]| / extent); neighbours outside [0, n_s) are skipped.  The aggregation
+    over the neighbours and its transpose are HIP kernels (csrc/kpconv.hip); the products with `weight` are matrix products.
+    Gradients: feat and weight only."""
+
+    @staticmethod
+    def forward(ctx, query_xyz, support_xyz, neighbors, feat, k_points, weight, extent):
+        n_q, n_nb = neighbors.shape
+        n_s, c = feat.shape
+        n_kp, out = weight.shape[0], weight.shape[2]
+        with torch.autocast("cuda", enabled=False):  # fp32 throughout, whatever the caller's autocast state
+            wf = torch.empty((n_q, n_kp * c), dtype=torch.float32, device=feat.device)
+            if n_q > 0:
+                pointops_cuda.kpconv_aggregate_forward(n_q, n_s, n_nb, c, n_kp, query_xyz, support_xyz, neighbors, feat, k_points, extent, wf)
+            result = wf @ weight.reshape(n_kp * c, out)
+        ctx.extent, ctx.n_s = extent, n_s
+        ctx.save_for_backward(query_xyz, support_xyz, neighbors, k_points, weight, wf if ctx.needs_input_grad[5] else None)
+        return result
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[4]:
+            raise RuntimeError("kpconv: gradients of query_xyz, support_xyz and k_points are not implemented (only feat and weight are "
+                               "differentiable); detach the coordinates / kernel points")
+        query_xyz, support_xyz, neighbors, k_points, weight, wf = ctx.saved_tensors
+        (n_q, n_nb), (n_kp, c, out) = neighbors.shape, weight.shape
+        grad_feat = grad_weight = None
+        with torch.autocast("cuda", enabled=False):
+            grad_output = grad_output.float().contiguous()
+            if ctx.needs_input_grad[5]:
+                grad_weight = (wf.t() @ grad_output).reshape(n_kp, c, out)
+            if ctx.needs_input_grad[3]:  # never for the model's first block: its input is data
+                grad_feat = _zeros((ctx.n_s, c), grad_output)
+                if n_q > 0 and ctx.n_s > 0:
+                    grad_wf = grad_output @ weight.reshape(n_kp * c, out).t()
+                    pointops_cuda.kpconv_aggregate_backward(n_q, ctx.n_s, n_nb, c, n_kp, query_xyz, support_xyz, neighbors, k_points,
+                                                            ctx.extent, grad_wf, grad_feat)
+        return None, None, None, grad_feat, None, grad_weight, None
+
+
+def kpconv(query_xyz, support_xyz, neighbors, feat, k_points, weight, extent):
+    """KPConv (rigid, linear influence, sum aggregation) of feat [n_s, c] at query_xyz [n_q, 3] -> [n_q, out] fp32.
+    support_xyz [n_s, 3]; neighbors [n_q, n_nb] int32 / int64 (entries outside [0, n_s) - the -1 padding of `ball_query`, or n_s,
+    the shadow point of torch_points3d - are skipped); k_points [n_kp, 3]; weight [n_kp, c, out]; extent = the influence radius
+    of a kernel point (KPConvLayer.point_influence).  feat may be f16 / bf16 (autocast): its rows are widened, the arithmetic and the
+    result are fp32 and autograd casts the gradient back (as `_gather_operands` does for interpolation).  Differentiable w.r.t.
+    feat and weight only.  1 <= c <= 64, 1 <= n_nb <= 64, n_kp <= 32.  Third-party semantics (torch_points3d 1.3.0): PARITY UNPINNED."""
+    named = (("query_xyz", query_xyz), ("support_xyz", support_xyz), ("neighbors", neighbors), ("feat", feat), ("k_points", k_points), ("weight", weight))
+    for name, t in named:
+        if not t.is_cuda:
+            raise RuntimeError(f"kpconv: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+        if t.device != feat.device:
+            raise RuntimeError(f"kpconv: {name} is on {t.device}, feat on {feat.device}")
+    for name, t in named[:2] + named[4:5]:
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"kpconv: {name} must be [n, 3], got {tuple(t.shape)}")
+    if neighbors.dtype not in (torch.int32, torch.int64) or neighbors.dim() != 2 or neighbors.shape[0] != query_xyz.shape[0]:
+        raise ValueError(f"kpconv: neighbors must be an int32 / int64 [{query_xyz.shape[0]}, n_nb], got {neighbors.dtype} {tuple(neighbors.shape)}")
+    if feat.dim() != 2 or feat.shape[0] != support_xyz.shape[0]:
+        raise ValueError(f"kpconv: feat must be [{support_xyz.shape[0]}, c], got {tuple(feat.shape)}")
+    if feat.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"kpconv: feat must be f32, f16 or bf16, got {feat.dtype}")
+    if weight.dim() != 3 or weight.shape[0] != k_points.shape[0] or weight.shape[1] != feat.shape[1]:
+        raise ValueError(f"kpconv: weight must be [{k_points.shape[0]}, {feat.shape[1]}, out], got {tuple(weight.shape)}")
+    n_s = feat.shape[0]
+    if neighbors.dtype == torch.int64:
+        neighbors = neighbors.clamp(-1, n_s).to(torch.int32)
+    return KPConv.apply(query_xyz.float().contiguous(), support_xyz.float().contiguous(), neighbors.contiguous(), feat.float().contiguous(),
+                        k_points.float().contiguous(), weight.float(), float(extent))
+
+
 class Subtraction(Function):
     @staticmethod
     def forward(ctx, input1, input2, idx):

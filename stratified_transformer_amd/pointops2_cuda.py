@@ -70,6 +70,21 @@ def interpolation_backward_cuda(n, c, k, grad_output, idx, weight, grad_input, *
     _call("interpolation_backward_cuda_launcher", grad_output, int(n), int(c), int(k), ptr(grad_output), ptr(idx), ptr(weight), ptr(grad_input), opts=opts)
 
 
+# csrc/kpconv.hip (no counterpart in the reference's launcher set: the KPConv stem of torch_points3d)
+def kpconv_aggregate_forward(n_q, n_s, n_nb, c, n_kp, query_xyz, support_xyz, neighbors, feat, k_points, extent, wf, *, opts=None):
+    _chk((query_xyz, F32, "query_xyz"), (support_xyz, F32, "support_xyz"), (neighbors, I32, "neighbors"), (feat, F32, "feat"),
+         (k_points, F32, "k_points"), (wf, F32, "wf"))
+    _call("kpconv_aggregate_forward_launcher", query_xyz, int(n_q), int(n_s), int(n_nb), int(c), int(n_kp), ptr(query_xyz), ptr(support_xyz),
+          ptr(neighbors), ptr(feat), ptr(k_points), float(extent), ptr(wf), opts=opts)
+
+
+def kpconv_aggregate_backward(n_q, n_s, n_nb, c, n_kp, query_xyz, support_xyz, neighbors, k_points, extent, grad_wf, grad_feat, *, opts=None):
+    _chk((query_xyz, F32, "query_xyz"), (support_xyz, F32, "support_xyz"), (neighbors, I32, "neighbors"), (k_points, F32, "k_points"),
+         (grad_wf, F32, "grad_wf"), (grad_feat, F32, "grad_feat"))
+    _call("kpconv_aggregate_backward_launcher", query_xyz, int(n_q), int(n_s), int(n_nb), int(c), int(n_kp), ptr(query_xyz), ptr(support_xyz),
+          ptr(neighbors), ptr(k_points), float(extent), ptr(grad_wf), ptr(grad_feat), opts=opts)
+
+
 # attention/attention_cuda.cpp
 def attention_step1_forward_cuda(N, M, h, C, q, k, index0, index1, attn, *, opts=None):
     _chk((q, F32, "q"), (k, F32, "k"), (index0, I32, "index0"), (index1, I32, "index1"), (attn, F32, "attn"))
