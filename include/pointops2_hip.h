@@ -40,7 +40,7 @@ void *pointops2_get_stream(void);
 const char *pointops2_last_error(void);
 /* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
- * version 5 - a caller that needs them looks the symbols up. */
+ * version 5, the grouped_max_*_launcher pair after them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -416,6 +416,27 @@ void kpconv_aggregate_forward_launcher(int n_q, int n_s, int n_nb, int c, int n_
 void kpconv_aggregate_backward_launcher(int n_q, int n_s, int n_nb, int c, int n_kp, const float *query_xyz, const float *support_xyz,
                                         const int *neighbors, const float *k_points, float extent, const float *grad_wf,
                                         float *grad_feat);
+
+/* ---- grouped max pooling: the tail of TransitionDown (model/stratified_transformer.py:106-109).  LayerNorm and the bias-free Linear
+ * act on one row at a time, so pooling linear(norm(feats[knn])) over the k gathered copies is pooling y = linear(norm(feats)) ----
+ *   forward:  out[i,ch] = max_n feat[idx[i,n], ch]; arg[i,ch] = the smallest n that attains it (nn.MaxPool1d's rule: first maximum,
+ *             a NaN among the k values gives NaN, arg then the n of the first NaN).  An idx entry outside [0, n_s) is skipped and never
+ *             read; a row with no valid entry gives 0 and arg = 255, which carries no gradient.  The maximum is a selection: exact in
+ *             every row type.  out [m,c] (row_type) and arg [m,c] are fully written; arg may be NULL (no backward wanted).
+ *   backward: grad_feat[j,ch] = sum over the pairs (i,n) with idx[i,n] == j and arg[i,ch] == n of grad_out[i,ch], gathered by source
+ *             row through the key-major view of idx: src_offsets [n_s+1] / src_pair [m*k] are what pointops2_csc_build yields for the
+ *             CSR offsets = {0, k, 2k, ...}, index1 = idx with launch_opts.key_rows = n_s (pair id = i * k + n, ascending per source
+ *             row; idx entries outside [0, n_s) must be kept out of that build - key them to an extra row n_s).  fp32 accumulation in
+ *             pair order, one rounding to the row type; grad_feat [n_s,c] (row_type) is FULLY WRITTEN: no float atomics, no zero-fill,
+ *             bitwise reproducible.  Offsets and pair ids are clamped / skipped, never followed outside the arrays.
+ * feat [n_s,c], grad_out [m,c]: row_type = POINTOPS2_ROWS_F32, _F16 or _BF16 (the Linear in front yields half under autocast); idx
+ * [m,k] int32.  1 <= k <= 64, 1 <= c <= 1024 and m * k < 2^31, otherwise an error is recorded and nothing is launched; m = 0 or
+ * n_s = 0 is a no-op.  Rows of whole 16-byte chunks (c % 4 == 0 for fp32, c % 8 == 0 for the halves) of 16-byte aligned operands take
+ * the chunked kernels, anything else one thread per element: same results. */
+void grouped_max_forward_launcher(int m, int n_s, int k, int c, int row_type, const void *feat, const int *idx, void *out,
+                                  unsigned char *arg);
+void grouped_max_backward_launcher(int m, int n_s, int k, int c, int row_type, const void *grad_out, const unsigned char *arg,
+                                   const int *src_offsets, const int *src_pair, void *grad_feat);
 
 #ifdef __cplusplus
 }

@@ -22,19 +22,24 @@ def build(verbose=False):
     return _lib.build(verbose=verbose)
 
 
-def install(third_party=True, fast_layers=False):
+def install(third_party=True, fast_layers=False, pooled_transition=False):
     """Make `import pointops2_cuda`, `from lib.pointops2.functions import pointops` and (optionally) the
     model's third-party imports resolve to this package.
 
     fast_layers=True: additionally rebind `BasicLayer.forward` / `WindowAttention.forward` of the (unmodified, importable)
     `model.stratified_transformer` to the forms of `stratified_transformer_amd.layers`: the stage's index is built once on
     the device and every attention block runs as one fused function on its cell plan - the path bench.py's headline
-    (`single_pass.cell`) measures.  Without it the model runs on the operator API alone (`single_pass.operator_api`)."""
+    (`single_pass.cell`) measures.  Without it the model runs on the operator API alone (`single_pass.operator_api`).
+
+    pooled_transition: sets `layers.POOLED_TRANSITION`.  True: the installed `TransitionDown.forward` runs its LayerNorm and Linear
+    once per source row and pools with `pointops.grouped_max` (csrc/grouped_max.hip) instead of pushing the k gathered copies of
+    every sampled row through them; the same maxima up to fp32 rounding.  The default keeps the reference's order of operations."""
     from . import pointops2_cuda
     sys.modules.setdefault("pointops2_cuda", pointops2_cuda)
     if third_party:
         from . import compat
         compat.install()
+    from . import layers
+    layers.POOLED_TRANSITION = bool(pooled_transition)
     if fast_layers:
-        from . import layers
         return layers.install_fast_layers()

@@ -94,6 +94,8 @@ SIGNATURES = {
     "cell_attention_qkv_backward_launcher": [P, I, I, I, P, P, I, F] + [P] * 10,
     "kpconv_aggregate_forward_launcher": [I, I, I, I, I, P, P, P, P, P, F, P],
     "kpconv_aggregate_backward_launcher": [I, I, I, I, I, P, P, P, P, F, P, P],
+    "grouped_max_forward_launcher": [I, I, I, I, I, P, P, P, P],
+    "grouped_max_backward_launcher": [I, I, I, I, I, P, P, P, P, P],
 }
 # entry points with a non-void result
 RESULTS = {
@@ -112,7 +114,7 @@ RESULTS = {
 
 # codes of pointops2_cell_forward_variant (POINTOPS2_CELL_FWD_* of include/pointops2_hip.h): the forward kernel a cell launch runs
 CELL_FWD = {"error": -1, "none": 0, "mfma64": 1, "mfma80": 2, "valu80": 3, "valu160": 4}
-# storage type of the rows of a packed qkv (POINTOPS2_ROWS_*): cell_attention_qkv_*_launcher
+# storage type of the rows of a packed qkv (POINTOPS2_ROWS_*): cell_attention_qkv_*_launcher, grouped_max_*_launcher
 ROW_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 

@@ -50,6 +50,9 @@ _ORIGINAL = {}
 # under the unmodified model's own call order.  P2_LAYER_CHAIN=0: everything on the caller's stream, in the model's order.
 CHAIN = os.environ.get("P2_LAYER_CHAIN", "1") != "0"
 SPECULATE = os.environ.get("P2_SPECULATE", "1") != "0"
+# TransitionDown's tail (:106-109) as norm / linear on the N source rows + pointops.grouped_max, instead of on the k gathered copies of
+# every sampled row (install(pooled_transition=True)).  Same maxima up to the fp32 rounding of the Linear's sums taken in another order.
+POOLED_TRANSITION = False
 STATS = {"layers": 0, "speculated": 0, "reruns": 0, "transitions_prefetched": 0}
 _CLOUDS = {}  # id(xyz) -> _Cloud
 _FLAG_HOST = {}  # device index -> ring of pinned bool [1] words (speculation checks)
@@ -320,13 +323,37 @@ def basic_layer_forward(self, feats, xyz, offset):
     return body(sampled)
 
 
+def _pooled_transition_forward(self, feats, xyz, offset, t):
+    """TransitionDown.forward with POOLED_TRANSITION: norm and linear on the N source rows, then the grouped maximum (csrc/grouped_max.hip).
+    t: the prefetched geometry, or None - then it is computed here as the original does (:100-104)."""
+    if t is not None:
+        main = torch.cuda.current_stream(xyz.device)
+        main.wait_event(t["ready"])
+        for x in (t["n_xyz"], t["knn"], t["n_offset"]):
+            x.record_stream(main)
+        n_xyz, knn, n_offset = t["n_xyz"], t["knn"], t["n_offset"]
+    else:
+        n_offset = _offsets(index_build.transition_down_offset(offset.tolist(), self.ratio), xyz.device)                           # :100-102
+        idx = P.furthestsampling(xyz, offset, n_offset)                                                                             # :103
+        n_xyz = xyz[idx.long(), :]                                                                                                  # :104
+        knn, _ = P.knnquery(int(self.k), xyz, n_xyz, offset, n_offset)
+    y = self.linear(self.norm(feats) if self.norm is not None else feats)                                                          # :106-107
+    pooled = P.grouped_max(y.contiguous(), knn)                                                                                     # :108-109
+    return pooled, n_xyz, n_offset
+
+
 def transition_down_forward(self, feats, xyz, offset):
     """Replacement of TransitionDown.forward (:98-111), same arguments, same three results: sampling, the next cloud and the grouping
     query are taken from what the installed BasicLayer.forward put on the side streams (else the original forward runs); grouping,
-    norm, linear and max-pool are the module's own."""
+    norm, linear and max-pool are the module's own.  With POOLED_TRANSITION norm and linear run once per source row and the pool is
+    pointops.grouped_max; geometry that was not prefetched is then computed here (the original forward is not called)."""
     cloud = _cloud_of(xyz)
     t = cloud.trans if cloud is not None else None
-    if t is None or (t["ratio"], t["k"]) != (self.ratio, self.k) or not feats.is_cuda:
+    if t is not None and (t["ratio"], t["k"]) != (self.ratio, self.k):
+        t = None
+    if POOLED_TRANSITION and feats.is_cuda:
+        return _pooled_transition_forward(self, feats, xyz, offset, t)
+    if t is None or not feats.is_cuda:
         return _original(self)(self, feats, xyz, offset)
     main = torch.cuda.current_stream(xyz.device)
     main.wait_event(t["ready"])

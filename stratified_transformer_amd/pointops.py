@@ -59,6 +59,26 @@ class _CSC:
         self.offsets, self.pair, self.query, self.keep = offsets, pair, query, keep
 
 
+def _csc_build(index0_offsets, index1, n_keys):
+    """pointops2_csc_build on the current stream, uncached: (offsets [n_keys + 1], pair [M], query [M]); every index1 entry must
+    lie in [0, n_keys) - the build follows them"""
+    M = int(index1.shape[0])
+    N = int(index0_offsets.shape[0]) - 1
+    dev = index1.device
+    offsets = torch.empty(n_keys + 1, dtype=torch.int32, device=dev)
+    pair = torch.empty(M, dtype=torch.int32, device=dev)
+    query = torch.empty(M, dtype=torch.int32, device=dev)
+    if M > 0:
+        nbytes = int(_lib.lib().pointops2_csc_workspace_bytes(max(N, n_keys), M))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("pointops2_csc_build", N, M, ptr(index0_offsets), ptr(index1), ptr(offsets), ptr(pair), ptr(query),
+                      ptr(ws), nbytes, device=dev, opts=_lib.LaunchOpts(key_rows=int(n_keys)))
+    else:
+        offsets.zero_()
+    return offsets, pair, query
+
+
 _CSC_CACHE = OrderedDict()
 _CSC_CACHE_SIZE = 8
 CSC_BUILDS = 0  # transpositions built so far (tests: one per block on the drop-in path)
@@ -92,21 +112,7 @@ def csc_of(index0_offsets, index1, n_keys, alias=None):
         if akey is not None:
             _CSC_CACHE[akey] = hit
         return hit
-    M = int(index1.shape[0])
-    N = int(index0_offsets.shape[0]) - 1
-    dev = index1.device
-    l = _lib.lib()
-    offsets = torch.empty(n_keys + 1, dtype=torch.int32, device=dev)
-    pair = torch.empty(M, dtype=torch.int32, device=dev)
-    query = torch.empty(M, dtype=torch.int32, device=dev)
-    if M > 0:
-        nbytes = int(l.pointops2_csc_workspace_bytes(max(N, n_keys), M))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("pointops2_csc_build", N, M, ptr(index0_offsets), ptr(index1), ptr(offsets), ptr(pair), ptr(query),
-                      ptr(ws), nbytes, device=dev, opts=_lib.LaunchOpts(key_rows=int(n_keys)))
-    else:
-        offsets.zero_()
+    offsets, pair, query = _csc_build(index0_offsets, index1, n_keys)
     csc = _CSC(offsets, pair, query, (index0_offsets, index1, alias))
     csc.n_keys = int(n_keys)
     _CSC_CACHE[key] = csc
@@ -933,6 +939,76 @@ def kpconv(query_xyz, support_xyz, neighbors, feat, k_points, weight, extent):
         neighbors = neighbors.clamp(-1, n_s).to(torch.int32)
     return KPConv.apply(query_xyz.float().contiguous(), support_xyz.float().contiguous(), neighbors.contiguous(), feat.float().contiguous(),
                         k_points.float().contiguous(), weight.float(), float(extent))
+
+
+# ---------------------------------------------------------------------------------------------
+# grouped max pooling: the tail of TransitionDown (model/stratified_transformer.py:106-109) taken per source row
+# ---------------------------------------------------------------------------------------------
+GROUPED_MAX_ARGS = 0  # `arg` tensors allocated so far (tests: none without a gradient)
+
+
+class GroupedMax(Function):
+    """out[i, :] = max_n feat[idx[i, n], :] with nn.MaxPool1d's rules (first maximum, NaN wins); csrc/grouped_max.hip.  The backward
+    gathers by source row through the key-major view of idx: no atomics, bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, feat, idx, need):
+        (m, k), (n_s, c) = idx.shape, feat.shape
+        out = _zeros((m, c), feat, feat.dtype) if n_s == 0 else torch.empty((m, c), dtype=feat.dtype, device=feat.device)
+        arg = None
+        if need:
+            global GROUPED_MAX_ARGS
+            GROUPED_MAX_ARGS += 1
+            arg = torch.empty((m, c), dtype=torch.uint8, device=feat.device)
+        if m > 0 and n_s > 0:
+            pointops_cuda.grouped_max_forward(m, n_s, k, c, feat, idx, out, arg)
+        ctx.n_s = n_s
+        if need:
+            ctx.save_for_backward(idx, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, arg = ctx.saved_tensors
+        (m, k), c, n_s = idx.shape, grad_out.shape[1], ctx.n_s
+        if m == 0 or n_s == 0:
+            return _zeros((n_s, c), grad_out, grad_out.dtype), None, None
+        # key-major view of idx: pointops2_csc_build follows every key, so the entries the forward skipped are keyed to an extra
+        # row n_s, behind the n_s + 1 offsets the kernel reads
+        keys = torch.where((idx >= 0) & (idx < n_s), idx, torch.full_like(idx, n_s)).view(-1)
+        rows = torch.arange(0, m * k + 1, k, dtype=torch.int32, device=idx.device)
+        src_offsets, src_pair, _ = _csc_build(rows, keys, n_s + 1)
+        grad_feat = torch.empty((n_s, c), dtype=grad_out.dtype, device=grad_out.device)
+        pointops_cuda.grouped_max_backward(m, n_s, k, c, grad_out.contiguous(), arg, src_offsets[:n_s + 1], src_pair, grad_feat)
+        return grad_feat, None, None
+
+
+def grouped_max(feat, idx):
+    """Max pooling over groups of rows: out[i, :] = max over n of feat[idx[i, n], :] -> [m, c] of feat's dtype.  feat [n_s, c] f32, f16 or
+    bf16 (what a Linear yields under autocast); idx [m, k] int32 / int64.  nn.MaxPool1d's rules: the first maximum wins a tie, a NaN
+    in a group gives NaN.  Entries of idx outside [0, n_s) are skipped; a row without a valid entry gives 0 and no gradient.
+    With y = linear(norm(feats)) this is TransitionDown's `pool(linear(norm(feats[knn])))` (model/stratified_transformer.py:106-109)
+    without the k gathered copies.  Differentiable w.r.t. feat; the index of the maximum is kept only when feat requires a
+    gradient.  1 <= k <= 64, 1 <= c <= 1024."""
+    for name, t in (("feat", feat), ("idx", idx)):
+        if not t.is_cuda:
+            raise RuntimeError(f"grouped_max: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+    if idx.device != feat.device:
+        raise RuntimeError(f"grouped_max: idx is on {idx.device}, feat on {feat.device}")
+    if feat.dim() != 2:
+        raise ValueError(f"grouped_max: feat must be [n_s, c], got {tuple(feat.shape)}")
+    if feat.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"grouped_max: feat must be f32, f16 or bf16, got {feat.dtype}")
+    if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 2:
+        raise ValueError(f"grouped_max: idx must be an int32 / int64 [m, k], got {idx.dtype} {tuple(idx.shape)}")
+    if not 1 <= idx.shape[1] <= 64:
+        raise ValueError(f"grouped_max: k must be in [1, 64], got idx {tuple(idx.shape)}")
+    if not 1 <= feat.shape[1] <= 1024:
+        raise ValueError(f"grouped_max: c must be in [1, 1024], got feat {tuple(feat.shape)}")
+    if idx.dtype == torch.int64:
+        idx = idx.clamp(-1, feat.shape[0]).to(torch.int32)
+    need = bool(feat.requires_grad) and torch.is_grad_enabled()  # (needs_input_grad is set under no_grad too)
+    return GroupedMax.apply(feat.contiguous(), idx.contiguous(), need)
 
 
 class Subtraction(Function):

@@ -85,6 +85,46 @@ def kpconv_aggregate_backward(n_q, n_s, n_nb, c, n_kp, query_xyz, support_xyz, n
           ptr(neighbors), ptr(k_points), float(extent), ptr(grad_wf), ptr(grad_feat), opts=opts)
 
 
+# csrc/grouped_max.hip (no counterpart in the reference's launcher set: the max-pool of TransitionDown taken per source row)
+def _row_type(t, name):
+    if t.dtype not in _lib.ROW_TYPES:
+        raise TypeError(f"{name}: expected torch.float32, torch.float16 or torch.bfloat16, got {t.dtype}")
+    return _lib.ROW_TYPES[t.dtype]
+
+
+def _shaped(t, shape, name):
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {list(shape)}, got {list(t.shape)}")
+
+
+def grouped_max_forward(m, n_s, k, c, feat, idx, out, arg, *, opts=None):
+    """out [m,c] (feat's dtype), arg [m,c] uint8 or None <- feat [n_s,c] f32 / f16 / bf16, idx [m,k] int32"""
+    m, n_s, k, c = int(m), int(n_s), int(k), int(c)
+    rt = _row_type(feat, "feat")
+    _chk((feat, feat.dtype, "feat"), (idx, I32, "idx"), (out, feat.dtype, "out"))
+    _shaped(feat, (n_s, c), "feat"), _shaped(idx, (m, k), "idx"), _shaped(out, (m, c), "out")
+    if arg is not None:
+        _chk((arg, torch.uint8, "arg"))
+        _shaped(arg, (m, c), "arg")
+    _call("grouped_max_forward_launcher", feat, m, n_s, k, c, rt, ptr(feat), ptr(idx), ptr(out), ptr(arg), opts=opts)
+
+
+def grouped_max_backward(m, n_s, k, c, grad_out, arg, src_offsets, src_pair, grad_feat, *, opts=None):
+    """grad_feat [n_s,c] (fully written) <- grad_out [m,c] of the same dtype, arg [m,c] uint8, the key-major view of idx:
+    src_offsets (n_s + 1 entries), src_pair (m * k entries), int32"""
+    m, n_s, k, c = int(m), int(n_s), int(k), int(c)
+    rt = _row_type(grad_out, "grad_out")
+    _chk((grad_out, grad_out.dtype, "grad_out"), (arg, torch.uint8, "arg"), (src_offsets, I32, "src_offsets"), (src_pair, I32, "src_pair"),
+         (grad_feat, grad_out.dtype, "grad_feat"))
+    _shaped(grad_out, (m, c), "grad_out"), _shaped(arg, (m, c), "arg"), _shaped(grad_feat, (n_s, c), "grad_feat")
+    if src_offsets.numel() != n_s + 1:
+        raise ValueError(f"src_offsets: expected {n_s + 1} entries, got {src_offsets.numel()}")
+    if src_pair.numel() != m * k:
+        raise ValueError(f"src_pair: expected {m * k} entries, got {src_pair.numel()}")
+    _call("grouped_max_backward_launcher", grad_out, m, n_s, k, c, rt, ptr(grad_out), ptr(arg), ptr(src_offsets), ptr(src_pair), ptr(grad_feat),
+          opts=opts)
+
+
 # attention/attention_cuda.cpp
 def attention_step1_forward_cuda(N, M, h, C, q, k, index0, index1, attn, *, opts=None):
     _chk((q, F32, "q"), (k, F32, "k"), (index0, I32, "index0"), (index1, I32, "index1"), (attn, F32, "attn"))
