@@ -37,6 +37,15 @@ __device__ __forceinline__ void stage_table_t(T *lds, const T *__restrict__ tab,
         lds[x] = tab[(((size_t)r * h + head) * 16 + i) * 3 + ax];
     }
 }
+// the three tables of a head, TS elements apart, ready for every wave of the workgroup
+template <int TS, typename T>
+__device__ __forceinline__ void stage_tables(T *lds, const T *__restrict__ table_q, const T *__restrict__ table_k, const T *__restrict__ table_v, int L,
+                                             int h, int head) {
+    stage_table_t<T>(lds, table_q, L, h, head);
+    stage_table_t<T>(lds + TS, table_k, L, h, head);
+    stage_table_t<T>(lds + 2 * TS, table_v, L, h, head);
+    __syncthreads();
+}
 
 // ---- LDS image of a head's three tables: table TB at float offset TB * TS (TS a compile-time constant, so that the
 // three tables of one (axis, row) differ by an immediate offset), inside a table [axis][row][16] ----
@@ -128,9 +137,23 @@ struct LaneCtx {
         else return ld_row4(q + (size_t)i * C + hoff);
     }
 };
-struct CellBufs {
-    rsrc_t rel, key, qid;
-};
+// this thread's context in a workgroup that serves head blockIdx.y
+template <typename TT, bool PK>
+__device__ __forceinline__ LaneCtx<TT, PK> make_lane_ctx(const TT *lds, int h, int L, int rs, float qscale) {
+    LaneCtx<TT, PK> x;
+    x.lds = lds;
+    x.L = L;
+    x.h = h;
+    x.head = blockIdx.y;
+    x.C = h * 16;
+    x.rs_packed = rs;
+    x.qscale = qscale;
+    x.lane = threadIdx.x & 63;
+    x.p = x.lane >> 2;
+    x.c = x.lane & 3;
+    x.hoff = x.head * 16 + 4 * x.c;
+    return x;
+}
 
 // ------------------------------------------------------------------------------------------------
 // forward
@@ -284,26 +307,12 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
                                                                  const T *__restrict__ table_q, const T *__restrict__ table_k,
                                                                  const T *__restrict__ table_v, float *__restrict__ out,
                                                                  float *__restrict__ ml, float *__restrict__ pbuf, size_t plane) {
-    constexpr int D = 16, TS = TabGeo<LCAP>::TS;
+    constexpr int TS = TabGeo<LCAP>::TS;
     extern __shared__ float lds_raw[];
     T *lds = reinterpret_cast<T *>(lds_raw);
-    LaneCtx<T, PK> x;
-    x.lds = lds;
-    x.L = L;
-    x.h = h;
-    x.head = blockIdx.y;
-    x.C = h * D;
-    x.rs_packed = rs;
-    x.qscale = qscale;
-    x.lane = threadIdx.x & 63;
-    x.p = x.lane >> 2;
-    x.c = x.lane & 3;
-    x.hoff = x.head * D + 4 * x.c;
+    const LaneCtx<T, PK> x = make_lane_ctx<T, PK>(lds, h, L, rs, qscale);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    stage_table_t<T>(lds, table_q, L, h, x.head);
-    stage_table_t<T>(lds + TS, table_k, L, h, x.head);
-    stage_table_t<T>(lds + 2 * TS, table_v, L, h, x.head);
-    __syncthreads();
+    stage_tables<TS, T>(lds, table_q, table_k, table_v, L, h, x.head);
     const int nC = share_count(pl, pl.counts[0]);
     float *pb = pbuf + (size_t)x.head * plane;
     const int slots = gridDim.x * CA_WAVES, slot = blockIdx.x * CA_WAVES + wave;
@@ -312,12 +321,8 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
         if (task >= nC) continue;
         const CellTask ct = cell_task(pl, share_task(pl, task));
         const int nch = (ct.nk + 16 * NP - 1) / (16 * NP);
-        const unsigned tile_bytes = (unsigned)ct.nq * ct.nk * 4u;
-        CellBufs cb;
-        cb.rel = make_rsrc(pl.relp + ct.pbase, tile_bytes);
-        cb.key = make_rsrc(pl.cell_keys + ct.kb, (unsigned)ct.nk * 4u);
-        cb.qid = make_rsrc(pl.cell_order + ct.qs, (unsigned)ct.nq * 4u);
-        const rsrc_t rs_p = make_rsrc(pb + ct.pbase, tile_bytes);
+        const CellBufs cb = make_cell_bufs(pl, ct);
+        const rsrc_t rs_p = tile_rsrc(pb, ct);
         for (int ch = 0; ch < nch; ch++) {  // sweep 1: logits and softmax
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
@@ -478,27 +483,13 @@ __global__ __launch_bounds__(CA_WAVES_BWD * 64) void cell_bwd_kernel(pointops2_c
                                                                  const T *__restrict__ table_v, const float *__restrict__ pbuf,
                                                                  float *__restrict__ gsbuf, size_t plane, float *__restrict__ grad_q,
                                                                  float *__restrict__ grad_k, float *__restrict__ grad_v) {
-    constexpr int D = 16, TS = TabGeo<LCAP>::TS;
+    constexpr int TS = TabGeo<LCAP>::TS;
     extern __shared__ float lds_raw[];
     T *lds = reinterpret_cast<T *>(lds_raw);
-    LaneCtx<T, PK> x;
-    x.lds = lds;
-    x.L = L;
-    x.h = h;
-    x.head = blockIdx.y;
-    x.C = h * D;
-    x.rs_packed = rs;
-    x.qscale = qscale;
-    x.lane = threadIdx.x & 63;
-    x.p = x.lane >> 2;
-    x.c = x.lane & 3;
-    x.hoff = x.head * D + 4 * x.c;
+    const LaneCtx<T, PK> x = make_lane_ctx<T, PK>(lds, h, L, rs, qscale);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float *scr = reinterpret_cast<float *>(lds + 3 * TS) + wave * 256;
-    stage_table_t<T>(lds, table_q, L, h, x.head);
-    stage_table_t<T>(lds + TS, table_k, L, h, x.head);
-    stage_table_t<T>(lds + 2 * TS, table_v, L, h, x.head);
-    __syncthreads();
+    stage_tables<TS, T>(lds, table_q, table_k, table_v, L, h, x.head);
     const int nC = share_count(pl, pl.counts[0]);
     const float *pb = pbuf + (size_t)x.head * plane;
     float *gb = gsbuf + (size_t)x.head * plane;
@@ -508,13 +499,8 @@ __global__ __launch_bounds__(CA_WAVES_BWD * 64) void cell_bwd_kernel(pointops2_c
         if (task >= nC) continue;
         const CellTask ct = cell_task(pl, share_task(pl, task));
         const int nch = (ct.nk + 16 * NP - 1) / (16 * NP);
-        const unsigned tile_bytes = (unsigned)ct.nq * ct.nk * 4u;
-        CellBufs cb;
-        cb.rel = make_rsrc(pl.relp + ct.pbase, tile_bytes);
-        cb.key = make_rsrc(pl.cell_keys + ct.kb, (unsigned)ct.nk * 4u);
-        cb.qid = make_rsrc(pl.cell_order + ct.qs, (unsigned)ct.nq * 4u);
-        const rsrc_t rs_p = make_rsrc(pb + ct.pbase, tile_bytes);
-        const rsrc_t rs_g = make_rsrc(gb + ct.pbase, tile_bytes);
+        const CellBufs cb = make_cell_bufs(pl, ct);
+        const rsrc_t rs_p = tile_rsrc(pb, ct), rs_g = tile_rsrc(gb, ct);
         for (int ch = 0; ch < nch; ch++) {
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
@@ -614,10 +600,8 @@ __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &
         } else {
             ct = cell_task(pl, share_task(pl, task));
         }
-        const unsigned tile_bytes = (unsigned)ct.nq * ct.nk * 4u;
-        const rsrc_t rs_rel = make_rsrc(pl.relp + ct.pbase, tile_bytes);
-        const rsrc_t rs_w = make_rsrc(wb + ct.pbase, tile_bytes);
-        const rsrc_t rs_row = BYKEY ? make_rsrc(pl.cell_keys + ct.kb, (unsigned)ct.nk * 4u) : make_rsrc(pl.cell_order + ct.qs, (unsigned)ct.nq * 4u);
+        const CellBufs cb = make_cell_bufs(pl, ct);
+        const rsrc_t rs_rel = cb.rel, rs_w = tile_rsrc(wb, ct), rs_row = BYKEY ? cb.key : cb.qid;
         const int nrows = BYKEY ? ct.nk : ct.nq, nent = BYKEY ? ct.nq : ct.nk;
         // entry e of row r0 + c: rows = keys: tile[e][r0 + c];  rows = queries: tile[r0 + c][e]
         auto entry_off = [&](int r0, int ent) -> int { return (BYKEY ? ent * ct.nk + r0 + c : (r0 + c) * ct.nk + ent) * 4; };
@@ -742,16 +726,26 @@ __global__ __launch_bounds__(CT_WAVES * 64) void cell_table_grad3_kernel(pointop
     else cell_table_grad_body<TA, false, false, float>(pl, h, L, pbuf, plane, grad_out, h * 16, 1.0f, gtv);
 }
 
+// What a launch refuses before anything else (nullptr: nothing), forward and backward in one place.  The texts are literals because
+// the library keeps the pointer (set_error); the backward names itself in them and states its range of L first.
+static const char *cell_refusal(const pointops2_cell_plan *plan, int hdim, int L, bool backward) {
+    if (hdim != 16) return "cell_attention: d != 16";
+    if (backward && (L < 1 || L > 80)) return "cell_attention backward: table rows L must be in 1..80";
+    if (L < 1) return "cell_attention: no table rows";
+    // relp's indices were clamped to [0, plan->table_rows) and L is the axis stride of the LDS table image
+    if (L != plan->table_rows)
+        return backward ? "cell_attention backward: the tables' row count differs from the plan's table_rows"
+                        : "cell_attention: the tables' row count differs from the plan's table_rows";
+    if (L > 160) return "cell_attention: more than 160 table rows (use the operators)";
+    return nullptr;
+}
+
 // The forward kernel a launch runs (codes of pointops2_cell_forward_variant): launch_cell_fwd takes its decision from here alone,
 // so the table the tests pin is the one that runs.  *why = the error a refusal records (NULL otherwise).
 static int cell_fwd_variant(const pointops2_cell_plan *plan, int h, int hdim, int L, bool bf16, const char **why) {
     *why = nullptr;
     if (plan == nullptr || plan->n_points <= 0) return POINTOPS2_CELL_FWD_NONE;
-    if (hdim != 16) { *why = "cell_attention: d != 16"; return POINTOPS2_CELL_FWD_ERROR; }
-    if (L < 1) { *why = "cell_attention: no table rows"; return POINTOPS2_CELL_FWD_ERROR; }
-    // relp's indices were clamped to [0, plan->table_rows) and L is the axis stride of the LDS table image
-    if (L != plan->table_rows) { *why = "cell_attention: the tables' row count differs from the plan's table_rows"; return POINTOPS2_CELL_FWD_ERROR; }
-    if (L > 160) { *why = "cell_attention: more than 160 table rows (use the operators)"; return POINTOPS2_CELL_FWD_ERROR; }
+    if ((*why = cell_refusal(plan, hdim, L, false)) != nullptr) return POINTOPS2_CELL_FWD_ERROR;
     if (L > 80) return POINTOPS2_CELL_FWD_VALU160;
     if (!bf16) {
         // The matrix-core forward (cell_attn_mfma.hip) where it was measured faster than the VALU walkers (tools/bench_cell.py, MI355X,
@@ -764,56 +758,47 @@ static int cell_fwd_variant(const pointops2_cell_plan *plan, int h, int hdim, in
     return POINTOPS2_CELL_FWD_VALU80;
 }
 
-// RT / TT: storage types of the rows and of the tables.  q, k, v: the first point's row of each.  PK (the packed entry points): rs
-// elements to the next point's, q scaled as it is loaded; otherwise rs = h * 16 and scale = 1 are what the kernels assume.
+// the VALU forward with a table image of LCAP rows per axis
+template <int LCAP, typename RT, typename TT, bool PK>
+static void launch_valu_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const CellRows<RT> &r, const CellTables<TT> &t, float *out, float *ml,
+                            float *pbuf) {
+    const size_t lds = TabGeo<LCAP>::bytes(sizeof(TT));
+    allow_big_lds(cell_fwd_kernel<CA_NP, LCAP, RT, TT, PK>, lds);
+    const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
+    hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, LCAP, RT, TT, PK>), grid, dim3(CA_WAVES * 64), lds, st, *plan, h, L, r.q, r.k, r.v, r.rs, r.scale, t.q, t.k, t.v, out,
+                       ml, pbuf, (size_t)plan->n_pairs);
+}
+
+// RT / TT: storage types of the rows and of the tables.  PK: the packed entry points (CellRows, cell_common.h)
 template <typename RT, typename TT, bool PK>
-static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const RT *q, const RT *k, const RT *v, int rs, float scale,
-                            const TT *table_q, const TT *table_k, const TT *table_v, float *out, float *ml, float *pbuf) {
+static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const CellRows<RT> &r, const CellTables<TT> &t, float *out,
+                            float *ml, float *pbuf) {
     const char *why;
     const int variant = cell_fwd_variant(plan, h, hdim, L, !std::is_same<TT, float>::value, &why);
     if (why != nullptr) { set_error(why); return; }
     if (variant == POINTOPS2_CELL_FWD_NONE) return;
     if constexpr (std::is_same<TT, float>::value) {
         if (variant == POINTOPS2_CELL_FWD_MFMA64 || variant == POINTOPS2_CELL_FWD_MFMA80) {
-            constexpr int row_type = std::is_same<RT, float>::value ? POINTOPS2_ROWS_F32 : std::is_same<RT, f16_t>::value ? POINTOPS2_ROWS_F16 : POINTOPS2_ROWS_BF16;
-            cell_fwd_mfma_launch(st, variant, plan, h, L, row_type, PK, q, k, v, rs, scale, table_q, table_k, table_v, out, pbuf);
+            cell_fwd_mfma_launch(st, variant, plan, h, L, RowTag<RT>::code, PK, CellRows<void>{r.q, r.k, r.v, r.rs, r.scale}, t, out, pbuf);
             check_launch();
             return;
         }
     }
-    const dim3 block(CA_WAVES * 64);
-    const size_t plane = (size_t)plan->n_pairs;
-    if (variant == POINTOPS2_CELL_FWD_VALU80) {
-        const size_t lds = TabGeo<80>::bytes(sizeof(TT));
-        allow_big_lds(cell_fwd_kernel<CA_NP, 80, RT, TT, PK>, lds);
-        const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
-        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 80, RT, TT, PK>), grid, block, lds, st, *plan, h, L, q, k, v, rs, scale, table_q, table_k, table_v, out, ml,
-                           pbuf, plane);
-    } else {  // POINTOPS2_CELL_FWD_VALU160
-        const size_t lds = TabGeo<160>::bytes(sizeof(TT));
-        allow_big_lds(cell_fwd_kernel<CA_NP, 160, RT, TT, PK>, lds);
-        const dim3 grid(cell_grid_x(1, plan->n_cells, h, CA_WAVES), h);
-        hipLaunchKernelGGL((cell_fwd_kernel<CA_NP, 160, RT, TT, PK>), grid, block, lds, st, *plan, h, L, q, k, v, rs, scale, table_q, table_k, table_v, out, ml,
-                           pbuf, plane);
-    }
+    if (variant == POINTOPS2_CELL_FWD_VALU80) launch_valu_fwd<80, RT, TT, PK>(st, plan, h, L, r, t, out, ml, pbuf);
+    else launch_valu_fwd<160, RT, TT, PK>(st, plan, h, L, r, t, out, ml, pbuf);  // POINTOPS2_CELL_FWD_VALU160
     check_launch();
 }
 
-// grad_q / grad_k / grad_v: the first point's row of each, laid out as the rows they belong to
 template <typename RT, typename TT, bool PK>
-static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const RT *q, const RT *k, const RT *v,
-                            int rs, float scale, const float *out, const TT *table_q, const TT *table_k, const TT *table_v, const float *pbuf, float *gsbuf,
-                            float *grad_q, float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
+static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const CellRows<RT> &r, const float *out,
+                            const CellTables<TT> &t, const float *pbuf, float *gsbuf, const CellGrads &g, const CellGrads &gt) {
     if (plan == nullptr || plan->n_points <= 0) return;
-    if (hdim != 16) { set_error("cell_attention: d != 16"); return; }
-    if (L < 1 || L > 80) { set_error("cell_attention backward: table rows L must be in 1..80"); return; }
-    if (L != plan->table_rows) { set_error("cell_attention backward: the tables' row count differs from the plan's table_rows"); return; }
+    if (const char *why = cell_refusal(plan, hdim, L, true)) { set_error(why); return; }
     const size_t lds = TabGeo<80>::bytes(sizeof(TT)) + (size_t)CA_WAVES_BWD * 256 * sizeof(float);
     allow_big_lds(cell_bwd_kernel<CA_NP_BWD, 80, RT, TT, PK>, lds);
     const size_t plane = (size_t)plan->n_pairs;
     hipLaunchKernelGGL((cell_bwd_kernel<CA_NP_BWD, 80, RT, TT, PK>), dim3(cell_grid_x(1, plan->n_cells, h, CA_WAVES_BWD), h),
-                       dim3(CA_WAVES_BWD * 64), lds, st, *plan, h, L, grad_out, q, k, v, rs, scale, out, table_q, table_k, table_v, pbuf, gsbuf, plane, grad_q,
-                       grad_k, grad_v);
+                       dim3(CA_WAVES_BWD * 64), lds, st, *plan, h, L, grad_out, r.q, r.k, r.v, r.rs, r.scale, out, t.q, t.k, t.v, pbuf, gsbuf, plane, g.q, g.k, g.v);
     // the three table gradients read p / gs only
     // Grid of the table-gradient bodies: ONE workgroup of 8 waves per free CU and body (round 2: two of 12).
     // Measured (tools/bench_cell.py, backward of a block, us, two -> one -> half): stage 0 784 -> 717 -> 725 / 905 -> 831 -> 833 (plain / shifted
@@ -824,11 +809,18 @@ static void launch_cell_bwd(hipStream_t st, const pointops2_cell_plan *plan, int
     // it does not.)  The three as ONE grid rather than three launches in a row: backward of a block 10-120 us shorter, most on the small
     // stages.
     const dim3 grid3(cell_grid_x(1, plan->n_cells, h, CT_WAVES), h, 3), tblock(CT_WAVES * 64);
-    if (L <= 64) hipLaunchKernelGGL((cell_table_grad3_kernel<4, RT, PK>), grid3, tblock, CellTableGeo<4>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
-                                    grad_table_q, grad_table_k, grad_table_v, rs, scale);
-    else hipLaunchKernelGGL((cell_table_grad3_kernel<5, RT, PK>), grid3, tblock, CellTableGeo<5>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, q, k, grad_out,
-                            grad_table_q, grad_table_k, grad_table_v, rs, scale);
+    if (L <= 64) hipLaunchKernelGGL((cell_table_grad3_kernel<4, RT, PK>), grid3, tblock, CellTableGeo<4>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, r.q, r.k,
+                                    grad_out, gt.q, gt.k, gt.v, r.rs, r.scale);
+    else hipLaunchKernelGGL((cell_table_grad3_kernel<5, RT, PK>), grid3, tblock, CellTableGeo<5>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, r.q, r.k, grad_out,
+                            gt.q, gt.k, gt.v, r.rs, r.scale);
     check_launch();
+}
+
+// the rows of a packed projection qkv [N, 3, h, 16] (gradients alike) where they lie
+template <typename RT>
+static CellRows<RT> packed_rows(const void *qkv, int h, float scale) {
+    const RT *r = static_cast<const RT *>(qkv);
+    return {r, r + h * 16, r + 2 * h * 16, 3 * h * 16, scale};
 }
 
 }  // namespace p2
@@ -845,27 +837,27 @@ int pointops2_cell_forward_variant(const pointops2_cell_plan *plan, int h, int h
 void cell_attention_forward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *q, const float *k,
                                      const float *v, const float *table_q, const float *table_k, const float *table_v, float *out,
                                      float *ml, float *pbuf) {
-    launch_cell_fwd<float, float, false>(begin_launch().stream, plan, h, hdim, L, q, k, v, h * 16, 1.0f, table_q, table_k, table_v, out, ml, pbuf);
+    launch_cell_fwd<float, float, false>(begin_launch().stream, plan, h, hdim, L, {q, k, v, h * 16, 1.0f}, {table_q, table_k, table_v}, out, ml, pbuf);
 }
 void cell_attention_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const float *q,
                                       const float *k, const float *v, const float *out, const float *table_q, const float *table_k,
                                       const float *table_v, const float *pbuf, float *gsbuf, float *grad_q, float *grad_k,
                                       float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
-    launch_cell_bwd<float, float, false>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, h * 16, 1.0f, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
-                           grad_table_k, grad_table_v);
+    launch_cell_bwd<float, float, false>(begin_launch().stream, plan, h, hdim, L, grad_out, {q, k, v, h * 16, 1.0f}, out, {table_q, table_k, table_v}, pbuf, gsbuf,
+                                         {grad_q, grad_k, grad_v}, {grad_table_q, grad_table_k, grad_table_v});
 }
 // bf16 storage of q / k / v / tables (raw 16-bit patterns), fp32 arithmetic, fp32 outputs and gradients
 void cell_attention_forward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const uint16_t *q, const uint16_t *k,
                                           const uint16_t *v, const uint16_t *table_q, const uint16_t *table_k, const uint16_t *table_v,
                                           float *out, float *ml, float *pbuf) {
-    launch_cell_fwd<bf16_t, bf16_t, false>(begin_launch().stream, plan, h, hdim, L, q, k, v, h * 16, 1.0f, table_q, table_k, table_v, out, ml, pbuf);
+    launch_cell_fwd<bf16_t, bf16_t, false>(begin_launch().stream, plan, h, hdim, L, {q, k, v, h * 16, 1.0f}, {table_q, table_k, table_v}, out, ml, pbuf);
 }
 void cell_attention_backward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const uint16_t *q,
                                            const uint16_t *k, const uint16_t *v, const float *out, const uint16_t *table_q,
                                            const uint16_t *table_k, const uint16_t *table_v, const float *pbuf, float *gsbuf, float *grad_q,
                                            float *grad_k, float *grad_v, float *grad_table_q, float *grad_table_k, float *grad_table_v) {
-    launch_cell_bwd<bf16_t, bf16_t, false>(begin_launch().stream, plan, h, hdim, L, grad_out, q, k, v, h * 16, 1.0f, out, table_q, table_k, table_v, pbuf, gsbuf, grad_q, grad_k, grad_v, grad_table_q,
-                            grad_table_k, grad_table_v);
+    launch_cell_bwd<bf16_t, bf16_t, false>(begin_launch().stream, plan, h, hdim, L, grad_out, {q, k, v, h * 16, 1.0f}, out, {table_q, table_k, table_v}, pbuf, gsbuf,
+                                           {grad_q, grad_k, grad_v}, {grad_table_q, grad_table_k, grad_table_v});
 }
 
 // The rows of the packed projection qkv [N, 3, h, 16] read in place (fp32, half or bf16: what the model's qkv Linear returns, under
@@ -873,42 +865,21 @@ void cell_attention_backward_bf16_launcher(const pointops2_cell_plan *plan, int 
 void cell_attention_qkv_forward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const void *qkv, int row_type, float scale,
                                          const float *table_q, const float *table_k, const float *table_v, float *out, float *ml, float *pbuf) {
     const hipStream_t st = begin_launch().stream;
-    const int C = h * 16;
-    if (row_type == POINTOPS2_ROWS_F32) {
-        const float *r = static_cast<const float *>(qkv);
-        launch_cell_fwd<float, float, true>(st, plan, h, hdim, L, r, r + C, r + 2 * C, 3 * C, scale, table_q, table_k, table_v, out, ml, pbuf);
-    } else if (row_type == POINTOPS2_ROWS_F16) {
-        const f16_t *r = static_cast<const f16_t *>(qkv);
-        launch_cell_fwd<f16_t, float, true>(st, plan, h, hdim, L, r, r + C, r + 2 * C, 3 * C, scale, table_q, table_k, table_v, out, ml, pbuf);
-    } else if (row_type == POINTOPS2_ROWS_BF16) {
-        const bf16_t *r = static_cast<const bf16_t *>(qkv);
-        launch_cell_fwd<bf16_t, float, true>(st, plan, h, hdim, L, r, r + C, r + 2 * C, 3 * C, scale, table_q, table_k, table_v, out, ml, pbuf);
-    } else {
-        set_error("cell_attention_qkv: unknown row_type");
-    }
+    if (!with_row_type(row_type, [&](auto tag) {
+        using RT = typename decltype(tag)::type;
+        launch_cell_fwd<RT, float, true>(st, plan, h, hdim, L, packed_rows<RT>(qkv, h, scale), {table_q, table_k, table_v}, out, ml, pbuf);
+    })) set_error("cell_attention_qkv: unknown row_type");
 }
 void cell_attention_qkv_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const void *qkv, int row_type,
                                           float scale, const float *out, const float *table_q, const float *table_k, const float *table_v,
                                           const float *pbuf, float *gsbuf, float *grad_qkv, float *grad_table_q, float *grad_table_k,
                                           float *grad_table_v) {
     const hipStream_t st = begin_launch().stream;
-    const int C = h * 16;
-    float *g = grad_qkv;
-    if (row_type == POINTOPS2_ROWS_F32) {
-        const float *r = static_cast<const float *>(qkv);
-        launch_cell_bwd<float, float, true>(st, plan, h, hdim, L, grad_out, r, r + C, r + 2 * C, 3 * C, scale, out, table_q, table_k, table_v, pbuf, gsbuf, g, g + C,
-                                      g + 2 * C, grad_table_q, grad_table_k, grad_table_v);
-    } else if (row_type == POINTOPS2_ROWS_F16) {
-        const f16_t *r = static_cast<const f16_t *>(qkv);
-        launch_cell_bwd<f16_t, float, true>(st, plan, h, hdim, L, grad_out, r, r + C, r + 2 * C, 3 * C, scale, out, table_q, table_k, table_v, pbuf, gsbuf, g, g + C,
-                                      g + 2 * C, grad_table_q, grad_table_k, grad_table_v);
-    } else if (row_type == POINTOPS2_ROWS_BF16) {
-        const bf16_t *r = static_cast<const bf16_t *>(qkv);
-        launch_cell_bwd<bf16_t, float, true>(st, plan, h, hdim, L, grad_out, r, r + C, r + 2 * C, 3 * C, scale, out, table_q, table_k, table_v, pbuf, gsbuf, g, g + C,
-                                       g + 2 * C, grad_table_q, grad_table_k, grad_table_v);
-    } else {
-        set_error("cell_attention_qkv backward: unknown row_type");
-    }
+    if (!with_row_type(row_type, [&](auto tag) {
+        using RT = typename decltype(tag)::type;
+        launch_cell_bwd<RT, float, true>(st, plan, h, hdim, L, grad_out, packed_rows<RT>(qkv, h, scale), out, {table_q, table_k, table_v}, pbuf, gsbuf,
+                                         {grad_qkv, grad_qkv + h * 16, grad_qkv + 2 * h * 16}, {grad_table_q, grad_table_k, grad_table_v});
+    })) set_error("cell_attention_qkv backward: unknown row_type");
 }
 
 }  // extern "C"

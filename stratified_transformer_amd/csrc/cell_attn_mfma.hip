@@ -109,16 +109,13 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
         const int task = snake_task(round, slot, slots);
         if (task >= nC) continue;
         const CellTask ct = cell_task(pl, share_task(pl, task));
-        const unsigned tile_bytes = (unsigned)ct.nq * ct.nk * 4u;
-        const rsrc_t rs_rel = make_rsrc(pl.relp + ct.pbase, tile_bytes);
-        const rsrc_t rs_key = make_rsrc(pl.cell_keys + ct.kb, (unsigned)ct.nk * 4u);
-        const rsrc_t rs_qid = make_rsrc(pl.cell_order + ct.qs, (unsigned)ct.nq * 4u);
-        const rsrc_t rs_p = make_rsrc(pb + ct.pbase, tile_bytes);
+        const CellBufs cb = make_cell_bufs(pl, ct);
+        const rsrc_t rs_p = tile_rsrc(pb, ct);
         const int nch = (ct.nk + 16 * NKT - 1) / (16 * NKT);
         // pieces of more than 16 queries run as consecutive groups of 16
         for (int i0 = 0; i0 < ct.nq; i0 += 16) {
             const bool qok = i0 + n < ct.nq;
-            const int qid = (int)bload_u32(rs_qid, (i0 + n) * 4);  // (past the end: 0, never used)
+            const int qid = (int)bload_u32(cb.qid, (i0 + n) * 4);  // (past the end: 0, never used)
             float4 qf = make_float4(0.f, 0.f, 0.f, 0.f);
             if (qok) {
                 if constexpr (PK) qf = scaled_row4<RT>(q + (size_t)qid * rs + hoff, qscale);
@@ -133,10 +130,10 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
             auto logits_chunk = [&](int j0, int nkt) {
                 int keyid[NKT];
 #pragma unroll
-                for (int kt = 0; kt < NKT; kt++) keyid[kt] = (int)bload_u32(rs_key, (j0 + 16 * kt + n) * 4);  // (past the end: 0, masked below)
+                for (int kt = 0; kt < NKT; kt++) keyid[kt] = (int)bload_u32(cb.key, (j0 + 16 * kt + n) * 4);  // (past the end: 0, masked below)
                 float4 kf_nx = ld_row4(k + (size_t)keyid[0] * rs + hoff);
                 unsigned w_nx[4];
-                bload_words<4>(rs_rel, row_off + (j0 + 4 * g) * 4, w_nx);
+                bload_words<4>(cb.rel, row_off + (j0 + 4 * g) * 4, w_nx);
 #pragma unroll 1
                 for (int ax = 0; ax < 3; ax++) {  // (a real loop: unrolled, the kernel is 67 KB of code - more than the instruction cache)
 #pragma unroll
@@ -156,7 +153,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                                 const int kn = kt + 1 < nkt ? kt + 1 : 0;
                                 const int key_n = kt + 1 < nkt ? keyid[kt + 1 < NKT ? kt + 1 : 0] : keyid[0];
                                 kf_nx = ld_row4(k + (size_t)key_n * rs + hoff);
-                                bload_words<4>(rs_rel, row_off + (j0 + 16 * kn + 4 * g) * 4, w_nx);
+                                bload_words<4>(cb.rel, row_off + (j0 + 16 * kn + 4 * g) * 4, w_nx);
                             }
                             if (ax == 0) {
                                 const f32x4c s = mfma4(kf, qf, zero4);  // D[key 4g + t][query n]
@@ -192,7 +189,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
             // ---- sweep 2 of a chunk: lg holds the softmax weights; out += P V + H Tv ----
             auto values_chunk = [&](int j0, int nkt) {
                 unsigned kid_nx[4];
-                bload_words<4>(rs_key, (j0 + 4 * g) * 4, kid_nx);  // keys 4g .. 4g + 3 of the tile (past the end: 0, masked below)
+                bload_words<4>(cb.key, (j0 + 4 * g) * 4, kid_nx);  // keys 4g .. 4g + 3 of the tile (past the end: 0, masked below)
 #pragma unroll
                 for (int kt = 0; kt < NKT; kt++)
                     if (kt < nkt) {
@@ -207,12 +204,12 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                         vf.y = left > 1 ? vf.y : 0.f;
                         vf.z = left > 2 ? vf.z : 0.f;
                         vf.w = left > 3 ? vf.w : 0.f;
-                        if (kt + 1 < nkt) bload_words<4>(rs_key, (j0 + 16 * (kt + 1) + 4 * g) * 4, kid_nx);
+                        if (kt + 1 < nkt) bload_words<4>(cb.key, (j0 + 16 * (kt + 1) + 4 * g) * 4, kid_nx);
                         acc = mfma4(vf, make_float4(lg[kt][0], lg[kt][1], lg[kt][2], lg[kt][3]), acc);  // D[feature 4g + t][query n]
                     }
                 int *hb = reinterpret_cast<int *>(qtb);
                 unsigned w_nx[4];
-                bload_words<4>(rs_rel, row_off + (j0 + 4 * g) * 4, w_nx);
+                bload_words<4>(cb.rel, row_off + (j0 + 4 * g) * 4, w_nx);
 #pragma unroll 1
                 for (int ax = 0; ax < 3; ax++) {
                     for (int x = lane * 4; x < TILE; x += 256) *reinterpret_cast<int4 *>(hb + x) = make_int4(0, 0, 0, 0);
@@ -223,7 +220,7 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
                             unsigned w[4];
 #pragma unroll
                             for (int t = 0; t < 4; t++) w[t] = w_nx[t];
-                            bload_words<4>(rs_rel, row_off + (j0 + 16 * (kt + 1 < nkt ? kt + 1 : 0) + 4 * g) * 4, w_nx);
+                            bload_words<4>(cb.rel, row_off + (j0 + 16 * (kt + 1 < nkt ? kt + 1 : 0) + 4 * g) * 4, w_nx);
 #pragma unroll
                             for (int t = 0; t < 4; t++) {
                                 const float p = lg[kt][t];
@@ -318,33 +315,28 @@ __global__ __launch_bounds__((CmGeo<LP>::WAVES * 64)) void cell_fwd_mfma_kernel(
 }
 
 template <int LP, typename RT, bool PK>
-static void launch_mfma_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const RT *q, const RT *k, const RT *v, int rs, float scale,
-                            const float *table_q, const float *table_k, const float *table_v, float *out, float *pbuf) {
+static void launch_mfma_fwd(hipStream_t st, const pointops2_cell_plan *plan, int h, int L, const CellRows<void> &r, const CellTables<float> &t, float *out,
+                            float *pbuf) {
     using G = CmGeo<LP>;
     const size_t lds = G::lds_bytes();
     allow_big_lds(cell_fwd_mfma_kernel<LP, RT, PK>, lds);
     const dim3 grid(cell_grid_x(1, plan->n_cells, h, G::WAVES), h);
-    hipLaunchKernelGGL((cell_fwd_mfma_kernel<LP, RT, PK>), grid, dim3(G::WAVES * 64), lds, st, *plan, h, L, q, k, v, rs, scale, table_q, table_k, table_v, out,
-                       pbuf, (size_t)plan->n_pairs);
-}
-template <typename RT, bool PK>
-static void launch_mfma_rows(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, const void *q, const void *k, const void *v, int rs,
-                             float scale, const float *table_q, const float *table_k, const float *table_v, float *out, float *pbuf) {
-    const RT *qr = static_cast<const RT *>(q), *kr = static_cast<const RT *>(k), *vr = static_cast<const RT *>(v);
-    if (variant == POINTOPS2_CELL_FWD_MFMA64) launch_mfma_fwd<64, RT, PK>(st, plan, h, L, qr, kr, vr, rs, scale, table_q, table_k, table_v, out, pbuf);
-    else launch_mfma_fwd<80, RT, PK>(st, plan, h, L, qr, kr, vr, rs, scale, table_q, table_k, table_v, out, pbuf);
+    hipLaunchKernelGGL((cell_fwd_mfma_kernel<LP, RT, PK>), grid, dim3(G::WAVES * 64), lds, st, *plan, h, L, static_cast<const RT *>(r.q),
+                       static_cast<const RT *>(r.k), static_cast<const RT *>(r.v), r.rs, r.scale, t.q, t.k, t.v, out, pbuf, (size_t)plan->n_pairs);
 }
 
 // fp32 tables, d = 16; variant = POINTOPS2_CELL_FWD_MFMA64 (L <= 64) or POINTOPS2_CELL_FWD_MFMA80 (L <= 80), as
 // pointops2_cell_forward_variant (cell_attn.hip) chose it; row_type = POINTOPS2_ROWS_* (the caller passes no other).  Not packed: fp32
-// rows [N, h, 16] as they stand (row_stride and scale are not read).
-void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, int row_type, bool packed, const void *q,
-                          const void *k, const void *v, int row_stride, float scale, const float *table_q, const float *table_k, const float *table_v,
-                          float *out, float *pbuf) {
-    if (!packed) launch_mfma_rows<float, false>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
-    else if (row_type == POINTOPS2_ROWS_F16) launch_mfma_rows<f16_t, true>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
-    else if (row_type == POINTOPS2_ROWS_BF16) launch_mfma_rows<bf16_t, true>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
-    else launch_mfma_rows<float, true>(st, variant, plan, h, L, q, k, v, row_stride, scale, table_q, table_k, table_v, out, pbuf);
+// rows [N, h, 16] as they stand (rows.rs and rows.scale are not read).
+void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, int row_type, bool packed, const CellRows<void> &rows,
+                          const CellTables<float> &tabs, float *out, float *pbuf) {
+    auto launch = [&](auto tag, auto pk) {
+        using RT = typename decltype(tag)::type;
+        if (variant == POINTOPS2_CELL_FWD_MFMA64) launch_mfma_fwd<64, RT, decltype(pk)::value>(st, plan, h, L, rows, tabs, out, pbuf);
+        else launch_mfma_fwd<80, RT, decltype(pk)::value>(st, plan, h, L, rows, tabs, out, pbuf);
+    };
+    if (!packed) launch(RowTag<float>{}, std::false_type{});
+    else with_row_type(row_type, [&](auto tag) { launch(tag, std::true_type{}); });
 }
 
 }  // namespace p2

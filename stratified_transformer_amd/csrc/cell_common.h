@@ -184,6 +184,20 @@ __device__ __forceinline__ int share_task(const pointops2_cell_plan &pl, int i) 
     if (pl.task_list != nullptr) return i;
     return pl.task_step > 1 ? pl.task_first + i * pl.task_step : i;
 }
+// Descriptors of a task's tile: its packed rel-pos words, its key list and its query ids ...
+struct CellBufs {
+    rsrc_t rel, key, qid;
+};
+__device__ __forceinline__ unsigned tile_bytes(const CellTask &ct) { return (unsigned)ct.nq * ct.nk * 4u; }
+__device__ __forceinline__ CellBufs make_cell_bufs(const pointops2_cell_plan &pl, const CellTask &ct) {
+    CellBufs cb;
+    cb.rel = make_rsrc(pl.relp + ct.pbase, tile_bytes(ct));
+    cb.key = make_rsrc(pl.cell_keys + ct.kb, (unsigned)ct.nk * 4u);
+    cb.qid = make_rsrc(pl.cell_order + ct.qs, (unsigned)ct.nq * 4u);
+    return cb;
+}
+// ... and its tile of one head's weight plane (pbuf, gsbuf)
+__device__ __forceinline__ rsrc_t tile_rsrc(const float *plane_base, const CellTask &ct) { return make_rsrc(plane_base + ct.pbase, tile_bytes(ct)); }
 
 
 // Persistent grid of the cell walkers: `per_cu` workgroups for every CU that is FREE, over all heads; never more waves than
@@ -202,11 +216,40 @@ static int cell_grid_x(int per_cu, int tasks, int h, int waves) {
     return max(1, min(cap, div_up(tasks, waves)));
 }
 
+// ---- host side: the operands of a launch.  Rows: the first point's row of each, `rs` elements to the next point's, q taken times `scale` as
+// it is loaded (packed instances only: the others assume rs = h * 16 and scale = 1); RT = void: on their way into another translation unit ----
+template <typename RT>
+struct CellRows {
+    const RT *q, *k, *v;
+    int rs;
+    float scale;
+};
+template <typename TT>
+struct CellTables {
+    const TT *q, *k, *v;
+};
+struct CellGrads {  // of the rows (the first point's row of each, laid out as the rows they belong to) or of the tables
+    float *q, *k, *v;
+};
+template <typename RT>
+struct RowTag {
+    using type = RT;
+    static constexpr int code = std::is_same<RT, float>::value ? POINTOPS2_ROWS_F32 : std::is_same<RT, f16_t>::value ? POINTOPS2_ROWS_F16 : POINTOPS2_ROWS_BF16;
+};
+// f(RowTag<RT>{}) for the storage type that `row_type` (POINTOPS2_ROWS_*) names; false: no such code, f was not called
+template <typename F>
+static bool with_row_type(int row_type, F f) {
+    if (row_type == POINTOPS2_ROWS_F32) f(RowTag<float>{});
+    else if (row_type == POINTOPS2_ROWS_F16) f(RowTag<f16_t>{});
+    else if (row_type == POINTOPS2_ROWS_BF16) f(RowTag<bf16_t>{});
+    else return false;
+    return true;
+}
+
 // cell_attn_mfma.hip: the forward on the matrix cores (fp32 tables), variant POINTOPS2_CELL_FWD_MFMA64 or _MFMA80 of
-// pointops2_cell_forward_variant (cell_attn.hip decides).  packed: q / k / v are rows of `row_type` (POINTOPS2_ROWS_*), `row_stride`
-// elements from one point's row to the next, q scaled as it is loaded; otherwise fp32 [N, h, 16] tensors taken as they stand.
-void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, int row_type, bool packed, const void *q,
-                          const void *k, const void *v, int row_stride, float scale, const float *table_q, const float *table_k, const float *table_v,
-                          float *out, float *pbuf);
+// pointops2_cell_forward_variant (cell_attn.hip decides).  packed: rows of `row_type` (POINTOPS2_ROWS_*), q scaled as it is loaded;
+// otherwise fp32 [N, h, 16] tensors taken as they stand.
+void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, int row_type, bool packed, const CellRows<void> &rows,
+                          const CellTables<float> &tabs, float *out, float *pbuf);
 
 }  // namespace p2

@@ -97,6 +97,44 @@ def window_attention(q, k, v, table_q, table_k, table_v, index0_offsets, index1,
     return WindowAttention.apply(q, k, v, table_q, table_k, table_v, index0_offsets, index1, rel_idx)
 
 
+def _cell_checks(plan, hdim, L, rows, needs_grad):
+    """What both cell functions refuse before they launch; rows: the row counts of q, k, v."""
+    if hdim != 16:
+        raise RuntimeError("cell_attention: d != 16 (use the operators of pointops for other head dims)")
+    if any(r != plan.n_points for r in rows):
+        raise RuntimeError("cell_attention: the plan was built for %d points, q/k/v have %d/%d/%d rows" % (plan.n_points, *rows))
+    # The plan's packed rel-pos indices were clamped to [0, plan.table_rows) when it was filled and the kernels take the
+    # tables' L as the axis stride of their LDS image: any other L would index another axis / table (the model asserts the
+    # index range instead, model/stratified_transformer.py:189-190).
+    if L != plan.table_rows:
+        raise RuntimeError("cell_attention: the plan was built for tables of %d rows (cell_table_rows), the tables have %d" % (plan.table_rows, L))
+    if L > 80 and needs_grad:
+        raise RuntimeError("cell_attention: the backward supports at most 80 table rows (L = %d): use the operators of pointops, "
+                           "or run the forward under torch.no_grad()" % L)
+
+
+def _cell_forward_buffers(plan, N, h, dev):
+    """out [N, h, 16], ml [N, h, 2], pbuf [h, n_pairs], fp32."""
+    # a plan restricted to a share of the cells (CellPlan.share: one scene over several ranks) leaves the other cells' rows and
+    # tile entries untouched: they must read as zero (the ranks' outputs are summed; the key-side table gradient walks all cells)
+    alloc = torch.zeros if plan.partial else torch.empty
+    f32 = dict(dtype=torch.float32, device=dev)
+    return alloc((N, h, 16), **f32), torch.empty((N, h, 2), **f32), alloc((h, max(plan.n_pairs, 1)), **f32)
+
+
+def _cell_backward_buffers(plan, pbuf, *accumulated):
+    """gsbuf like pbuf, and one zero-filled fp32 gradient per tensor of `accumulated`: views of ONE buffer, so that a block pays one
+    fill kernel instead of one per gradient."""
+    gsbuf = torch.zeros_like(pbuf) if plan.partial else torch.empty_like(pbuf)
+    acc = torch.zeros(sum(t.numel() for t in accumulated), dtype=torch.float32, device=pbuf.device)
+    return gsbuf, [g.view(t.shape) for g, t in zip(acc.split([t.numel() for t in accumulated]), accumulated)]
+
+
+def _as_operand(dtype, *grads):
+    """autograd wants a gradient of the operand's dtype; the kernels took the sums in fp32"""
+    return grads if dtype == torch.float32 else tuple(g.to(dtype) for g in grads)
+
+
 class CellAttention(Function):
     """The same operator sequence on a cell plan (index_build.CellPlan; csrc/cell_attn.hip): one wave per
     (cell, head) loads the cell's key / value rows once for all its queries; the backward keeps dK / dV of a cell in
@@ -105,33 +143,16 @@ class CellAttention(Function):
     @staticmethod
     def forward(ctx, q, k, v, table_q, table_k, table_v, plan):
         N, h, hdim = q.shape
-        if hdim != 16:
-            raise RuntimeError("cell_attention: d != 16 (use the operators of pointops for other head dims)")
         L = table_q.shape[0]
-        if plan.n_points != N or k.shape[0] != N or v.shape[0] != N:
-            raise RuntimeError("cell_attention: the plan was built for %d points, q/k/v have %d/%d/%d rows" % (plan.n_points, N, k.shape[0], v.shape[0]))
-        # The plan's packed rel-pos indices were clamped to [0, plan.table_rows) when it was filled and the kernels take the
-        # tables' L as the axis stride of their LDS image: any other L would index another axis / table (the model asserts the
-        # index range instead, model/stratified_transformer.py:189-190).
-        if L != plan.table_rows:
-            raise RuntimeError("cell_attention: the plan was built for tables of %d rows (cell_table_rows), the tables have %d" % (plan.table_rows, L))
-        if L > 80 and any(ctx.needs_input_grad[:6]):
-            raise RuntimeError("cell_attention: the backward supports at most 80 table rows (L = %d): use the operators of pointops, "
-                               "or run the forward under torch.no_grad()" % L)
+        _cell_checks(plan, hdim, L, (N, k.shape[0], v.shape[0]), any(ctx.needs_input_grad[:6]))
         st = q.dtype  # storage type of q / k / v / tables: fp32, or bf16 (fp32 arithmetic and outputs either way)
         if st not in (torch.float32, torch.bfloat16):
             raise TypeError("cell_attention: q / k / v / tables must all be float32 or all bfloat16, got %s" % st)
         pointops_cuda._chk((q, st, "q"), (k, st, "k"), (v, st, "v"), (table_q, st, "table_q"), (table_k, st, "table_k"), (table_v, st, "table_v"))
         assert table_k.shape == table_q.shape and table_v.shape == table_q.shape
-        dev = q.device
-        # a plan restricted to a share of the cells (CellPlan.share: one scene over several ranks) leaves the other cells' rows and
-        # tile entries untouched: they must read as zero (the ranks' outputs are summed; the key-side table gradient walks all cells)
-        alloc = torch.zeros if plan.partial else torch.empty
-        out = alloc((N, h, hdim), dtype=torch.float32, device=dev)
-        ml = torch.empty((N, h, 2), dtype=torch.float32, device=dev)
-        pbuf = alloc((h, max(plan.n_pairs, 1)), dtype=torch.float32, device=dev)
+        out, ml, pbuf = _cell_forward_buffers(plan, N, h, q.device)
         _lib.call("cell_attention_forward_launcher" if st == torch.float32 else "cell_attention_forward_bf16_launcher", plan.c_arg(), h, hdim, L, ptr(q), ptr(k), ptr(v), ptr(table_q), ptr(table_k), ptr(table_v),
-                  ptr(out), ptr(ml), ptr(pbuf), device=dev)
+                  ptr(out), ptr(ml), ptr(pbuf), device=q.device)
         ctx.plan = plan
         ctx.save_for_backward(q, k, v, table_q, table_k, table_v, out, pbuf)
         return out
@@ -142,23 +163,14 @@ class CellAttention(Function):
         plan = ctx.plan
         N, h, hdim = q.shape
         L = table_q.shape[0]
-        dev = q.device
         grad_out = grad_out.contiguous()
         pointops_cuda._chk((grad_out, torch.float32, "grad_out"))
-        gsbuf = torch.zeros_like(pbuf) if plan.partial else torch.empty_like(pbuf)
-        f32 = dict(dtype=torch.float32, device=dev)
-        grad_q = (torch.zeros if plan.partial else torch.empty)(q.shape, **f32)
-        # the five accumulated gradients are views of ONE zero-filled buffer: one fill kernel instead of five per block
-        nkv, ntab = k.numel(), table_q.numel()
-        acc = torch.zeros(2 * nkv + 3 * ntab, **f32)
-        grad_k, grad_v = acc[:nkv].view(k.shape), acc[nkv:2 * nkv].view(v.shape)
-        gtq, gtk, gtv = (acc[2 * nkv + i * ntab:2 * nkv + (i + 1) * ntab].view(table_q.shape) for i in range(3))
+        grad_q = (torch.zeros if plan.partial else torch.empty)(q.shape, dtype=torch.float32, device=q.device)
+        gsbuf, (grad_k, grad_v, gtq, gtk, gtv) = _cell_backward_buffers(plan, pbuf, k, v, table_q, table_k, table_v)
         _lib.call("cell_attention_backward_launcher" if q.dtype == torch.float32 else "cell_attention_backward_bf16_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(q), ptr(k), ptr(v), ptr(out), ptr(table_q),
                   ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_q), ptr(grad_k), ptr(grad_v), ptr(gtq), ptr(gtk), ptr(gtv),
-                  device=dev)
-        if q.dtype != torch.float32:  # autograd wants a gradient of the operand's dtype; the sums above were taken in fp32
-            grad_q, grad_k, grad_v, gtq, gtk, gtv = (g.to(q.dtype) for g in (grad_q, grad_k, grad_v, gtq, gtk, gtv))
-        return grad_q, grad_k, grad_v, gtq, gtk, gtv, None
+                  device=q.device)
+        return (*_as_operand(q.dtype, grad_q, grad_k, grad_v, gtq, gtk, gtv), None)
 
 
 def cell_attention(q, k, v, table_q, table_k, table_v, plan):
@@ -178,28 +190,16 @@ class CellAttentionQKV(Function):
         if qkv.dim() != 4 or qkv.shape[1] != 3:
             raise RuntimeError("cell_attention_qkv: qkv must be [N, 3, h, 16], got %s" % (tuple(qkv.shape),))
         N, _, h, hdim = qkv.shape
-        if hdim != 16:
-            raise RuntimeError("cell_attention: d != 16 (use the operators of pointops for other head dims)")
         L = table_q.shape[0]
-        if plan.n_points != N:
-            raise RuntimeError("cell_attention: the plan was built for %d points, q/k/v have %d/%d/%d rows" % (plan.n_points, N, N, N))
-        if L != plan.table_rows:
-            raise RuntimeError("cell_attention: the plan was built for tables of %d rows (cell_table_rows), the tables have %d" % (plan.table_rows, L))
-        if L > 80 and any(ctx.needs_input_grad[:5]):
-            raise RuntimeError("cell_attention: the backward supports at most 80 table rows (L = %d): use the operators of pointops, "
-                               "or run the forward under torch.no_grad()" % L)
+        _cell_checks(plan, hdim, L, (N, N, N), any(ctx.needs_input_grad[:5]))
         if qkv.dtype not in _lib.ROW_TYPES:
             raise TypeError("cell_attention_qkv: qkv must be float32, float16 or bfloat16, got %s" % qkv.dtype)
         f32 = torch.float32
         pointops_cuda._chk((qkv, qkv.dtype, "qkv"), (table_q, f32, "table_q"), (table_k, f32, "table_k"), (table_v, f32, "table_v"))
         assert table_k.shape == table_q.shape and table_v.shape == table_q.shape
-        dev = qkv.device
-        alloc = torch.zeros if plan.partial else torch.empty  # (a share of the cells: CellAttention.forward)
-        out = alloc((N, h, hdim), dtype=f32, device=dev)
-        ml = torch.empty((N, h, 2), dtype=f32, device=dev)
-        pbuf = alloc((h, max(plan.n_pairs, 1)), dtype=f32, device=dev)
+        out, ml, pbuf = _cell_forward_buffers(plan, N, h, qkv.device)
         _lib.call("cell_attention_qkv_forward_launcher", plan.c_arg(), h, hdim, L, ptr(qkv), _lib.ROW_TYPES[qkv.dtype], float(scale), ptr(table_q),
-                  ptr(table_k), ptr(table_v), ptr(out), ptr(ml), ptr(pbuf), device=dev)
+                  ptr(table_k), ptr(table_v), ptr(out), ptr(ml), ptr(pbuf), device=qkv.device)
         ctx.plan, ctx.scale = plan, float(scale)
         ctx.save_for_backward(qkv, table_q, table_k, table_v, out, pbuf)
         return out
@@ -210,20 +210,12 @@ class CellAttentionQKV(Function):
         plan = ctx.plan
         N, _, h, hdim = qkv.shape
         L = table_q.shape[0]
-        dev = qkv.device
         grad_out = grad_out.contiguous()
         pointops_cuda._chk((grad_out, torch.float32, "grad_out"))
-        gsbuf = torch.zeros_like(pbuf) if plan.partial else torch.empty_like(pbuf)
-        # the gradient of qkv and the three table gradients are views of ONE zero-filled buffer
-        nqkv, ntab = qkv.numel(), table_q.numel()
-        acc = torch.zeros(nqkv + 3 * ntab, dtype=torch.float32, device=dev)
-        grad_qkv = acc[:nqkv].view(qkv.shape)
-        gtq, gtk, gtv = (acc[nqkv + i * ntab:nqkv + (i + 1) * ntab].view(table_q.shape) for i in range(3))
+        gsbuf, (grad_qkv, gtq, gtk, gtv) = _cell_backward_buffers(plan, pbuf, qkv, table_q, table_k, table_v)
         _lib.call("cell_attention_qkv_backward_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(qkv), _lib.ROW_TYPES[qkv.dtype], ctx.scale,
-                  ptr(out), ptr(table_q), ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_qkv), ptr(gtq), ptr(gtk), ptr(gtv), device=dev)
-        if qkv.dtype != torch.float32:  # autograd wants a gradient of the operand's dtype; the sums above were taken in fp32
-            grad_qkv = grad_qkv.to(qkv.dtype)
-        return grad_qkv, None, gtq, gtk, gtv, None
+                  ptr(out), ptr(table_q), ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_qkv), ptr(gtq), ptr(gtk), ptr(gtv), device=qkv.device)
+        return (*_as_operand(qkv.dtype, grad_qkv), None, gtq, gtk, gtv, None)
 
 
 def cell_attention_qkv(qkv, scale, table_q, table_k, table_v, plan):
