@@ -341,6 +341,16 @@ void pointops2_cell_plan_fill_launcher(int N, const float *xyz, float window, fl
                                        const float *wc, const int *cell_order, const int *qcell, const int *cell_qstart,
                                        const int *cell_desc, const int *cell_kbase, const int *cell_pbase, int *cell_keys, int *kcell,
                                        unsigned int *relp);
+/* Swin3D variant (model/swin3d_transformer.py:149-154: vanilla windows, no sampled keys, tables of L = 2 * qgl - 1 rows with
+ * qgl = int(window / quant)).  The rel-pos index of a pair is q[index_0] - q[index_1] + qgl - 1 with q the per-point quantised in-window
+ * coordinate ((xyz - min + shift) % window) // quant in torch's fp32 arithmetic: `quant` writes q [N,3] for the plain (shifted = 0) or
+ * the shifted pattern (bbox6: pointops2_bbox_launcher), `pairs_rel` the rel_idx [M,3] of a pair list, `cell_fill` is pass 2 of a cell
+ * plan (pointops2_cell_plan_fill_launcher: same arrays, same layout and flag rule) with the indices clamped to [0, L). */
+void pointops2_swin_quant_launcher(int N, const float *xyz, const float *bbox6, float window, float quant, int shifted, int *q);
+void pointops2_swin_pairs_rel_launcher(int N, int M, const int *index_0, const int *index_1, const int *q, int qgl, int *rel_idx);
+void pointops2_swin_cell_fill_launcher(int N, int L, int qgl, const int *q, const int *s_order, const int *ls, const float *wc,
+                                       const int *cell_order, const int *qcell, const int *cell_qstart, const int *cell_desc,
+                                       const int *cell_kbase, const int *cell_pbase, int *cell_keys, int *kcell, unsigned int *relp);
 /* The whole operator sequence of WindowAttention.forward (:183-208) on a cell plan, d = 16.  q, k, v [N,h,16]; tables [L,h,16,3];
  * out [N,h,16] fully written; pbuf [h, P] receives the softmax weights in tile order (kept for the backward); ml [N,h,2] is
  * scratch (running max / sum of rows longer than one register chunk). */

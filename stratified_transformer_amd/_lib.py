@@ -86,6 +86,9 @@ SIGNATURES = {
     "pointops2_cell_plan_prepare_launcher": [I, I, P, P, P, P, P, P, Z],
     "pointops2_cell_plan_sizes_launcher": [I, P, P, P, P, P, P, P, P, P, P, P, P, P, Z],
     "pointops2_cell_plan_fill_launcher": [I, P, F, F, I, P, P, P, P, P, P, P, P, P, P, P, P],
+    "pointops2_swin_quant_launcher": [I, P, P, F, F, I, P],
+    "pointops2_swin_pairs_rel_launcher": [I, I, P, P, P, I, P],
+    "pointops2_swin_cell_fill_launcher": [I, I, I] + [P] * 13,
     "cell_attention_forward_launcher": [P, I, I, I] + [P] * 9,
     "cell_attention_backward_launcher": [P, I, I, I] + [P] * 16,
     "cell_attention_forward_bf16_launcher": [P, I, I, I] + [P] * 9,

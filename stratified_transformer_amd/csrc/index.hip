@@ -381,6 +381,66 @@ __global__ __launch_bounds__(256) void cell_fill_kernel(int N, const float *__re
     }
 }
 
+// ---- Swin3D variant (model/swin3d_transformer.py:149-154): vanilla windows, no sampled keys.  The rel-pos index of a
+// pair is the difference of the two points' quantised in-window coordinates + int(window / quant) - 1: integer arithmetic once the
+// per-point coordinate exists, so it is computed per point and the pair list / the cell tiles only subtract.
+// torch's device `%` on floats: fmod, then + b where the result is non-zero and its sign differs from b's
+__device__ __forceinline__ float remainder_f(float a, float b) {
+    float mod = fmodf(a, b);
+    if ((mod != 0.f) && ((b < 0.f) != (mod < 0.f))) mod = __fadd_rn(mod, b);
+    return mod;
+}
+// q[i, a] = ((xyz - xyz.min(0)[0] + shift) % window) // quant   (:151-152), shift = 0 or 1/2 * window taken in fp32 (:261)
+__global__ void swin_quant_kernel(int N, const float *__restrict__ xyz, const float *__restrict__ bbox6, float window, float quant, int shifted,
+                                  int *__restrict__ q) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N * 3) return;
+    float v = __fsub_rn(xyz[t], bbox6[t % 3]);                 // xyz - xyz_min
+    if (shifted) v = __fadd_rn(v, __fmul_rn(0.5f, window));   // + shift_size (the plain pattern adds 0.0)
+    q[t] = (int)div_floor(remainder_f(v, window), quant);     // % window_size, // quant_size
+}
+// rel_idx[m, a] = q[index_0[m], a] - q[index_1[m], a] + bias   (:153-154, map_func :129-130; bias = int(window / quant) - 1)
+__global__ void swin_pairs_rel_kernel(int N, int M, const int *__restrict__ index_0, const int *__restrict__ index_1, const int *__restrict__ q, int bias,
+                                      int *__restrict__ rel_idx) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const int i = index_0[m], j = index_1[m];
+    if ((unsigned)i >= (unsigned)N || (unsigned)j >= (unsigned)N) return;  // (not a pair of this cloud: nothing to read)
+#pragma unroll
+    for (int a = 0; a < 3; a++) rel_idx[(size_t)m * 3 + a] = q[(size_t)i * 3 + a] - q[(size_t)j * 3 + a] + bias;
+}
+// cell_fill_kernel for this variant: the same tile layout, key lists and flag rule; the three bytes of a word come from the integer
+// difference of the quantised coordinates, clamped to [0, L)
+__global__ __launch_bounds__(256) void cell_fill_swin_kernel(int N, int L, int bias, const int *__restrict__ q, const int *__restrict__ s_order,
+                                                             const int *__restrict__ ls, const float *__restrict__ wc, const int *__restrict__ order,
+                                                             const int *__restrict__ qcell, const int *__restrict__ cell_qstart,
+                                                             const int *__restrict__ cell_desc, const int *__restrict__ cell_kbase,
+                                                             const int *__restrict__ cell_pbase, int *__restrict__ cell_keys,
+                                                             int *__restrict__ kcell, unsigned *__restrict__ relp) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + wave;
+    if (t >= N) return;
+    const int cid = qcell[t], i = order[t];
+    const int d0 = cell_desc[cid * 4], nd = cell_desc[cid * 4 + 1], c0 = cell_desc[cid * 4 + 2], ns = cell_desc[cid * 4 + 3];
+    const int nk = nd + ns, il = t - cell_qstart[cid], kb = cell_kbase[cid];
+    unsigned *row = relp + (size_t)cell_pbase[cid] + (size_t)il * nk;
+    const int qi[3] = {q[(size_t)i * 3], q[(size_t)i * 3 + 1], q[(size_t)i * 3 + 2]};
+    for (int jl = lane; jl < nk; jl += 64) {
+        const int j = jl < nd ? s_order[d0 + jl] : ls[c0 + jl - nd];
+        unsigned w = (jl >= nd && !coord_differs(wc, i, j)) ? 0x80000000u : 0u;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const int b = min(max(qi[a] - q[(size_t)j * 3 + a] + bias, 0), L - 1);
+            w |= (unsigned)b << (8 * a);
+        }
+        row[jl] = w;
+        if (il == 0) {
+            cell_keys[kb + jl] = j;
+            kcell[kb + jl] = cid;
+        }
+    }
+}
+
 static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 static size_t sort64_bytes(int N) {
     size_t bytes = 0;
@@ -690,6 +750,46 @@ void pointops2_cell_plan_fill_launcher(int N, const float *xyz, float window, fl
     const float two_w = (float)(2.0 * (double)window);
     hipLaunchKernelGGL(cell_fill_kernel, dim3(div_up(N, 4)), dim3(256), 0, st, N, xyz, two_w, quant, L, s_order, ls, wc, cell_order,
                        qcell, cell_qstart, cell_desc, cell_kbase, cell_pbase, cell_keys, kcell, relp);
+    check_launch();
+}
+
+// ---- Swin3D variant (see swin_quant_kernel) -----------------------------------------------------------------------
+// q [N,3]: the quantised in-window coordinate of every point of the plain (shifted = 0) or the shifted pattern; bbox6 from pointops2_bbox_launcher
+void pointops2_swin_quant_launcher(int N, const float *xyz, const float *bbox6, float window, float quant, int shifted, int *q) {
+    const hipStream_t st = begin_launch().stream;
+    if (N < 0 || N > 0x7fffffff / 3) { set_error("pointops2_swin_quant: N out of range"); return; }
+    if (N == 0) return;
+    if (xyz == nullptr || bbox6 == nullptr || q == nullptr) { set_error("pointops2_swin_quant: null pointer"); return; }
+    hipLaunchKernelGGL(swin_quant_kernel, dim3(div_up(N * 3, 256)), dim3(256), 0, st, N, xyz, bbox6, window, quant, shifted, q);
+    check_launch();
+}
+
+// rel_idx [M,3] of a pair list over N points: q[index_0] - q[index_1] + qgl - 1, qgl = int(window / quant)
+void pointops2_swin_pairs_rel_launcher(int N, int M, const int *index_0, const int *index_1, const int *q, int qgl, int *rel_idx) {
+    const hipStream_t st = begin_launch().stream;
+    if (N < 0 || M < 0) { set_error("pointops2_swin_pairs_rel: N or M negative"); return; }
+    if (qgl < 1 || 2 * qgl - 1 > 255) { set_error("pointops2_swin_pairs_rel: table rows L = 2 * qgl - 1 must be in 1..255"); return; }
+    if (M == 0 || N == 0) return;
+    if (index_0 == nullptr || index_1 == nullptr || q == nullptr || rel_idx == nullptr) { set_error("pointops2_swin_pairs_rel: null pointer"); return; }
+    hipLaunchKernelGGL(swin_pairs_rel_kernel, dim3(div_up(M, 256)), dim3(256), 0, st, N, M, index_0, index_1, q, qgl - 1, rel_idx);
+    check_launch();
+}
+
+// pass 2 of a cell plan (pointops2_cell_plan_fill_launcher) for this variant: q from pointops2_swin_quant_launcher of the same pattern
+void pointops2_swin_cell_fill_launcher(int N, int L, int qgl, const int *q, const int *s_order, const int *ls, const float *wc, const int *cell_order,
+                                       const int *qcell, const int *cell_qstart, const int *cell_desc, const int *cell_kbase,
+                                       const int *cell_pbase, int *cell_keys, int *kcell, unsigned *relp) {
+    const hipStream_t st = begin_launch().stream;
+    if (N < 0) { set_error("pointops2_swin_cell_fill: N negative"); return; }
+    if (L < 1 || L > 255) { set_error("pointops2_swin_cell_fill: table rows L must be in 1..255 (packed rel-pos index)"); return; }
+    if (N == 0) return;
+    if (q == nullptr || s_order == nullptr || ls == nullptr || wc == nullptr || cell_order == nullptr || qcell == nullptr || cell_qstart == nullptr ||
+        cell_desc == nullptr || cell_kbase == nullptr || cell_pbase == nullptr || cell_keys == nullptr || kcell == nullptr || relp == nullptr) {
+        set_error("pointops2_swin_cell_fill: null pointer");
+        return;
+    }
+    hipLaunchKernelGGL(cell_fill_swin_kernel, dim3(div_up(N, 4)), dim3(256), 0, st, N, L, qgl - 1, q, s_order, ls, wc, cell_order, qcell, cell_qstart,
+                       cell_desc, cell_kbase, cell_pbase, cell_keys, kcell, relp);
     check_launch();
 }
 

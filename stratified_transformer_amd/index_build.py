@@ -363,7 +363,9 @@ def stage_index_hip(xyz, offset, window_size, quant_size, downsample_idx, cell_t
         return _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_rows, cell_max_queries, on_even, patterns)
 
 
-def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_rows, cell_max_queries, on_even, patterns):
+def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_rows, cell_max_queries, on_even, patterns, swin=0):
+    """swin = int(window / quant) > 0: the Swin3D variant (swin_stage_index_hip) - no sampled keys, cells = the small windows alone, and the rel-pos index (pair
+    list and plan) is the difference of the points' quantised in-window coordinates; every other phase is the Stratified one."""
     import numpy as np
     from . import _lib
     from ._lib import ptr
@@ -377,6 +379,7 @@ def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_ro
 
     parts, ws, ws_bytes, bbox, w32 = ctx["parts"], ctx["ws"], ctx["ws_bytes"], ctx["bbox"], ctx["w32"]
     overflow = ctx.get("overflow")
+    qgl = int(swin)   # (the model's quant_grid_length, swin3d_transformer.py:109, in the caller's Python arithmetic)
     with torch.cuda.device(dev):
         sampled = torch.zeros(N, **i32)
         out = [None, None]   # [plain, shifted]
@@ -398,7 +401,7 @@ def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_ro
             # The cell plans first: the window-centric kernels need nothing else of a pattern, so a caller that waits for `cells_ready`
             # (pipeline.scene_pass) starts its attention blocks while the pair lists - 100 us per pattern at stage 0 - are still being written.
             fills = []
-            for (s, lg, ls, ls_starts, wc, offsets, cells, which), (M, ccounts) in zip(pend, totals):
+            for (s, lg, ls, ls_starts, wc, offsets, cells, which, qc), (M, ccounts) in zip(pend, totals):
                 index_0, index_1 = torch.empty(M, **i32), torch.empty(M, **i32)
                 rel = torch.empty((M, 3), **i32)
                 counts = offsets[1:] - offsets[:-1]
@@ -408,9 +411,12 @@ def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_ro
                     if P < 0 or P >= 2 ** 31 - 1:
                         raise RuntimeError("cell plan: more than 2^31 tile entries")
                     cell_keys, kcell, relp = torch.empty(max(K, 1), **i32), torch.empty(max(K, 1), **i32), torch.empty(max(P, 1), **i32)
-                    call("pointops2_cell_plan_fill_launcher", N, ptr(xyz), float(w32), _f32(quant_size), int(cell_table_rows), ptr(s.order), ptr(ls),
-                         ptr(wc), ptr(cells["cell_order"]), ptr(cells["qcell"]), ptr(cells["cell_qstart"]), ptr(cells["cell_desc"]),
-                         ptr(cells["cell_kbase"]), ptr(cells["cell_pbase"]), ptr(cell_keys), ptr(kcell), ptr(relp))
+                    tile = (ptr(s.order), ptr(ls), ptr(wc), ptr(cells["cell_order"]), ptr(cells["qcell"]), ptr(cells["cell_qstart"]), ptr(cells["cell_desc"]),
+                            ptr(cells["cell_kbase"]), ptr(cells["cell_pbase"]), ptr(cell_keys), ptr(kcell), ptr(relp))
+                    if swin:
+                        call("pointops2_swin_cell_fill_launcher", N, int(cell_table_rows), qgl, ptr(qc), *tile)
+                    else:
+                        call("pointops2_cell_plan_fill_launcher", N, ptr(xyz), float(w32), _f32(quant_size), int(cell_table_rows), *tile)
                     plan = CellPlan(N, n_cells, P, K, nk_max, int(cell_table_rows), n_parents, cell_keys=cell_keys, kcell=kcell, relp=relp,
                                     max_queries=int(cell_max_queries), **cells)
                 out[which] = BlockIndex(index_0, index_1, offsets, counts.max(), rel, None, plan, parts=parts)
@@ -418,23 +424,34 @@ def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_ro
                 # take their rows in it (pointops.row_order_of) without sorting anything
                 from . import pointops as _P
                 _P.seed_row_order(offsets, index_1, s.order, out[which].n_max)
-                fills.append((s, lg, ls, ls_starts, wc, offsets, index_0, index_1, rel))
+                fills.append((s, lg, ls, ls_starts, wc, offsets, index_0, index_1, rel, qc))
             if cell_table_rows is not None:
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(dev))
-                for (_, _, _, _, _, _, _, which), _t in zip(pend, totals):
-                    out[which].cells_ready = ev
-            for s, lg, ls, ls_starts, wc, offsets, index_0, index_1, rel in fills:
+                for p in pend:
+                    out[p[7]].cells_ready = ev
+            for s, lg, ls, ls_starts, wc, offsets, index_0, index_1, rel, qc in fills:
                 call("pointops2_pairs_fill_launcher", N, ptr(xyz), float(w32), _f32(quant_size), ptr(s.cluster), ptr(s.order), ptr(s.starts),
                      ptr(lg.cluster), ptr(ls), ptr(ls_starts), ptr(wc), ptr(offsets), ptr(index_0), ptr(index_1), ptr(rel))
+                if swin:   # (the variant's own rel-pos index over the Stratified one the fill wrote)
+                    call("pointops2_swin_pairs_rel_launcher", N, int(index_0.shape[0]), ptr(index_0), ptr(index_1), ptr(qc), qgl, ptr(rel))
 
         for shifted, sname, lname in ((0, "small", "large"), (1, "small_shift", "large_shift")):
             if shifted not in patterns:
                 continue
             s, lg = parts[sname], parts[lname]
-            ls, ls_starts = torch.empty(max(m, 1), **i32), torch.empty(N + 1, **i32)
-            call("pointops2_sampled_buckets_launcher", N, m, ptr(downsample_idx), ptr(lg.order), ptr(lg.starts), ptr(lg.n_windows),
-                 ptr(sampled), ptr(ls), ptr(ls_starts), ptr(ws), ws_bytes)
+            qc = None
+            if swin:
+                # no sampled keys: every window's candidate list is empty, and a cell is a small window (the "large window" of the cell
+                # key is the small one again, so that the shifted pattern's windows are not cut along the 2x grid)
+                lg = s
+                ls, ls_starts = torch.zeros(1, **i32), torch.zeros(N + 1, **i32)
+                qc = torch.empty((N, 3), **i32)
+                call("pointops2_swin_quant_launcher", N, ptr(xyz), ptr(bbox), float(w32), _f32(quant_size), shifted, ptr(qc))
+            else:
+                ls, ls_starts = torch.empty(max(m, 1), **i32), torch.empty(N + 1, **i32)
+                call("pointops2_sampled_buckets_launcher", N, m, ptr(downsample_idx), ptr(lg.order), ptr(lg.starts), ptr(lg.n_windows),
+                     ptr(sampled), ptr(ls), ptr(ls_starts), ptr(ws), ws_bytes)
             wc = torch.empty((N, 3), dtype=torch.float32, device=dev)
             call("pointops2_window_coord_launcher", N, ptr(xyz), ptr(bbox), float(w32), shifted, ptr(wc))
             offsets = torch.empty(N + 1, **i32)
@@ -442,7 +459,7 @@ def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_ro
                  ptr(offsets), ptr(ws), ws_bytes)
             cells = None
             if cell_table_rows is not None:
-                ready = ctx.get("cells_prepared")
+                ready = None if swin else ctx.get("cells_prepared")   # (prepared cells are keyed by the 2x windows)
                 if ready is not None and ready.get("cap") == int(cell_max_queries) and shifted in ready and not ctx.get("cells_prepared_used", {}).get(shifted):
                     # the first half of the pass ran with the partitions (stage_partitions_hip): only what needs the samples is left
                     cells, cws, cws_bytes = ready[shifted]
@@ -458,7 +475,7 @@ def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_ro
                          ptr(cells["cell_order"]), ptr(cells["qcell"]), ptr(cells["cell_desc"]), ptr(cells["cell_qstart"]), ptr(cells["cell_kbase"]),
                          ptr(cells["cell_pbase"]), ptr(cells["cell_perm"]), ptr(cells["parent_first"]), ptr(cells["counts"]), ptr(cws),
                          max(cws_bytes, ws_bytes))
-            pending.append((s, lg, ls, ls_starts, wc, offsets, cells, shifted))
+            pending.append((s, lg, ls, ls_starts, wc, offsets, cells, shifted, qc))
             if on_even is not None and shifted == 0:
                 # the caller wants the plain pattern as soon as it exists (its first block runs beside the shifted pattern's
                 # build): one more host sync, the plain pattern ~0.4 ms earlier
@@ -486,10 +503,27 @@ def swin_rel_pos_index(xyz, index_0, index_1, window_size, quant_size, shift):
     return (xyz_quant[index_0.long()] - xyz_quant[index_1.long()] + qgl - 1).int()
 
 
-def swin_stage_index_hip(xyz, offset, window_size, quant_size):
+def swin_stage_index_hip(xyz, offset, window_size, quant_size, cell_table_rows=None, cell_max_queries=0):
     """Plain and shifted block index of one Swin3D stage (swin3d_transformer.py:239-278) from the HIP index build: the dense
-    pairs of the small-window partitions (a Stratified stage without sampled keys), then the Swin rel-pos index."""
+    pairs of the small-window partitions (a Stratified stage without sampled keys), then the Swin rel-pos index.
+
+    cell_table_rows = L (must be swin_table_rows(window_size, quant_size)): also the cell plan of both patterns (BlockIndex.cells, one cell
+    per window, cut into pieces of cell_max_queries queries) for fused.cell_attention, and the rel-pos index - of the pair list and, clamped
+    to [0, L), of the plan - by the HIP kernels of csrc/index.hip (swin_quant_kernel ...) instead of the torch chain."""
     none = torch.empty(0, dtype=torch.int32, device=xyz.device)
+    if cell_table_rows is not None:
+        L = swin_table_rows(window_size, quant_size)
+        if int(cell_table_rows) != L:
+            raise ValueError("swin_stage_index_hip: cell_table_rows = %d, but window %g / quant %g has tables of %d rows"
+                             % (int(cell_table_rows), window_size, quant_size, L))
+        assert xyz.is_cuda and xyz.dtype == torch.float32 and xyz.is_contiguous()
+        ctx = stage_partitions_hip(xyz, offset, window_size)
+        args = (xyz, offset, quant_size, none, L, cell_max_queries, None, (0, 1))
+        try:
+            return _stage_index_hip(ctx, *args, swin=(L + 1) // 2)
+        except _KeyOverflow:
+            ctx.update(stage_partitions_hip(xyz, offset, window_size, one_sort=False))
+            return _stage_index_hip(ctx, *args, swin=(L + 1) // 2)
     even, odd, parts = stage_index_hip(xyz, offset, window_size, quant_size, none)
     ws = torch.tensor([window_size] * 3).type_as(xyz)
     for blk, shift in ((even, 0.0), (odd, 1 / 2 * ws)):

@@ -31,6 +31,11 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
     is pipeline.scene_pass's schedule under the unmodified model's call order.  With only BasicLayer / WindowAttention rebound,
     the model's own TransitionDown finds the samples in the sampler's kept state (ordered behind the side stream by an event).
 
+  * The Swin3D variant (model/swin3d_transformer.py: vanilla windows, `blk(feats, xyz, index_0, index_0_offsets, n_max, index_1,
+    shift_size)`): `install_swin_layers()` / `patch_swin_classes()` rebind its BasicLayer / WindowAttention to swin_basic_layer_forward /
+    swin_window_attention_forward - one `index_build.swin_stage_index_hip` per stage with both patterns' cell plans (every cell a dense
+    small window: no flagged tile entries), the same `fused.cell_attention*` per block.  No sampler, no side streams.
+
 Numbers: the same sums in another order (tests/test_hip_parity.py::test_installed_fast_layers_against_the_reference_layer:
 output and every parameter gradient of a depth-2 BasicLayer with TransitionDown against the reference's own run, <= 1e-3).
 """
@@ -132,11 +137,20 @@ def _heads_dim(attn):
 
 def window_attention_forward(self, feats, xyz, index_0, index_1, index_0_offsets, n_max):
     """Replacement of WindowAttention.forward (:164-217), same arguments, same result."""
-    N, C = feats.shape
-    h, d = _heads_dim(self)
     assert index_0.shape[0] == index_1.shape[0]
     if not (self.rel_query and self.rel_key and self.rel_value) or not feats.is_cuda:
         return _original(self)(self, feats, xyz, index_0, index_1, index_0_offsets, n_max)
+    # :186-188 with the GPU's arithmetic; the range asserts of :189-190 become a clamp (no host sync)
+    return _attention(self, feats, index_0_offsets, index_1, n_max, lambda L: index_build.rel_pos_index(
+        xyz, index_0, index_1, float(self.window_size), float(self.quant_size)).clamp_(0, L - 1).contiguous())
+
+
+def _attention(self, feats, index_0_offsets, index_1, n_max, rel_index):
+    """What both model files' WindowAttention.forward do between the qkv Linear and proj (stratified_transformer.py:180-215,
+    swin3d_transformer.py:145-176) on the block the layer handed over (`_sta_block`); rel_index(L): the variant's own rel-pos index of
+    the pair list, asked for only when no block (or one of another pair list) is there."""
+    N, C = feats.shape
+    h, d = _heads_dim(self)
     tq, tk, tv = (t.float().contiguous() for t in (self.relative_pos_query_table, self.relative_pos_key_table, self.relative_pos_value_table))
     L = int(tq.shape[0])
     blk = getattr(self, "_sta_block", None)
@@ -158,8 +172,8 @@ def window_attention_forward(self, feats, xyz, index_0, index_1, index_0_offsets
         offs, i1 = index_0_offsets.int().contiguous(), index_1.int().contiguous()
         if blk is not None and blk.rel_idx is not None and blk.rel_idx.shape[0] == i1.shape[0]:
             rel = blk.rel_idx
-        else:  # :186-188 with the GPU's arithmetic; the range asserts of :189-190 become a clamp (no host sync)
-            rel = index_build.rel_pos_index(xyz, index_0, index_1, float(self.window_size), float(self.quant_size)).clamp_(0, L - 1).contiguous()
+        else:
+            rel = rel_index(L)
         if d == 16:
             x = fused.window_attention(query, key, value, tq, tk, tv, offs, i1, rel)
         else:
@@ -368,11 +382,46 @@ def transition_down_forward(self, feats, xyz, offset):
     return pooled.squeeze(-1), t["n_xyz"], t["n_offset"]
 
 
-def patch_classes(basic_layer_cls=None, window_attention_cls=None, transition_down_cls=None):
-    """Rebinds `forward` on the given classes (any classes with the reference's attribute names); returns what was patched."""
+def swin_window_attention_forward(self, feats, xyz, index_0, index_0_offsets, n_max, index_1, shift_size):
+    """Replacement of the Swin3D WindowAttention.forward (model/swin3d_transformer.py:132-178), same arguments, same result: on the
+    cell plan swin_basic_layer_forward handed over, else on the pair list it was given (rel-pos index :151-154 by torch, clamped)."""
+    if not (self.rel_query and self.rel_key and self.rel_value) or not feats.is_cuda:
+        return _original(self)(self, feats, xyz, index_0, index_0_offsets, n_max, index_1, shift_size)
+    return _attention(self, feats, index_0_offsets, index_1, n_max, lambda L: index_build.swin_rel_pos_index(
+        xyz, index_0, index_1, float(self.window_size), float(self.quant_size), shift_size).clamp_(0, L - 1).contiguous())
+
+
+def swin_basic_layer_forward(self, feats, xyz, offset):
+    """Replacement of the Swin3D BasicLayer.forward (model/swin3d_transformer.py:230-296), same arguments, same six results: both
+    patterns' pair lists, rel-pos indices and cell plans from ONE index_build.swin_stage_index_hip call (the reference: two [nW,k,k]
+    masks and two pair sorts); the blocks run through their own forward with the model's shift_size.  No sampler, so no side streams."""
+    attn0 = self.blocks[0].attn
+    if not (feats.is_cuda and attn0.rel_query and attn0.rel_key and attn0.rel_value):
+        return _original(self)(self, feats, xyz, offset)
+    h, d = _heads_dim(attn0)
+    N = xyz.shape[0]
+    L = int(attn0.relative_pos_query_table.shape[0])
+    even, odd, _ = index_build.swin_stage_index_hip(xyz.float().contiguous(), offset.int().contiguous(), float(self.window_size), float(attn0.quant_size),
+                                                    cell_table_rows=L if d == 16 and L <= 80 else None,
+                                                    cell_max_queries=index_build.cell_query_cap(N, h))
+    shift_size = 1 / 2 * torch.tensor([self.window_size] * 3).type_as(xyz).to(xyz.device)   # :234,261
+    for i, blk in enumerate(self.blocks):                                                 # :282-289
+        bi = even if i % 2 == 0 else odd
+        blk.attn._sta_block = bi
+        try:
+            feats = blk(feats, xyz, bi.index_0, bi.offsets, bi.n_max, bi.index_1, 0.0 if i % 2 == 0 else shift_size)
+        finally:
+            blk.attn._sta_block = None
+    if self.downsample:                                                                   # :291-294
+        feats_down, xyz_down, offset_down = self.downsample(feats, xyz, offset)
+    else:
+        feats_down, xyz_down, offset_down = None, None, None
+    return feats, xyz, offset, feats_down, xyz_down, offset_down
+
+
+def _patch(pairs):
     done = []
-    for cls, fn in ((basic_layer_cls, basic_layer_forward), (window_attention_cls, window_attention_forward),
-                    (transition_down_cls, transition_down_forward)):
+    for cls, fn in pairs:
         if cls is None:
             continue
         if (cls, "forward") not in _ORIGINAL:
@@ -380,6 +429,33 @@ def patch_classes(basic_layer_cls=None, window_attention_cls=None, transition_do
         cls.forward = fn
         done.append(cls)
     return done
+
+
+def patch_swin_classes(basic_layer_cls=None, window_attention_cls=None, transition_down_cls=None):
+    """patch_classes for classes with the attribute names and call conventions of model/swin3d_transformer.py (its TransitionDown is
+    the Stratified one); uninstall_fast_layers() restores them too."""
+    return _patch(((basic_layer_cls, swin_basic_layer_forward), (window_attention_cls, swin_window_attention_forward),
+                   (transition_down_cls, transition_down_forward)))
+
+
+def install_swin_layers(module=None):
+    """Patches BasicLayer / WindowAttention / TransitionDown of the reference's Swin3D model module: the imported module (or a list);
+    default `model.swin3d_transformer`, which must be importable (see install_fast_layers)."""
+    import importlib
+    if module is None:
+        mods = [importlib.import_module("model.swin3d_transformer")]
+    else:
+        mods = list(module) if isinstance(module, (list, tuple)) else [module]
+    done = []
+    for m in mods:
+        done += patch_swin_classes(getattr(m, "BasicLayer", None), getattr(m, "WindowAttention", None), getattr(m, "TransitionDown", None))
+    return done
+
+
+def patch_classes(basic_layer_cls=None, window_attention_cls=None, transition_down_cls=None):
+    """Rebinds `forward` on the given classes (any classes with the reference's attribute names); returns what was patched."""
+    return _patch(((basic_layer_cls, basic_layer_forward), (window_attention_cls, window_attention_forward),
+                   (transition_down_cls, transition_down_forward)))
 
 
 def install_fast_layers(module=None):
