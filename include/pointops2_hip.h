@@ -40,7 +40,8 @@ void *pointops2_get_stream(void);
 const char *pointops2_last_error(void);
 /* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
- * version 5, the grouped_max_*_launcher pair after them - a caller that needs them looks the symbols up. */
+ * version 5, the grouped_max_*_launcher pair and the five pointops2_dbscan_*_launcher after them - a caller that needs them looks
+ * the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -447,6 +448,37 @@ void grouped_max_forward_launcher(int m, int n_s, int k, int c, int row_type, co
                                   unsigned char *arg);
 void grouped_max_backward_launcher(int m, int n_s, int k, int c, int row_type, const void *grad_out, const unsigned char *arg,
                                    const int *src_offsets, const int *src_pair, void *grad_feat);
+
+/* ---- DBSCAN: the clustering behind the model (util/train_utils.py:549-566 runs sklearn.cluster.DBSCAN per predicted class) ----
+ * Neighbours: same group and d2 <= eps2[group], in fp32 with d2 = ((dx*dx) + (dy*dy)) + (dz*dz), dx = xi - xj, no fused operation; a
+ * point is its own neighbour.  Core: at least min_samples[group] neighbours.  Clusters: the connected components of the core points,
+ * numbered per group by ascending smallest core index; a non-core point takes the smallest cluster number among its core neighbours
+ * or -1.  The five steps, in order (stratified_transformer_amd/cluster.py drives them and owns every buffer):
+ *   keys:    keys[i] = ((group * nz + cz) * ny + cy) * nx + cx with c? = clamp(floor((x - o?) / cell), 0, n? - 1) taken in double; a
+ *            point whose group is outside [0, n_groups) gets INT64_MAX.  cell must exceed every eps by enough that two points the
+ *            fp32 test accepts are at most one cell apart (cluster.py: max eps * (1 + 2^-7)); n_groups * nx * ny * nz < 4e18.
+ *   prepare: from the caller's ascending sort of the keys (sorted_keys, order: int64 [n]; n_valid = points inside a group, which sort
+ *            first): pts [n_valid] = {x, y, z, original index as bits} (16-byte aligned), sorted_group [n_valid], ranges [18, n_valid]
+ *            = begin / end in sorted positions of the nine (dy, dz) rows of three x-adjacent cells around every point.
+ *   core:    sorted_core [n_valid] and, by original index, core [n] (1 / 0) and parent [n] = own index for a core point, else -1.
+ *            Entries of points outside every group are not written: the caller presets core = 0 and parent = -1.
+ *   round:   one hook (atomicMin of the smaller label onto parent[larger label], over every core-core neighbour pair whose labels
+ *            differ) and one full pointer jump; *changed (device int) = 1 when a hook happened, else 0.  The caller repeats rounds
+ *            until it reads 0 and bounds their number; at that point parent[i] is the smallest core index of i's component.
+ *   label:   labels[i] for the n_valid points from cluster_of_root [n] (the cluster number of every root index, -1 elsewhere, which
+ *            the caller ranks from parent); entries of points outside every group are not written (preset -1).
+ * No kernel waits on another thread; ranges and indices are clamped / skipped, never followed outside the arrays.  n = 0 or
+ * n_valid = 0 launches nothing. */
+void pointops2_dbscan_keys_launcher(int n, int n_groups, const float *xyz, const int *group, double ox, double oy, double oz, double cell,
+                                    int nx, int ny, int nz, long long *keys);
+void pointops2_dbscan_prepare_launcher(int n, int n_valid, int nx, int ny, int nz, const float *xyz, const long long *sorted_keys,
+                                       const long long *order, float *pts, int *sorted_group, int *ranges);
+void pointops2_dbscan_core_launcher(int n, int n_valid, const float *pts, const int *sorted_group, const int *ranges, const float *eps2,
+                                    const int *min_samples, unsigned char *sorted_core, unsigned char *core, int *parent);
+void pointops2_dbscan_round_launcher(int n, int n_valid, const float *pts, const int *sorted_group, const int *ranges, const float *eps2,
+                                     const unsigned char *sorted_core, int *parent, int *changed);
+void pointops2_dbscan_label_launcher(int n, int n_valid, const float *pts, const int *sorted_group, const int *ranges, const float *eps2,
+                                     const unsigned char *sorted_core, const int *parent, const int *cluster_of_root, int *labels);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libpointops2_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 _lib = None
 
-I, U, P, Z, F = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float
+I, U, P, Z, F, D = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
 
 
 class LaunchOpts(ctypes.Structure):
@@ -99,6 +99,11 @@ SIGNATURES = {
     "kpconv_aggregate_backward_launcher": [I, I, I, I, I, P, P, P, P, F, P, P],
     "grouped_max_forward_launcher": [I, I, I, I, I, P, P, P, P],
     "grouped_max_backward_launcher": [I, I, I, I, I, P, P, P, P, P],
+    "pointops2_dbscan_keys_launcher": [I, I, P, P, D, D, D, D, I, I, I, P],
+    "pointops2_dbscan_prepare_launcher": [I, I, I, I, I, P, P, P, P, P, P],
+    "pointops2_dbscan_core_launcher": [I, I, P, P, P, P, P, P, P, P],
+    "pointops2_dbscan_round_launcher": [I, I, P, P, P, P, P, P, P],
+    "pointops2_dbscan_label_launcher": [I, I, P, P, P, P, P, P, P, P],
 }
 # entry points with a non-void result
 RESULTS = {
