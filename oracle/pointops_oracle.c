@@ -126,8 +126,9 @@ void oracle_furthestsampling(int b, int n, const float *xyz, const int *offset,
 }
 
 /* ------------------------------------------------------------------------------------------
- * knnquery: knnquery_cuda_kernel.cu:21-108.  Max-heap of size nsample (<=100), candidates
- * visited in index order with strict '<' against the heap top (:96), reheap (:21-37),
+ * knnquery: knnquery_cuda_kernel.cu:21-108.  Max-heap of size nsample (<=100 in the reference;
+ * <=101 here, so that a test can look at the (k+1)-th best of k = 100), candidates visited in
+ * index order with strict '<' against the heap top (:96), reheap (:21-37),
  * heap_sort ascending (:40-49).  dist2 holds SQUARED distances (sqrt is applied by the
  * Python wrapper, pointops.py:47).
  * ---------------------------------------------------------------------------------------- */
@@ -158,8 +159,8 @@ void oracle_knnquery(int m, int nsample, const float *xyz, const float *new_xyz,
         int start = bt == 0 ? 0 : offset[bt - 1];
         int end = offset[bt];
         float nx = new_xyz[pt * 3 + 0], ny = new_xyz[pt * 3 + 1], nz = new_xyz[pt * 3 + 2];
-        float best_dist[100];
-        int best_idx[100];
+        float best_dist[101]; /* the reference holds 100; one more lets a test look at the (k+1)-th best of k = 100 */
+        int best_idx[101];
         for (int i = 0; i < nsample; i++) { best_dist[i] = 1e10f; best_idx[i] = start; }
         for (int i = start; i < end; i++) {
             float x = xyz[i * 3 + 0], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];

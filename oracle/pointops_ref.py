@@ -85,6 +85,7 @@ def knnquery(nsample, xyz, new_xyz, offset, new_offset):
     new_xyz = xyz if new_xyz is None else _f(new_xyz)
     offset, new_offset = _i(offset), _i(new_offset)
     m = new_xyz.shape[0]
+    assert 1 <= nsample <= 101, nsample  # the native heap holds 101 entries (the reference's limit is 100)
     idx = np.zeros((m, nsample), dtype=np.int32)
     dist2 = np.zeros((m, nsample), dtype=np.float32)
     lib().oracle_knnquery(m, nsample, _p(xyz), _p(new_xyz), _p(offset), _p(new_offset), _p(idx), _p(dist2))
