@@ -40,8 +40,8 @@ void *pointops2_get_stream(void);
 const char *pointops2_last_error(void);
 /* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
- * version 5, the grouped_max_*_launcher pair and the five pointops2_dbscan_*_launcher after them - a caller that needs them looks
- * the symbols up. */
+ * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher and the pointops2_evaltile_* entry points after
+ * them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -479,6 +479,34 @@ void pointops2_dbscan_round_launcher(int n, int n_valid, const float *pts, const
                                      const unsigned char *sorted_core, int *parent, int *changed);
 void pointops2_dbscan_label_launcher(int n, int n_valid, const float *pts, const int *sorted_group, const int *ranges, const float *eps2,
                                      const unsigned char *sorted_core, const int *parent, const int *cluster_of_root, int *labels);
+
+/* ---- Whole-scene evaluation: the crop cover and the vote of the reference's test loop (test_backup.py:238-251, :278-281) ----
+ * One crop of a part of n points (stratified_transformer_amd/evaluate.py drives the loop and owns every buffer):
+ *   seed_dist: seed = argmin(priority) (float64 [n], non-negative; the LOWEST index among equal values; 0 when every value is a NaN),
+ *              found on the device - per-workgroup (value, index) pairs in part_value / part_index (pointops2_evaltile_max_parts()
+ *              entries each), reduced again by every workgroup of the distance kernel - and written to *seed (device int64); then
+ *              dist[i] = sum over the three axes, left to right, of (coord[i] - coord[seed])^2 in the coordinates' own precision
+ *              (is_f64: coord / dist are double arrays, else float), exactly as pointops2_crop_dist_launcher evaluates it.
+ *   update:    for crop [voxel_max] int64 (the caller's first voxel_max entries of the stable ascending sort of dist; distinct):
+ *              dmax = dist[crop[voxel_max-1]]; priority[crop[j]] += (double)((1 - dist[crop[j]] / dmax)^2), the three operations rounded
+ *              one by one in the coordinates' precision; covered[crop[j]] = 1; report[0] += the points newly covered.  When dmax is
+ *              not positive (voxel_max points coincide with the seed: the reference divides 0 / 0 and never ends) report[1] = 1 and
+ *              NOTHING else is written; an entry of crop outside [0, n) sets report[1] = 2 and is skipped.  report: two device ints the
+ *              caller zeroes before the first crop and reads after every crop.
+ * Vote: pred[idx[r], :] += softmax(logits[r, :]) for the m rows of one call (logits [m, classes] of row_type POINTOPS2_ROWS_F32, _F16
+ * or _BF16, arithmetic fp32, max-subtracted; idx int64 [m]; pred fp32 [n_points, classes]).  When an index repeats inside the call only
+ * the row at the LAST position writes (the reference's indexed assignment, as CPU torch evaluates it): stamp (int32 [n_points], preset
+ * -1 by the caller) takes the largest row number per point and is back at -1 when the call has run.  An index outside [0, n_points)
+ * sets status[0] = 2 (device int) and its row is skipped.  Bitwise reproducible; no [m, classes] temporary.  m = 0 is a no-op.
+ * n < 1, voxel_max outside [1, n], n_points < 1, classes outside [1, 64], an unknown row_type or a NULL array record an error and
+ * launch nothing.  No kernel waits on another workgroup; no index is followed outside its array. */
+int pointops2_evaltile_max_parts(void);
+void pointops2_evaltile_seed_dist_launcher(int n, int is_f64, const void *coord, const double *priority, double *part_value, int *part_index,
+                                           long long *seed, void *dist);
+void pointops2_evaltile_update_launcher(int n, int voxel_max, int is_f64, const void *dist, const long long *crop, double *priority,
+                                        unsigned char *covered, int *report);
+void pointops2_evaltile_vote_launcher(int m, int classes, int n_points, int row_type, const void *logits, const long long *idx, int *stamp,
+                                      float *pred, int *status);
 
 #ifdef __cplusplus
 }

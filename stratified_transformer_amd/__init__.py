@@ -6,6 +6,7 @@ windowed sparse-attention hot path, behind the reference's own o
     stratified_transformer_amd.compat          providers of the third-party names the model imports
                                                (torch_scatter.scatter_softmax, torch_geometric.nn.voxel_grid, ...)
     stratified_transformer_amd.cluster         the step behind the model: dbscan / instances on csrc/dbscan.hip (also exported here)
+    stratified_transformer_amd.evaluate        whole-scene evaluation on csrc/evaltile.hip: crop cover, votes, IoU (scene_eval also exported here)
     stratified_transformer_amd.layers          installable fast BasicLayer.forward / WindowAttention.forward (same signatures)
     include/pointops2_hip.h                    the C ABI underneath (libpointops2_hip.so)
 
@@ -14,7 +15,7 @@ model/stratified_transformer.py imports and runs unmodified under PyTorch-ROCm.
 """
 import sys
 
-__all__ = ["install", "build", "dbscan", "instances"]
+__all__ = ["install", "build", "dbscan", "instances", "scene_eval"]
 
 
 def __getattr__(name):
@@ -22,6 +23,9 @@ def __getattr__(name):
     if name in ("dbscan", "instances"):
         from . import cluster
         return getattr(cluster, name)
+    if name == "scene_eval":
+        from . import evaluate
+        return evaluate.scene_eval
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -104,6 +104,9 @@ SIGNATURES = {
     "pointops2_dbscan_core_launcher": [I, I, P, P, P, P, P, P, P, P],
     "pointops2_dbscan_round_launcher": [I, I, P, P, P, P, P, P, P],
     "pointops2_dbscan_label_launcher": [I, I, P, P, P, P, P, P, P, P],
+    "pointops2_evaltile_seed_dist_launcher": [I, I, P, P, P, P, P, P],
+    "pointops2_evaltile_update_launcher": [I, I, I, P, P, P, P, P],
+    "pointops2_evaltile_vote_launcher": [I, I, I, I, P, P, P, P, P],
 }
 # entry points with a non-void result
 RESULTS = {
@@ -118,6 +121,7 @@ RESULTS = {
     "pointops2_row_order_workspace_bytes": ([I], Z),
     "pointops2_cell_plan_workspace_bytes": ([I], Z),
     "pointops2_cell_forward_variant": ([P, I, I, I, I], I),
+    "pointops2_evaltile_max_parts": ([], I),
 }
 
 # codes of pointops2_cell_forward_variant (POINTOPS2_CELL_FWD_* of include/pointops2_hip.h): the forward kernel a cell launch runs

@@ -1,0 +1,245 @@
+// Whole-scene evaluation on the device: the crop cover and the vote of the reference's test loop (test_backup.py:238-251, :278-281).
+//
+// Crop cover of one part (n points, crops of voxel_max): per crop
+//   seed  = argmin(priority)                      float64, the LOWEST index among equal values          (:241)
+//   dist  = sum((coord - coord[seed])^2)          the coordinates' own type, left to right              (:242)
+//   crop  = first voxel_max of the stable ascending sort of dist (the caller's torch sort, as dataprep.crop_nearest) (:243)
+//   delta = (1 - dist[crop] / dmax)^2             dmax = dist[crop[-1]]; divide, subtract, multiply - each rounded on its own,
+//   priority[crop] += (double)delta               the library is built with -ffp-contract=off             (:245-247)
+// and the crop's points are marked covered (:250 keeps np.unique of everything seen so far; only its size is ever used).
+// The seed never leaves the device: argmin_partial_kernel leaves one (value, index) pair per workgroup, and every workgroup of
+// seed_dist_kernel reduces those pairs again in its prologue (at most ET_MAX_PARTS pairs: four per thread) - the kernel boundary
+// between the two is the only ordering needed, no kernel waits on another workgroup.  update_kernel reports through two words
+// that the host reads once per crop: the number of covered points so far and a status.
+//
+// Vote (:278, :281): pred[idx, :] += softmax(logits, -1) is an indexed assignment - when an index repeats inside one call only ONE
+// row writes.  Here, as in CPU torch, it is the row at the last position: vote_stamp_kernel takes the maximum row number per
+// point (integer atomicMax, order-independent), vote_add_kernel lets row r write when stamp[idx[r]] == r and resets the stamp to
+// -1 for the next call.  (A losing row reads either the winner's number or -1: neither is its own.)  A row is spread over LPR
+// lanes of one wave, one class per lane: the max and the sum are xor butterflies, so the result does not depend on the launch.
+#include <hip/hip_fp16.h>
+#include "common.h"
+
+namespace p2 {
+namespace {
+
+constexpr int ET_BLOCK = 256;
+constexpr int ET_WAVES = ET_BLOCK / WAVE;
+constexpr int ET_MAX_PARTS = 1024;        // workgroups of argmin_partial_kernel = pairs the prologue of seed_dist_kernel reduces
+constexpr int ET_POINTS_PER_PART = 1024;  // points per workgroup before the grid stops growing and the threads stride
+constexpr int ET_NO_INDEX = 0x7fffffff;
+
+constexpr int ET_STATUS_DMAX_ZERO = 1;    // update: dist[crop[-1]] is not positive - voxel_max points coincide with the seed
+constexpr int ET_STATUS_BAD_INDEX = 2;    // update: an entry of crop is outside [0, n); vote: an entry of idx is outside [0, n_points)
+
+inline int argmin_parts(int n) { return min(div_up(n, ET_POINTS_PER_PART), ET_MAX_PARTS); }
+
+// (v, i) orders before (bv, bi): np.argmin's order on non-negative values - smaller value, then smaller index.  A NaN never wins.
+__device__ __forceinline__ bool before(double v, int i, double bv, int bi) { return v < bv || (v == bv && i < bi); }
+
+// the best pair of the workgroup, in every thread; `slots` holds one pair per wave
+__device__ __forceinline__ void block_best(double &v, int &i, double *slot_v, int *slot_i) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double ov = __shfl_xor(v, s, WAVE);
+        const int oi = __shfl_xor(i, s, WAVE);
+        if (before(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    if (lane_id() == 0) { slot_v[threadIdx.x / WAVE] = v; slot_i[threadIdx.x / WAVE] = i; }
+    __syncthreads();
+    v = slot_v[0];
+    i = slot_i[0];
+#pragma unroll
+    for (int w = 1; w < ET_WAVES; w++)
+        if (before(slot_v[w], slot_i[w], v, i)) { v = slot_v[w]; i = slot_i[w]; }
+}
+
+__global__ __launch_bounds__(ET_BLOCK) void argmin_partial_kernel(int n, const double *__restrict__ priority, double *__restrict__ part_v,
+                                                                  int *__restrict__ part_i) {
+    __shared__ double slot_v[ET_WAVES];
+    __shared__ int slot_i[ET_WAVES];
+    double v = INFINITY;
+    int i = ET_NO_INDEX;
+    for (int p = blockIdx.x * ET_BLOCK + threadIdx.x; p < n; p += gridDim.x * ET_BLOCK) {
+        const double pv = priority[p];
+        if (before(pv, p, v, i)) { v = pv; i = p; }
+    }
+    block_best(v, i, slot_v, slot_i);
+    if (threadIdx.x == 0) { part_v[blockIdx.x] = v; part_i[blockIdx.x] = i; }
+}
+
+template <typename T>
+__global__ __launch_bounds__(ET_BLOCK) void seed_dist_kernel(int n, int n_parts, const T *__restrict__ coord, const double *__restrict__ part_v,
+                                                             const int *__restrict__ part_i, long long *__restrict__ seed_out,
+                                                             T *__restrict__ dist) {
+    __shared__ double slot_v[ET_WAVES];
+    __shared__ int slot_i[ET_WAVES];
+    __shared__ T rows[ET_BLOCK * 3];
+    // the workgroup's 3-value rows, read as one contiguous run (a thread reading its own row strides the wave's loads by 12 / 24 bytes)
+    const int base = blockIdx.x * ET_BLOCK, count = min(ET_BLOCK, n - base);
+    for (int k = threadIdx.x; k < count * 3; k += ET_BLOCK) rows[k] = coord[(size_t)base * 3 + k];
+
+    double v = INFINITY;
+    int seed = ET_NO_INDEX;
+    for (int p = threadIdx.x; p < n_parts; p += ET_BLOCK)
+        if (before(part_v[p], part_i[p], v, seed)) { v = part_v[p]; seed = part_i[p]; }
+    block_best(v, seed, slot_v, slot_i);  // (its barrier also publishes rows[])
+    if ((unsigned)seed >= (unsigned)n) seed = 0;  // every priority a NaN: np.argmin answers 0
+    if (blockIdx.x == 0 && threadIdx.x == 0) seed_out[0] = seed;
+
+    if (threadIdx.x >= count) return;
+    T s = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {  // np.sum(np.power(coord - coord[init_idx], 2), 1): left to right, as crop_dist_kernel
+        const T d = rows[threadIdx.x * 3 + a] - coord[(size_t)seed * 3 + a];
+        const T sq = d * d;
+        s = a == 0 ? sq : s + sq;
+    }
+    dist[base + threadIdx.x] = s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(ET_BLOCK) void update_kernel(int n, int voxel_max, const T *__restrict__ dist, const long long *__restrict__ crop,
+                                                          double *__restrict__ priority, unsigned char *__restrict__ covered,
+                                                          int *__restrict__ report) {
+    __shared__ int wave_new[ET_WAVES];
+    const int j = blockIdx.x * ET_BLOCK + threadIdx.x;
+    const long long last = crop[voxel_max - 1];
+    if (last < 0 || last >= n) {  // (the same for every thread of the grid, as the next test: whole workgroups leave)
+        if (j == 0) report[1] = ET_STATUS_BAD_INDEX;
+        return;
+    }
+    const T dmax = dist[last];
+    if (!(dmax > (T)0)) {
+        if (j == 0) report[1] = ET_STATUS_DMAX_ZERO;
+        return;
+    }
+    bool fresh = false;
+    if (j < voxel_max) {
+        const long long i = crop[j];
+        if (i >= 0 && i < n) {
+            const T q = dist[i] / dmax;  // np.square(1 - dist / np.max(dist)): three operations in the coordinates' type
+            const T t = (T)1 - q;
+            const T delta = t * t;
+            priority[i] += (double)delta;  // the entries of a crop are distinct: no atomics
+            fresh = covered[i] == 0;
+            if (fresh) covered[i] = 1;
+        } else {
+            report[1] = ET_STATUS_BAD_INDEX;
+        }
+    }
+    const int in_wave = __popcll(__ballot(fresh));
+    if (lane_id() == 0) wave_new[threadIdx.x / WAVE] = in_wave;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < ET_WAVES; w++) total += wave_new[w];
+        if (total > 0) atomicAdd(&report[0], total);
+    }
+}
+
+__global__ __launch_bounds__(ET_BLOCK) void vote_stamp_kernel(int m, int n_points, const long long *__restrict__ idx, int *stamp,
+                                                              int *__restrict__ status) {
+    const int r = blockIdx.x * ET_BLOCK + threadIdx.x;
+    if (r >= m) return;
+    const long long i = idx[r];
+    if (i < 0 || i >= n_points) { status[0] = ET_STATUS_BAD_INDEX; return; }
+    atomicMax(&stamp[i], r);
+}
+
+__device__ __forceinline__ float logit_value(const float *p, size_t k) { return p[k]; }
+__device__ __forceinline__ float logit_value(const __half *p, size_t k) { return __half2float(p[k]); }
+__device__ __forceinline__ float logit_value(const unsigned short *p, size_t k) { return __uint_as_float((unsigned)p[k] << 16); }  // bf16
+
+// LPR lanes per row (a power of two >= classes), ET_BLOCK / LPR rows per workgroup
+template <int LPR, typename T>
+__global__ __launch_bounds__(ET_BLOCK) void vote_add_kernel(int m, int classes, int n_points, const T *__restrict__ logits,
+                                                            const long long *__restrict__ idx, int *stamp, float *__restrict__ pred) {
+    const int r = blockIdx.x * (ET_BLOCK / LPR) + threadIdx.x / LPR, c = threadIdx.x % LPR;
+    long long i = -1;
+    if (r < m) i = idx[r];
+    const bool writer = i >= 0 && i < n_points && stamp[i] == r;
+    const bool active = writer && c < classes;
+    float x = active ? logit_value(logits, (size_t)r * classes + c) : -INFINITY;
+    float mx = x;
+#pragma unroll
+    for (int s = 1; s < LPR; s <<= 1) mx = fmaxf(mx, __shfl_xor(mx, s, WAVE));
+    const float e = active ? expf(x - mx) : 0.0f;
+    float sum = e;
+#pragma unroll
+    for (int s = 1; s < LPR; s <<= 1) sum += __shfl_xor(sum, s, WAVE);
+    if (active) pred[(size_t)i * classes + c] += e / sum;
+    if (writer && c == 0) stamp[i] = -1;
+}
+
+template <typename T>
+void launch_vote_add(hipStream_t st, int m, int classes, int n_points, const void *logits, const long long *idx, int *stamp, float *pred) {
+    const T *lg = (const T *)logits;
+    if (classes <= 8)
+        hipLaunchKernelGGL((vote_add_kernel<8, T>), dim3(div_up(m, ET_BLOCK / 8)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
+    else if (classes <= 16)
+        hipLaunchKernelGGL((vote_add_kernel<16, T>), dim3(div_up(m, ET_BLOCK / 16)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
+    else if (classes <= 32)
+        hipLaunchKernelGGL((vote_add_kernel<32, T>), dim3(div_up(m, ET_BLOCK / 32)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
+    else
+        hipLaunchKernelGGL((vote_add_kernel<64, T>), dim3(div_up(m, ET_BLOCK / 64)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
+}
+
+}  // namespace
+}  // namespace p2
+
+using namespace p2;
+
+extern "C" {
+
+int pointops2_evaltile_max_parts(void) { return ET_MAX_PARTS; }
+
+void pointops2_evaltile_seed_dist_launcher(int n, int is_f64, const void *coord, const double *priority, double *part_value, int *part_index,
+                                           long long *seed, void *dist) {
+    const hipStream_t st = begin_launch().stream;
+    if (n <= 0) { set_error("evaltile_seed_dist: need n >= 1"); return; }
+    if (!coord || !priority || !part_value || !part_index || !seed || !dist) { set_error("evaltile_seed_dist: a NULL array"); return; }
+    const int parts = argmin_parts(n);
+    hipLaunchKernelGGL(argmin_partial_kernel, dim3(parts), dim3(ET_BLOCK), 0, st, n, priority, part_value, part_index);
+    if (is_f64)
+        hipLaunchKernelGGL(seed_dist_kernel<double>, dim3(div_up(n, ET_BLOCK)), dim3(ET_BLOCK), 0, st, n, parts, (const double *)coord, part_value,
+                           part_index, seed, (double *)dist);
+    else
+        hipLaunchKernelGGL(seed_dist_kernel<float>, dim3(div_up(n, ET_BLOCK)), dim3(ET_BLOCK), 0, st, n, parts, (const float *)coord, part_value,
+                           part_index, seed, (float *)dist);
+    check_launch();
+}
+
+void pointops2_evaltile_update_launcher(int n, int voxel_max, int is_f64, const void *dist, const long long *crop, double *priority,
+                                        unsigned char *covered, int *report) {
+    const hipStream_t st = begin_launch().stream;
+    if (n <= 0 || voxel_max < 1 || voxel_max > n) { set_error("evaltile_update: need 1 <= voxel_max <= n"); return; }
+    if (!dist || !crop || !priority || !covered || !report) { set_error("evaltile_update: a NULL array"); return; }
+    if (is_f64)
+        hipLaunchKernelGGL(update_kernel<double>, dim3(div_up(voxel_max, ET_BLOCK)), dim3(ET_BLOCK), 0, st, n, voxel_max, (const double *)dist, crop,
+                           priority, covered, report);
+    else
+        hipLaunchKernelGGL(update_kernel<float>, dim3(div_up(voxel_max, ET_BLOCK)), dim3(ET_BLOCK), 0, st, n, voxel_max, (const float *)dist, crop,
+                           priority, covered, report);
+    check_launch();
+}
+
+void pointops2_evaltile_vote_launcher(int m, int classes, int n_points, int row_type, const void *logits, const long long *idx, int *stamp,
+                                      float *pred, int *status) {
+    const hipStream_t st = begin_launch().stream;
+    if (m < 0 || n_points < 1 || classes < 1 || classes > 64) { set_error("evaltile_vote: need m >= 0, n_points >= 1 and 1 <= classes <= 64"); return; }
+    if (row_type != POINTOPS2_ROWS_F32 && row_type != POINTOPS2_ROWS_F16 && row_type != POINTOPS2_ROWS_BF16) {
+        set_error("evaltile_vote: row_type must be POINTOPS2_ROWS_F32, _F16 or _BF16");
+        return;
+    }
+    if (m == 0) return;
+    if (!logits || !idx || !stamp || !pred || !status) { set_error("evaltile_vote: a NULL array"); return; }
+    hipLaunchKernelGGL(vote_stamp_kernel, dim3(div_up(m, ET_BLOCK)), dim3(ET_BLOCK), 0, st, m, n_points, idx, stamp, status);
+    if (row_type == POINTOPS2_ROWS_F32) launch_vote_add<float>(st, m, classes, n_points, logits, idx, stamp, pred);
+    else if (row_type == POINTOPS2_ROWS_F16) launch_vote_add<__half>(st, m, classes, n_points, logits, idx, stamp, pred);
+    else launch_vote_add<unsigned short>(st, m, classes, n_points, logits, idx, stamp, pred);
+    check_launch();
+}
+
+}  // extern "C"
