@@ -40,8 +40,8 @@ void *pointops2_get_stream(void);
 const char *pointops2_last_error(void);
 /* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
- * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher and the pointops2_evaltile_* entry points after
- * them - a caller that needs them looks the symbols up. */
+ * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points and the two
+ * pointops2_contacts_*_launcher after them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -479,6 +479,27 @@ void pointops2_dbscan_round_launcher(int n, int n_valid, const float *pts, const
                                      const unsigned char *sorted_core, int *parent, int *changed);
 void pointops2_dbscan_label_launcher(int n, int n_valid, const float *pts, const int *sorted_group, const int *ranges, const float *eps2,
                                      const unsigned char *sorted_core, const int *parent, const int *cluster_of_root, int *labels);
+
+/* ---- Contacts between labelled point sets: the distance primitive of the grouping behind the clustering (util/train_utils.py:595-714
+ * runs one dense cdist per (edge instance, face instance) pair; :251-261 and test.py:311 ask the same with other thresholds) ----
+ * Over the points with a label in [0, n_labels), in fp32 with d2 = ((dx*dx) + (dy*dy)) + (dz*dz), dx = xp - xq, no fused operation:
+ *   count [n_labels, n_labels] (int): count[a, b] = points p of label a for which some q of label b has d2(p, q) < r2 (strict; once per
+ *            b however many q are near; p is its own partner, so the diagonal holds the sizes).  The caller zeroes it.
+ *   min_d2 [n_labels, n_labels] (float): min over p in a, q in b of d2(p, q).  The caller presets +inf, which an empty label keeps.
+ * The two steps are independent (stratified_transformer_amd/cluster.py drives them and owns every buffer):
+ *   count: behind pointops2_dbscan_keys_launcher / _prepare_launcher run with ONE group (group 0 = labelled, -1 = not) and a cell of
+ *          at least r * (1 + 2^-7): pts and ranges as prepare wrote them, sorted_label [n_valid] = the labels in the same sorted order.
+ *          One thread per point walks its nine runs and marks the labels in reach in its own row of bitmap [n_valid, ceil(n_labels / 32)]
+ *          (unsigned, zeroed by the caller; not read or written, and may be NULL, for n_labels <= 64: the row stays in registers), then
+ *          adds its marks to count with integer atomics.
+ *   min:   label_pts [n_valid] = {x, y, z, label as bits} (16-byte aligned) in ASCENDING label order; a tiled sweep over all pairs,
+ *          atomicMin on the bit pattern of the non-negative float.  Quadratic in n_valid: callers that need count alone skip it.
+ * Both tables are independent of the order in which threads run.  No kernel waits on another workgroup; ranges are clamped and labels
+ * outside [0, n_labels) skipped, never followed outside the tables.  n_valid = 0 or n_labels = 0 launches nothing;
+ * n_labels * n_labels >= 2^31 records an error. */
+void pointops2_contacts_count_launcher(int n_valid, int n_labels, const float *pts, const int *sorted_label, const int *ranges, float r2,
+                                       unsigned *bitmap, int *count);
+void pointops2_contacts_min_launcher(int n_valid, int n_labels, const float *label_pts, float *min_d2);
 
 /* ---- Whole-scene evaluation: the crop cover and the vote of the reference's test loop (test_backup.py:238-251, :278-281) ----
  * One crop of a part of n points (stratified_transformer_amd/evaluate.py drives the loop and owns every buffer):

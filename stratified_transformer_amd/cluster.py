@@ -10,6 +10,11 @@ Semantics (scikit-learn's, pinned by tests/golden/dbscan_sklearn.npz):
   4. a non-core point with a core neighbour takes the smallest cluster number among its core neighbours, every other point gets -1.
 Distances are evaluated in fp32 as ((dx*dx) + (dy*dy)) + (dz*dz) <= eps*eps (scikit-learn: float64), so a pair whose distance is within
 about 1e-6 of eps may fall on the other side; everything else is equal label for label.
+
+The second half of `instantiation_eval` (util/train_utils.py:595-714: which face instances an edge instance links, merged into objects)
+is `objects`, on `contacts` (csrc/contacts.hip): per pair of labels, how many points of one set have a point of the other within a
+radius, and how close the two sets come - the question the fork also asks at :251-261 and test.py:311.  `link_objects` is the pairing
+and merging on plain host arrays.  scipy is not needed (and not imported).
 """
 import ctypes
 
@@ -244,3 +249,243 @@ def instances(coord, shift, pred, eps=None, min_samples=None, min_points=None):
     number = torch.where(keep, number, torch.full_like(number, -1))
     instance = torch.where(in_cluster, number[flat], torch.full_like(flat, -1)).to(torch.int32)
     return instance, cluster_class[keep].to(torch.int32), size[keep].to(torch.int32)
+
+
+# ---- contacts between labelled point sets, and the grouping of face instances into objects built on them (csrc/contacts.hip) ----
+MAX_BITMAP_BYTES = 1 << 30  # of the [n_valid, ceil(I / 32)] rows of labels in reach (more than 64 labels)
+MAX_LABELS = 1 << 15        # the two [I, I] tables are indexed with ints
+REG_LABELS = 64             # csrc/contacts.hip keeps rows of up to this many labels in registers: no bitmap
+# instantiation_eval's settings (util/train_utils.py:600, :629-631): the two face classes beside edge class 6 + c
+EDGE_FACES = ((0, 1), (0, 2), (1, 2), (0, 3), (1, 3), (0, 4), (2, 4), (3, 4), (1, 5), (2, 5), (3, 5), (4, 5))
+CONTACT_RADIUS = 0.08
+CONTACT_SHARE = 0.5
+LAST_CONTACTS = {"launches": 0, "readbacks": 0}   # of the most recent contacts() / objects() call (tools/bench_contacts.py)
+
+
+def _check_labelled(xyz, label, who):
+    if not getattr(xyz, "is_cuda", False) or not getattr(label, "is_cuda", False):
+        bad = xyz if not getattr(xyz, "is_cuda", False) else label
+        raise RuntimeError(f"{who}: expected GPU tensors (the pointops2 HIP path has no CPU fallback), got {getattr(bad, 'device', type(bad).__name__)}")
+    if label.device != xyz.device:
+        raise RuntimeError(f"{who}: label is on {label.device}, xyz on {xyz.device}")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{who}: xyz must be [N, 3], got {tuple(xyz.shape)}")
+    if xyz.dtype != torch.float32:
+        raise TypeError(f"{who}: xyz must be float32, got {xyz.dtype}")
+    if label.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{who}: label must be int32 / int64, got {label.dtype}")
+    if label.dim() != 1 or label.shape[0] != xyz.shape[0]:
+        raise ValueError(f"{who}: label must be [N] = [{xyz.shape[0]}], got {tuple(label.shape)}")
+
+
+def _positive_finite(value, who, name):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: {name} must be a number, got {type(value).__name__}")
+    if not np.isfinite(value) or not value > 0 or not np.isfinite(np.float32(value)) or not np.float32(value) > 0:
+        raise ValueError(f"{who}: {name} must be finite and > 0, got {value}")
+    return np.float32(value)
+
+
+def _contacts(xyz, label, radius, n_labels, want_min, who):
+    """-> (count int32 [I, I], min_d2 float32 [I, I] or None, I)"""
+    _check_labelled(xyz, label, who)
+    r = _positive_finite(radius, who, "radius")
+    with np.errstate(all="ignore"):
+        if not np.isfinite(r * r) or not r * r > 0:
+            raise ValueError(f"{who}: radius must be finite and > 0 when squared in fp32, got {radius}")
+    if n_labels is not None:
+        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+            raise TypeError(f"{who}: n_labels must be an int, got {type(n_labels).__name__}")
+        if n_labels < 0:
+            raise ValueError(f"{who}: n_labels must be >= 0, got {n_labels}")
+        n_labels = int(n_labels)
+    dev, n = xyz.device, xyz.shape[0]
+    LAST_CONTACTS["launches"], LAST_CONTACTS["readbacks"] = 0, 0
+
+    def tables(i):
+        return (torch.zeros(i, i, dtype=torch.int32, device=dev),
+                torch.full((i, i), float("inf"), dtype=torch.float32, device=dev) if want_min else None, i)
+
+    if n == 0:
+        return tables(n_labels or 0)
+    xyz = xyz.contiguous()
+    label = label.to(torch.int32).contiguous()
+
+    # one read-back up front: the label range, the points that take part and their bounding box
+    member = label >= 0
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
+    lo = torch.where(member[:, None], xyz, inf).amin(0)
+    hi = torch.where(member[:, None], xyz, -inf).amax(0)
+    finite = torch.isfinite(xyz).all()
+    head = torch.cat([label.min()[None].double(), label.max()[None].double(), member.sum()[None].double(), finite[None].double(),
+                      lo.double(), hi.double()]).cpu().numpy()
+    LAST_CONTACTS["readbacks"] += 1
+    l_min, l_max, n_valid, all_finite = int(head[0]), int(head[1]), int(head[2]), bool(head[3])
+    if n_labels is None:
+        n_labels = max(l_max + 1, 0)
+    if l_min < -1 or l_max >= n_labels:
+        raise ValueError(f"{who}: label values must be in -1 .. {n_labels - 1}, got {l_min} .. {l_max}")
+    if not all_finite:
+        raise ValueError(f"{who}: xyz must be finite")
+    words = (n_labels + 31) // 32
+    if n_labels > REG_LABELS and n_valid * words * 4 > MAX_BITMAP_BYTES:
+        raise ValueError(f"{who}: the bitmap of {n_valid} points x {n_labels} labels takes {n_valid * words * 4} bytes, more than {MAX_BITMAP_BYTES}")
+    if n_labels > MAX_LABELS:
+        raise ValueError(f"{who}: {n_labels} labels: the tables hold at most {MAX_LABELS} x {MAX_LABELS} entries")
+    if n_valid == 0 or n_labels == 0:
+        return tables(n_labels)
+    cell = float(r) * CELL_MARGIN
+    origin, top = head[4:7], head[7:10]
+    dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
+    if max(dims) > MAX_CELLS_PER_AXIS or dims[0] * dims[1] * dims[2] >= 2 ** 61:
+        raise ValueError(f"{who}: the cloud spans {dims} cells of edge {cell:g}: too many for the 64-bit cell keys")
+    count, min_d2, _ = tables(n_labels)
+
+    def call(name, *args):
+        LAST_CONTACTS["launches"] += 1
+        if dev.index == torch.cuda.current_device():
+            _lib.call(name, *args, device=dev)
+        else:
+            with torch.cuda.device(dev):
+                _lib.call(name, *args, device=dev)
+
+    group = member.to(torch.int32) - 1                       # one group: 0 for a labelled point, -1 for the others
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    call("pointops2_dbscan_keys_launcher", n, 1, ptr(xyz), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
+         ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
+    skeys, order = torch.sort(keys, stable=True)
+    pts = torch.empty(n_valid, 4, dtype=torch.float32, device=dev)
+    sgroup = torch.empty(n_valid, dtype=torch.int32, device=dev)
+    ranges = torch.empty(18, n_valid, dtype=torch.int32, device=dev)
+    call("pointops2_dbscan_prepare_launcher", n, n_valid, dims[0], dims[1], dims[2], ptr(xyz), ptr(skeys), ptr(order), ptr(pts), ptr(sgroup),
+         ptr(ranges))
+    slabel = label[order[:n_valid]].contiguous()
+    bitmap = torch.zeros(n_valid, words, dtype=torch.int32, device=dev) if n_labels > REG_LABELS else None
+    r2 = np.float32(r * r)                                   # fp32 product, rounded once
+    call("pointops2_contacts_count_launcher", n_valid, n_labels, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(bitmap), ptr(count))
+    if want_min:
+        llabel, by_label = torch.sort(slabel, stable=True)   # ascending label; inside a label the grid's order, which keeps tiles compact
+        label_pts = torch.cat([pts[by_label, :3], llabel.view(torch.float32)[:, None]], 1).contiguous()
+        call("pointops2_contacts_min_launcher", n_valid, n_labels, ptr(label_pts), ptr(min_d2))
+    return count, min_d2, n_labels
+
+
+def contacts(xyz, label, radius, n_labels=None):
+    """Which labelled point sets touch, and how close they come: xyz [N, 3] fp32 and label int32 / int64 [N] in -1 .. I-1 (GPU; -1 = the
+    point takes no part) -> (count int32 [I, I], min_d2 float32 [I, I]) with I = n_labels, or label.max() + 1.
+
+    count[a, b]: the points p of label a for which SOME point q of label b has d2(p, q) < radius^2 - strict, as the reference's
+    `dist < 0.08` (util/train_utils.py:629); p counts once per b however many q are near, and is its own partner, so count[a, a] is the
+    size of a.  count is not symmetric.  min_d2[a, b]: the minimum of d2(p, q) over p in a and q in b (symmetric), +inf where either
+    label is empty.  d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in fp32, dx = xp - xq, compared with fp32(radius) * fp32(radius) rounded once.
+    count comes from a fixed-radius grid walk, min_d2 from a sweep over all pairs: quadratic in the labelled points (csrc/contacts.hip).
+
+    Raises before any launch: RuntimeError for a CPU tensor or mismatched devices; TypeError / ValueError for a wrong dtype or shape,
+    radius <= 0 or non-finite, a label outside -1 .. I-1 or non-finite coordinates; ValueError when the rows of labels in reach
+    (n_valid * ceil(I / 32) * 4 bytes, needed above 64 labels) would exceed MAX_BITMAP_BYTES = 1 GiB, when I > MAX_LABELS, or when the grid
+    exceeds MAX_CELLS_PER_AXIS.  N = 0 or no labelled point: the tables of zeros / +inf, nothing launched."""
+    count, min_d2, _ = _contacts(xyz, label, radius, n_labels, True, "contacts")
+    return count, min_d2
+
+
+def link_objects(count, size, instance_class, share=CONTACT_SHARE, face_classes=FACE_CLASSES, edge_faces=None):
+    """The pairing and merging of `instantiation_eval` (util/train_utils.py:595-714) on plain arrays - no GPU: count [I, I] (contacts),
+    size [I], instance_class [I] (ascending, as instances() numbers them) -> (object_of_instance int32 [I], n_objects).
+
+      1. only the edge classes face_classes + c, c < len(edge_faces), take part; instances of higher classes are ignored;
+      2. an edge class is skipped entirely when either of its two face classes has no instance (:606-607);
+      3. an edge instance e links, for each of its two face classes in turn, the FIRST face instance k of that class in ascending
+         instance number with count[e, k] / size[e] > share (:627-639).  share = 0.5 is decided in integers, 2 * count > size (what the
+         Python float comparison decides for integers below 2^52); another share as count > share * size in float64;
+      4. objects = the connected components over the linked face instances, two faces joined when one edge linked both; a face no edge
+         linked is in no object, an edge that linked a single face makes it an object of its own;
+      5. objects are numbered by ascending smallest face instance number; an edge instance gets the object of its first linked face."""
+    count = np.asarray(count)
+    size = np.asarray(size).astype(np.int64).reshape(-1)
+    cls = np.asarray(instance_class).astype(np.int64).reshape(-1)
+    n_inst = cls.shape[0]
+    if count.shape != (n_inst, n_inst) or size.shape != (n_inst,):
+        raise ValueError(f"objects: count must be [I, I] and size [I] for the {n_inst} instances, got {count.shape} and {size.shape}")
+    if isinstance(share, bool) or not isinstance(share, (int, float, np.integer, np.floating)) or not np.isfinite(share) or share < 0:
+        raise ValueError(f"objects: share must be a finite number >= 0, got {share!r}")
+    edge_faces = EDGE_FACES if edge_faces is None else tuple(tuple(int(f) for f in pair) for pair in edge_faces)
+    face_classes = int(face_classes)
+    if any(len(pair) != 2 or not all(0 <= f < face_classes for f in pair) for pair in edge_faces):
+        raise ValueError(f"objects: edge_faces must hold pairs of face classes below {face_classes}")
+    count = count.astype(np.int64)
+    of_class = [np.nonzero(cls == c)[0] for c in range(face_classes)]             # ascending instance numbers
+    parent = np.arange(n_inst)
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    linked = np.zeros(n_inst, dtype=bool)
+    first_face = np.full(n_inst, -1, dtype=np.int64)
+    for c, (f1, f2) in enumerate(edge_faces):
+        if len(of_class[f1]) == 0 or len(of_class[f2]) == 0:                      # rule 2
+            continue
+        for e in np.nonzero(cls == face_classes + c)[0].tolist():
+            paired = []
+            for faces in (of_class[f1], of_class[f2]):
+                near = 2 * count[e, faces] > size[e] if share == 0.5 else count[e, faces].astype(np.float64) > np.float64(share) * np.float64(size[e])
+                hit = np.nonzero(near)[0]
+                if len(hit):
+                    paired.append(int(faces[hit[0]]))                             # the first match (break at :633, :639)
+            if not paired:
+                continue
+            first_face[e] = paired[0]
+            linked[paired] = True
+            a, b = find(paired[0]), find(paired[-1])
+            if a != b:
+                parent[max(a, b)] = min(a, b)                                     # the root is the smallest face of its component
+    object_of = np.full(n_inst, -1, dtype=np.int32)
+    faces = np.nonzero(linked)[0]
+    roots = np.array([find(i) for i in faces.tolist()], dtype=np.int64)
+    numbered = np.unique(roots)                                                   # ascending smallest face instance
+    object_of[faces] = np.searchsorted(numbered, roots)
+    edges = np.nonzero(first_face >= 0)[0]
+    object_of[edges] = object_of[first_face[edges]]
+    return object_of, int(len(numbered))
+
+
+def objects(coord, instance, instance_class, instance_size=None, radius=CONTACT_RADIUS, share=CONTACT_SHARE, face_classes=FACE_CLASSES,
+            edge_faces=None):
+    """The grouping of `instantiation_eval` (util/train_utils.py:595-714) on the output of instances(): which face instances form one
+    object ("box support").  coord [N, 3] fp32: the ORIGINAL coordinates (the reference pairs on pts_ori, not on the shifted points);
+    instance int32 / int64 [N] and instance_class [I] as instances() returns them; instance_size [I] defaults to a bincount of instance.
+    -> (object int32 [N]: the object of the point's FACE instance or -1 - the reference's supports hold face points only,
+        object_of_instance int32 [I]: for an edge instance the object of its first linked face, -1 = in no object, n_objects int).
+
+    An edge instance links, per face class beside its edge class (edge_faces, default the reference's lookup_face: edge class
+    face_classes + c -> two face classes, c < 12), the first face instance with more than `share` of the edge's points within `radius`
+    of it; objects are the connected components over the linked faces, numbered by ascending smallest face instance (rules 1-5 of
+    link_objects, which does this part on the host from ONE read-back of the contact counts; count comes from contacts' grid walk, the
+    quadratic min_d2 sweep is not run).  Two deliberate departures from the reference: with no link at all it raises IndexError
+    (pair_list[0], :670) - here the result is zero objects; its merge loop runs len + 100 iterations (:666) and equals the components
+    only when that reaches its fixed point - here the result is always the components.  The reference's list order (an artefact of the
+    rotating merge loop), the Open3D clean-up of every support (:716-720) and the OBB merging of test.py:294-326 are not reproduced.
+    Raises as contacts() does; ValueError for an instance_class / instance_size that is not [I]."""
+    _check_labelled(coord, instance, "objects")
+    dev = coord.device
+    if not isinstance(instance_class, torch.Tensor) or instance_class.dim() != 1 or instance_class.dtype not in (torch.int32, torch.int64):
+        raise ValueError("objects: instance_class must be an int32 / int64 tensor [I]")
+    n_inst = instance_class.shape[0]
+    if instance_size is not None and (not isinstance(instance_size, torch.Tensor) or tuple(instance_size.shape) != (n_inst,)
+                                      or instance_size.dtype not in (torch.int32, torch.int64)):
+        raise ValueError(f"objects: instance_size must be an int32 / int64 tensor [{n_inst}]")
+    link_objects(np.zeros((0, 0), np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64), share, face_classes, edge_faces)  # the settings
+    count, _, _ = _contacts(coord, instance, radius, n_inst, False, "objects")
+    n = coord.shape[0]
+    if instance_size is None:
+        instance_size = torch.bincount(instance[instance >= 0].long(), minlength=n_inst) if n > 0 else torch.zeros(n_inst, dtype=torch.int64)
+    head = torch.cat([count.flatten().long(), instance_size.to(dev).long(), instance_class.to(dev).long()]).cpu().numpy()   # the one read-back
+    LAST_CONTACTS["readbacks"] += 1
+    object_of, n_objects = link_objects(head[:n_inst * n_inst].reshape(n_inst, n_inst), head[n_inst * n_inst:n_inst * n_inst + n_inst],
+                                        head[n_inst * n_inst + n_inst:], share, face_classes, edge_faces)
+    face_object = np.where(head[n_inst * n_inst + n_inst:] < int(face_classes), object_of, -1).astype(np.int32)
+    table = torch.from_numpy(np.concatenate([face_object, np.full(1, -1, np.int32)])).to(dev)                # (the last entry serves -1)
+    obj = table[instance.long()] if n > 0 else torch.empty(0, dtype=torch.int32, device=dev)
+    return obj, torch.from_numpy(object_of).to(dev), n_objects
