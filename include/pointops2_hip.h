@@ -40,8 +40,9 @@ void *pointops2_get_stream(void);
 const char *pointops2_last_error(void);
 /* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
- * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points and the two
- * pointops2_contacts_*_launcher after them - a caller that needs them looks the symbols up. */
+ * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points, the two
+ * pointops2_contacts_*_launcher and pointops2_label_boxes_launcher / pointops2_reach_rows_launcher after them - a caller that needs
+ * them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -500,6 +501,30 @@ void pointops2_dbscan_label_launcher(int n, int n_valid, const float *pts, const
 void pointops2_contacts_count_launcher(int n_valid, int n_labels, const float *pts, const int *sorted_label, const int *ranges, float r2,
                                        unsigned *bitmap, int *count);
 void pointops2_contacts_min_launcher(int n_valid, int n_labels, const float *label_pts, float *min_d2);
+
+/* ---- Boxes and reach rows of labelled point sets: what the OBB merging behind the grouping (test.py:294-326, test_iou.py:373-406: one
+ * trimesh box per set and one dense cdist per pair of sets, every rotation) needs of the points ----
+ * Over the points with a label in [0, n_labels); the two steps are independent (stratified_transformer_amd/cluster.py drives them and
+ * owns every buffer; the merge loop itself runs on the host from one read-back of their results):
+ *   label_boxes: xyz [n, 3] float and label [n] in any order.  lo / hi [n_labels, 3] (float) = componentwise minimum / maximum of the
+ *          points of every label, size [n_labels] (int) = their number.  The caller presets lo = +inf, hi = -inf, size = 0; a label
+ *          without a point keeps them, and a further call on the same arrays accumulates.  Minimum and maximum are signed integer atomics
+ *          on an order-preserving image of the fp32 value (the bit pattern, its 31 low bits inverted for a negative value); -0.0 is taken
+ *          as +0.0, so results are to be compared by value.  Coordinates must not be NaN.  Up to 1024 labels every workgroup keeps a
+ *          private table in LDS and flushes the entries it touched; above that the atomics go to global memory.  Same result either way.
+ *   reach_rows: behind pointops2_dbscan_keys_launcher / _prepare_launcher run with ONE group (group 0 = labelled, -1 = not) and a cell of
+ *          at least r * (1 + 2^-7): pts and ranges as prepare wrote them, sorted_label [n_valid] = the labels in the same sorted order.
+ *          rows [n_valid, ceil(n_labels / 32)] (unsigned), in that sorted order: bit b of row p is set when some point q of label b
+ *          has d2(p, q) < r2 (strict), in fp32 with d2 = ((dx*dx) + (dy*dy)) + (dz*dz), dx = xp - xq, no fused operation - the test of
+ *          pointops2_contacts_count_launcher - and the bit of p's OWN label is cleared.  For n_labels <= 64 the row is built in registers
+ *          and every row is written (a point whose label is outside the range gets zeros); above that the caller zeroes rows and a
+ *          thread builds its row in place - no other thread touches it.  Plain stores, no atomics.
+ * Both results are independent of the order in which threads run.  No kernel waits on another workgroup; ranges are clamped and labels
+ * outside [0, n_labels) skipped, never followed outside the arrays.  n = 0, n_valid = 0 or n_labels = 0 launches nothing; a NULL array
+ * records an error. */
+void pointops2_label_boxes_launcher(int n, int n_labels, const float *xyz, const int *label, float *lo, float *hi, int *size);
+void pointops2_reach_rows_launcher(int n_valid, int n_labels, const float *pts, const int *sorted_label, const int *ranges, float r2,
+                                   unsigned *rows);
 
 /* ---- Whole-scene evaluation: the crop cover and the vote of the reference's test loop (test_backup.py:238-251, :278-281) ----
  * One crop of a part of n points (stratified_transformer_amd/evaluate.py drives the loop and owns every buffer):

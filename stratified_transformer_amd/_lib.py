@@ -106,6 +106,8 @@ SIGNATURES = {
     "pointops2_dbscan_label_launcher": [I, I, P, P, P, P, P, P, P, P],
     "pointops2_contacts_count_launcher": [I, I, P, P, P, F, P, P],
     "pointops2_contacts_min_launcher": [I, I, P, P],
+    "pointops2_label_boxes_launcher": [I, I, P, P, P, P, P],
+    "pointops2_reach_rows_launcher": [I, I, P, P, P, F, P],
     "pointops2_evaltile_seed_dist_launcher": [I, I, P, P, P, P, P, P],
     "pointops2_evaltile_update_launcher": [I, I, I, P, P, P, P, P],
     "pointops2_evaltile_vote_launcher": [I, I, I, I, P, P, P, P, P],

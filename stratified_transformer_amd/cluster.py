@@ -15,6 +15,10 @@ The second half of `instantiation_eval` (util/train_utils.py:595-714: which face
 is `objects`, on `contacts` (csrc/contacts.hip): per pair of labels, how many points of one set have a point of the other within a
 radius, and how close the two sets come - the question the fork also asks at :251-261 and test.py:311.  `link_objects` is the pairing
 and merging on plain host arrays.  scipy is not needed (and not imported).
+
+The step behind that, the OBB merging of test.py:294-326 (test_iou.py:373-406), is `merge_objects` on `label_boxes` and the reach rows of
+csrc/boxes.hip; `merge_sets` is its rotating loop on plain host arrays, `box_detection` the score test_iou.py:455-464 takes from the
+merged boxes (util/evaluation.py).  trimesh is not needed (and not imported).
 """
 import ctypes
 
@@ -466,7 +470,8 @@ def objects(coord, instance, instance_class, instance_size=None, radius=CONTACT_
     quadratic min_d2 sweep is not run).  Two deliberate departures from the reference: with no link at all it raises IndexError
     (pair_list[0], :670) - here the result is zero objects; its merge loop runs len + 100 iterations (:666) and equals the components
     only when that reaches its fixed point - here the result is always the components.  The reference's list order (an artefact of the
-    rotating merge loop), the Open3D clean-up of every support (:716-720) and the OBB merging of test.py:294-326 are not reproduced.
+    rotating merge loop) and the Open3D clean-up of every support (:716-720) are not reproduced; the OBB merging of test.py:294-326 is
+    the next step, merge_objects, on this function's output.
     Raises as contacts() does; ValueError for an instance_class / instance_size that is not [I]."""
     _check_labelled(coord, instance, "objects")
     dev = coord.device
@@ -489,3 +494,322 @@ def objects(coord, instance, instance_class, instance_size=None, radius=CONTACT_
     table = torch.from_numpy(np.concatenate([face_object, np.full(1, -1, np.int32)])).to(dev)                # (the last entry serves -1)
     obj = table[instance.long()] if n > 0 else torch.empty(0, dtype=torch.int32, device=dev)
     return obj, torch.from_numpy(object_of).to(dev), n_objects
+
+
+# ---- the OBB merging behind the grouping (test.py:294-326, the same loop at test_iou.py:373-406) and the box detection score that
+# test_iou.py:409-466 takes from the merged sets, on csrc/boxes.hip ----
+MERGE_RADIUS = 0.2          # test.py:310 pc_thre
+MERGE_OVERLAP = 0.3         # util/train_utils.py:861 thre
+MERGE_MIN_NEIGHBORS = 10    # test.py:312
+LAST_MERGE = {"launches": 0, "readbacks": 0}   # of the most recent label_boxes() / merge_objects() call (tools/bench_merge.py)
+
+
+def _merge_call(dev, name, *args):
+    LAST_MERGE["launches"] += 1
+    if dev.index == torch.cuda.current_device():
+        _lib.call(name, *args, device=dev)
+    else:
+        with torch.cuda.device(dev):
+            _lib.call(name, *args, device=dev)
+
+
+def _label_count(n_labels, who, name="n_labels"):
+    if n_labels is None:
+        return None
+    if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+        raise TypeError(f"{who}: {name} must be an int, got {type(n_labels).__name__}")
+    if n_labels < 0:
+        raise ValueError(f"{who}: {name} must be >= 0, got {n_labels}")
+    if n_labels > MAX_LABELS:
+        raise ValueError(f"{who}: {n_labels} labels: at most {MAX_LABELS}")
+    return int(n_labels)
+
+
+def _boxes(xyz, label, n_labels, dev):
+    """the launch of label_boxes on checked, contiguous inputs -> (lo, hi, size)"""
+    lo = torch.full((n_labels, 3), float("inf"), dtype=torch.float32, device=dev)
+    hi = torch.full((n_labels, 3), float("-inf"), dtype=torch.float32, device=dev)
+    size = torch.zeros(n_labels, dtype=torch.int32, device=dev)
+    if xyz.shape[0] > 0 and n_labels > 0:
+        _merge_call(dev, "pointops2_label_boxes_launcher", xyz.shape[0], n_labels, ptr(xyz), ptr(label), ptr(lo), ptr(hi), ptr(size))
+    return lo, hi, size
+
+
+def label_boxes(xyz, label, n_labels=None):
+    """The axis-aligned box and the size of every labelled point set: xyz [N, 3] fp32 and label int32 / int64 [N] in -1 .. I-1 (GPU; -1 =
+    the point takes no part) -> (lo float32 [I, 3], hi float32 [I, 3], size int32 [I]) with I = n_labels, or label.max() + 1.
+
+    lo / hi: the componentwise minimum / maximum of the label's points, exact (integer atomics on an order-preserving image of the fp32
+    values, csrc/boxes.hip); -0.0 counts as +0.0, so compare by value.  A label without a point keeps +inf / -inf / 0.
+    Raises before any launch: RuntimeError for a CPU tensor or mismatched devices; TypeError / ValueError for a wrong dtype or shape, a
+    label outside -1 .. I-1, non-finite coordinates or I > MAX_LABELS.  N = 0 or I = 0 launches nothing."""
+    _check_labelled(xyz, label, "label_boxes")
+    n_labels = _label_count(n_labels, "label_boxes")
+    dev, n = xyz.device, xyz.shape[0]
+    LAST_MERGE["launches"], LAST_MERGE["readbacks"] = 0, 0
+    if n == 0:
+        return _boxes(xyz, label, n_labels or 0, dev)
+    xyz = xyz.contiguous()
+    label = label.to(torch.int32).contiguous()
+    head = torch.cat([label.min()[None].long(), label.max()[None].long(), torch.isfinite(xyz).all()[None].long()]).cpu().numpy()
+    LAST_MERGE["readbacks"] += 1
+    l_min, l_max, all_finite = int(head[0]), int(head[1]), bool(head[2])
+    if n_labels is None:
+        n_labels = _label_count(max(l_max + 1, 0), "label_boxes")
+    if l_min < -1 or l_max >= n_labels:
+        raise ValueError(f"label_boxes: label values must be in -1 .. {n_labels - 1}, got {l_min} .. {l_max}")
+    if not all_finite:
+        raise ValueError("label_boxes: xyz must be finite")
+    return _boxes(xyz, label, n_labels, dev)
+
+
+def _overlaps(lo_a, hi_a, lo_b, hi_b, overlap):
+    """compute_partial_iou (util/train_utils.py:840-862) on the boxes that trimesh's PointCloud.bounding_box gives for the two point sets
+    (centre = (lo + hi) / 2, extents = hi - lo), in float64, operation for operation -> (a is covered, b is covered).  The boxes are
+    sequences of three Python floats - IEEE doubles, the arithmetic of the reference's numpy arrays without their per-call cost."""
+    edges, extent_a, extent_b = [], [], []
+    for k in range(3):
+        centre_a, e_a = (lo_a[k] + hi_a[k]) / 2, hi_a[k] - lo_a[k]
+        centre_b, e_b = (lo_b[k] + hi_b[k]) / 2, hi_b[k] - lo_b[k]
+        top = min(centre_a + e_a / 2, centre_b + e_b / 2)
+        bottom = max(centre_a - e_a / 2, centre_b - e_b / 2)
+        if not top > bottom:                                                       # strict: boxes that only touch, and flat boxes, never overlap
+            return False, False
+        edges.append(top - bottom)
+        extent_a.append(e_a)
+        extent_b.append(e_b)
+    inter = edges[0] * edges[1] * edges[2]
+    return inter / (extent_a[0] * extent_a[1] * extent_a[2]) > overlap, inter / (extent_b[0] * extent_b[1] * extent_b[2]) > overlap
+
+
+def merge_sets(lo, hi, size, pat_object, pat_rows, pat_count, overlap=MERGE_OVERLAP, min_neighbors=MERGE_MIN_NEIGHBORS):
+    """The rotating merge loop of test.py:294-326 on plain arrays - no GPU: lo / hi [O, 3] and size [O] (label_boxes), and the pattern
+    table of the border points: pat_object [P], pat_rows [P, ceil(O / 32)] (bit b: an object-b point within the radius, own bit cleared),
+    pat_count [P] = points of that (object, row) -> (set_of_object int32 [O], members: the final list, a list of lists of objects).
+
+    The loop as the reference runs it: the list starts with the objects of non-zero size in ascending object number and end_cnt is its
+    length; every round pops the first set, compares it with every remaining set - always against the set as it was popped - and
+    appends the popped set with everything it merged LAST.  The loop's sets are unions of whole objects, so
+      - a set's box is the minimum / maximum of its members' lo / hi (float64; exact from fp32), and its overlap test is
+        compute_partial_iou (util/train_utils.py:840-862) in float64, operation for operation: either ratio > overlap, and none when
+        the boxes do not intersect strictly on every axis;
+      - num_neighbor = np.sum(np.min(cdist(cur, targ), axis=0) < 0.2) is the number of border points whose object is in the target set
+        and whose row meets the current set - a point that reaches two members of the current set counts once;
+    and target merges when its box overlaps and num_neighbor > min_neighbors.  Sets are numbered in the order of the loop's final list,
+    the row order of the reference's pred_box (test_iou.py:409-423); an object of size 0 is in set -1.  With fewer than two objects the
+    reference returns before the loop (test.py:277); here nothing merges and every object is its own set."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    size = np.asarray(size).astype(np.int64).reshape(-1)
+    n_obj = size.shape[0]
+    words = (n_obj + 31) // 32
+    pat_object = np.asarray(pat_object).astype(np.int64).reshape(-1)
+    pat_count = np.asarray(pat_count).astype(np.int64).reshape(-1)
+    pat_rows = np.asarray(pat_rows)
+    if lo.shape != (n_obj, 3) or hi.shape != (n_obj, 3):
+        raise ValueError(f"merge_sets: lo and hi must be [O, 3] for the {n_obj} objects, got {lo.shape} and {hi.shape}")
+    n_pat = pat_object.shape[0]
+    if pat_rows.dtype.kind not in "iu":
+        raise TypeError(f"merge_sets: pat_rows must hold 32-bit words, got {pat_rows.dtype}")
+    pat_rows = pat_rows.astype(np.int64).astype(np.uint32).reshape(n_pat, -1) if n_pat else np.zeros((0, words), np.uint32)
+    if pat_rows.shape != (n_pat, words) or pat_count.shape != (n_pat,):
+        raise ValueError(f"merge_sets: pat_rows must be [P, {words}] and pat_count [P] for the {n_pat} patterns, got {pat_rows.shape} and {pat_count.shape}")
+    if n_pat and (pat_object.min() < 0 or pat_object.max() >= n_obj):
+        raise ValueError(f"merge_sets: pat_object must be in 0 .. {n_obj - 1}")
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, float, np.integer, np.floating)) or not np.isfinite(overlap) or overlap < 0:
+        raise ValueError(f"merge_sets: overlap must be a finite number >= 0, got {overlap!r}")
+    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or min_neighbors < 0:
+        raise ValueError(f"merge_sets: min_neighbors must be an int >= 0, got {min_neighbors!r}")
+
+    lo_l, hi_l = lo.tolist(), hi.tolist()                                           # Python floats: exact copies of the float64 values
+
+    def box_of(members):
+        return ([min(lo_l[o][k] for o in members) for k in range(3)], [max(hi_l[o][k] for o in members) for k in range(3)])
+
+    sets = [[int(o)] for o in np.nonzero(size > 0)[0]]
+    box = [box_of(s) for s in sets]
+    rounds = len(sets) if len(sets) >= 2 else 0
+    for _ in range(rounds):
+        cur, (cur_lo, cur_hi) = sets.pop(0), box.pop(0)
+        mask = np.zeros(words, dtype=np.uint32)
+        for o in cur:
+            mask[o >> 5] |= np.uint32(1 << (o & 31))
+        reaches_cur = (pat_rows & mask).any(1)                                      # the patterns that meet the current set, each once
+        near_of = np.bincount(pat_object[reaches_cur], weights=pat_count[reaches_cur], minlength=n_obj).astype(np.int64).tolist()   # exact below 2^53
+        merged, remain, remain_box = list(cur), [], []
+        for targ, (targ_lo, targ_hi) in zip(sets, box):
+            over_a, over_b = _overlaps(cur_lo, cur_hi, targ_lo, targ_hi, overlap)
+            if (over_a or over_b) and sum(near_of[o] for o in targ) > min_neighbors:
+                merged += targ
+            else:
+                remain.append(targ)
+                remain_box.append((targ_lo, targ_hi))
+        sets, box = remain + [merged], remain_box + [box_of(merged)]
+    set_of = np.full(n_obj, -1, dtype=np.int32)
+    for number, members in enumerate(sets):
+        set_of[members] = number
+    return set_of, sets
+
+
+def merge_objects(coord, obj, n_objects=None, radius=MERGE_RADIUS, overlap=MERGE_OVERLAP, min_neighbors=MERGE_MIN_NEIGHBORS):
+    """The OBB merging of test.py:294-326 (the same loop at test_iou.py:373-406) on the output of objects(): which objects the rotating
+    loop merges into one box.  coord [N, 3] fp32 and obj int32 / int64 [N] in -1 .. O-1 (GPU; -1 = in no object), O = n_objects or
+    obj.max() + 1 -> (merged int32 [N]: the set of the point's object or -1, set_of_object int32 [O] (-1 for an object without a point),
+    boxes float32 [S, 6] = lo | hi of every set, the reference's pred_box rows (test_iou.py:422), n_sets int).
+
+    The reference builds two trimesh boxes and one dense cdist per pair of sets in every rotation.  Here the device computes, once: the
+    box and size of every object (label_boxes), the row of objects within `radius` of every point (csrc/boxes.hip on the grid of
+    csrc/dbscan.hip; strict <, as `< pc_thre`), and - with torch - the table of distinct (object, row) patterns of the border points with
+    their counts.  ONE read-back of boxes, sizes and patterns later merge_sets runs the whole loop on the host; two read-backs in all
+    (LAST_MERGE), whatever the number of objects.  Distances are evaluated in fp32 as ((dx*dx) + (dy*dy)) + (dz*dz) < fp32(radius)^2
+    (the reference: float64 cdist), so a pair within about 1e-6 of the radius may fall on the other side.  Not reproduced: the Open3D
+    clean-up that the reference has commented out around the boxes, the .obj exports, and trimesh itself - PointCloud.bounding_box is
+    taken as the box of the bounds (min / max per axis), its published behaviour, which no fixture here pins.
+    Raises as contacts() does, before any launch.  N = 0 or no point in an object: no set, nothing launched."""
+    who = "merge_objects"
+    _check_labelled(coord, obj, who)
+    r = _positive_finite(radius, who, "radius")
+    with np.errstate(all="ignore"):
+        if not np.isfinite(r * r) or not r * r > 0:
+            raise ValueError(f"{who}: radius must be finite and > 0 when squared in fp32, got {radius}")
+    n_objects = _label_count(n_objects, who, "n_objects")
+    merge_sets(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0), np.zeros(0), np.zeros((0, 0), np.int32), np.zeros(0), overlap, min_neighbors)  # the settings
+    dev, n = coord.device, coord.shape[0]
+    LAST_MERGE["launches"], LAST_MERGE["readbacks"] = 0, 0
+
+    def nothing(o):
+        return (torch.full((n,), -1, dtype=torch.int32, device=dev), torch.full((o,), -1, dtype=torch.int32, device=dev),
+                torch.zeros(0, 6, dtype=torch.float32, device=dev), 0)
+
+    if n == 0:
+        return nothing(n_objects or 0)
+    coord = coord.contiguous()
+    label = obj.to(torch.int32).contiguous()
+
+    # one read-back up front: the object range, the points that take part and their bounding box
+    member = label >= 0
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
+    lo_all = torch.where(member[:, None], coord, inf).amin(0)
+    hi_all = torch.where(member[:, None], coord, -inf).amax(0)
+    finite = torch.isfinite(coord).all()
+    head = torch.cat([label.min()[None].double(), label.max()[None].double(), member.sum()[None].double(), finite[None].double(),
+                      lo_all.double(), hi_all.double()]).cpu().numpy()
+    LAST_MERGE["readbacks"] += 1
+    l_min, l_max, n_valid, all_finite = int(head[0]), int(head[1]), int(head[2]), bool(head[3])
+    if n_objects is None:
+        n_objects = _label_count(max(l_max + 1, 0), who, "n_objects")
+    if l_min < -1 or l_max >= n_objects:
+        raise ValueError(f"{who}: label values must be in -1 .. {n_objects - 1}, got {l_min} .. {l_max}")
+    if not all_finite:
+        raise ValueError(f"{who}: xyz must be finite")
+    words = (n_objects + 31) // 32
+    if n_objects > REG_LABELS and n_valid * words * 4 > MAX_BITMAP_BYTES:
+        raise ValueError(f"{who}: the bitmap of {n_valid} points x {n_objects} labels takes {n_valid * words * 4} bytes, more than {MAX_BITMAP_BYTES}")
+    if n_valid == 0 or n_objects == 0:
+        return nothing(n_objects)
+    cell = float(r) * CELL_MARGIN
+    origin, top = head[4:7], head[7:10]
+    dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
+    if max(dims) > MAX_CELLS_PER_AXIS or dims[0] * dims[1] * dims[2] >= 2 ** 61:
+        raise ValueError(f"{who}: the cloud spans {dims} cells of edge {cell:g}: too many for the 64-bit cell keys")
+
+    lo, hi, size = _boxes(coord, label, n_objects, dev)
+    slabel, rows = _reach_rows(coord, label, member, n, n_valid, n_objects, origin, cell, dims, np.float32(r * r), dev)
+    pat, pat_count = _patterns(slabel, rows)
+
+    # the one final read-back: boxes, sizes and patterns as one array of 32-bit words
+    n_pat = pat.shape[0]
+    flat = torch.cat([lo.view(torch.int32).flatten(), hi.view(torch.int32).flatten(), size, pat.flatten(), pat_count.to(torch.int32)]).cpu().numpy()
+    LAST_MERGE["readbacks"] += 1
+    at = np.cumsum([0, 3 * n_objects, 3 * n_objects, n_objects, n_pat * (1 + words), n_pat])
+    lo_h, hi_h = (flat[at[k]:at[k + 1]].view(np.float32).reshape(n_objects, 3) for k in (0, 1))
+    pat_h = flat[at[3]:at[4]].reshape(n_pat, 1 + words)
+    set_of, sets = merge_sets(lo_h, hi_h, flat[at[2]:at[3]], pat_h[:, 0], pat_h[:, 1:], flat[at[4]:at[5]], overlap, min_neighbors)
+    boxes = np.array([np.concatenate([lo_h[s].min(0), hi_h[s].max(0)]) for s in sets], dtype=np.float32).reshape(len(sets), 6)
+    table = torch.from_numpy(np.concatenate([set_of, np.full(1, -1, np.int32)])).to(dev)                     # (the last entry serves -1)
+    return table[label.long()], table[:n_objects], torch.from_numpy(boxes).to(dev), len(sets)
+
+
+def _merge_grid(coord, label, member, n, n_valid, origin, cell, dims, dev):
+    """the fixed-radius grid of csrc/dbscan.hip over the labelled points -> (pts [n_valid, 4], sorted_label [n_valid], ranges [18, n_valid])"""
+    group = member.to(torch.int32) - 1                       # one group: 0 for a labelled point, -1 for the others
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    _merge_call(dev, "pointops2_dbscan_keys_launcher", n, 1, ptr(coord), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
+                ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
+    skeys, order = torch.sort(keys, stable=True)
+    pts = torch.empty(n_valid, 4, dtype=torch.float32, device=dev)
+    sgroup = torch.empty(n_valid, dtype=torch.int32, device=dev)
+    ranges = torch.empty(18, n_valid, dtype=torch.int32, device=dev)
+    _merge_call(dev, "pointops2_dbscan_prepare_launcher", n, n_valid, dims[0], dims[1], dims[2], ptr(coord), ptr(skeys), ptr(order), ptr(pts),
+                ptr(sgroup), ptr(ranges))
+    return pts, label[order[:n_valid]].contiguous(), ranges
+
+
+def _rows_on_grid(pts, slabel, ranges, n_objects, r2, dev):
+    """-> rows int32 [n_valid, words] in the grid's order: the objects within reach of every point, its own left out"""
+    n_valid = slabel.shape[0]
+    rows = torch.zeros(n_valid, (n_objects + 31) // 32, dtype=torch.int32, device=dev)
+    _merge_call(dev, "pointops2_reach_rows_launcher", n_valid, n_objects, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(rows))
+    return rows
+
+
+def _reach_rows(coord, label, member, n, n_valid, n_objects, origin, cell, dims, r2, dev):
+    """grid keys, prepare and the reach rows -> (sorted_label int32 [n_valid], rows int32 [n_valid, words]), both in the grid's order"""
+    pts, slabel, ranges = _merge_grid(coord, label, member, n, n_valid, origin, cell, dims, dev)
+    return slabel, _rows_on_grid(pts, slabel, ranges, n_objects, r2, dev)
+
+
+def _patterns(slabel, rows):
+    """the distinct (object, row) patterns of the border points - the points whose row is not empty - and how many points show each
+    -> (pat int32 [P, 1 + words], count int64 [P]); on the device"""
+    border = (rows != 0).any(1)
+    keyed = torch.cat([slabel[border, None], rows[border]], 1)
+    if keyed.shape[0] == 0:
+        return keyed, torch.zeros(0, dtype=torch.int64, device=rows.device)
+    return torch.unique(keyed, dim=0, return_counts=True)
+
+
+def box_detection(pred_box, gt_box, overlap_threshold=0.5):
+    """The box detection score that test_iou.py:455-464 takes from the merged boxes, on host arrays - no GPU: pred_box [P, 6] and gt_box
+    [G, 6] as x1 y1 z1 x2 y2 z2 -> (tp_iou: the IoU of every matched prediction, fp: -1.0 per unmatched prediction, fn int: ground-truth
+    boxes left over, precision = TP / (TP + FP), recall = TP / (TP + FN)).
+
+    Follows util/evaluation.py in float64: DetectionMAP.intersect_area / jaccard (:109-152) - including the upper clip bound, which is the
+    LARGEST difference of the whole [P, G, 3] array: when no pair of boxes intersects on any axis that bound is negative and every
+    "intersection" becomes its cube, a negative volume, hence a negative IoU -; IoU < overlap_threshold -> 0 (:86); compute_TP_FP_FN
+    (:194-239): predictions in their given order, each takes the ground-truth box of largest remaining IoU, a ground-truth box is used
+    once; the two ratios of :95-96.  Two departures: with no prediction the reference's jaccard returns an array shaped [0, 6] and
+    reports FN = 6 - here FN is the number of ground-truth boxes; and a zero denominator gives None instead of ZeroDivisionError."""
+    pred = np.asarray(pred_box.detach().cpu().numpy() if isinstance(pred_box, torch.Tensor) else pred_box, dtype=np.float64)
+    gt = np.asarray(gt_box.detach().cpu().numpy() if isinstance(gt_box, torch.Tensor) else gt_box, dtype=np.float64)
+    pred, gt = pred.reshape(-1, 6) if pred.size == 0 else pred, gt.reshape(-1, 6) if gt.size == 0 else gt
+    if pred.ndim != 2 or pred.shape[1] != 6 or gt.ndim != 2 or gt.shape[1] != 6:
+        raise ValueError(f"box_detection: pred_box and gt_box must be [P, 6] and [G, 6], got {pred.shape} and {gt.shape}")
+    if isinstance(overlap_threshold, bool) or not isinstance(overlap_threshold, (int, float, np.integer, np.floating)) or not np.isfinite(overlap_threshold):
+        raise ValueError(f"box_detection: overlap_threshold must be a finite number, got {overlap_threshold!r}")
+    n_pred, n_gt = pred.shape[0], gt.shape[0]
+    iou = np.zeros((n_pred, n_gt))
+    if n_pred and n_gt:
+        diff = np.minimum(pred[:, None, 3:], gt[None, :, 3:]) - np.maximum(pred[:, None, :3], gt[None, :, :3])
+        with np.errstate(all="ignore"):
+            edge = np.clip(diff, a_min=0, a_max=np.max(diff))
+            inter = edge[:, :, 0] * edge[:, :, 1] * edge[:, :, 2]
+            vol_p = (pred[:, 3] - pred[:, 0]) * (pred[:, 4] - pred[:, 1]) * (pred[:, 5] - pred[:, 2])
+            vol_g = (gt[:, 3] - gt[:, 0]) * (gt[:, 4] - gt[:, 1]) * (gt[:, 5] - gt[:, 2])
+            iou = inter / (vol_p[:, None] + vol_g[None, :] - inter)
+        iou[iou < overlap_threshold] = 0
+    free = iou != 0
+    tp, fp, fn = [], [], n_gt
+    for i in range(n_pred):
+        best, best_iou = -1, -1
+        for j in range(n_gt):
+            if free[i, j] and iou[i, j] > best_iou:
+                best, best_iou = j, iou[i, j]
+        if best != -1:
+            tp.append(float(best_iou))
+            free[:, best] = False
+            fn -= 1
+        else:
+            fp.append(float(best_iou))
+    precision = len(tp) / (len(tp) + len(fp)) if tp or fp else None
+    recall = len(tp) / (len(tp) + fn) if len(tp) + fn else None
+    return tp, fp, fn, precision, recall
