@@ -19,8 +19,13 @@ and merging on plain host arrays.  scipy is not needed (and not imported).
 The step behind that, the OBB merging of test.py:294-326 (test_iou.py:373-406), is `merge_objects` on `label_boxes` and the reach rows of
 csrc/boxes.hip; `merge_sets` is its rotating loop on plain host arrays, `box_detection` the score test_iou.py:455-464 takes from the
 merged boxes (util/evaluation.py).  trimesh is not needed (and not imported).
+
+dbscan, contacts / objects and merge_objects stand on ONE fixed-radius grid: `_scan` (the read-back up front), `_dims` and `_grid` (cell
+keys, torch's sort, the nine prepared runs per point) build it here, csrc/radius_grid.h walks it on the device for all three.
 """
+import contextlib
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -31,6 +36,9 @@ from ._lib import ptr
 MAX_ROUNDS = 64            # of the component loop: the trees at least halve per round (csrc/dbscan.hip), so 2^31 points need 32
 CELL_MARGIN = 1.0 + 2.0 ** -7   # the grid's cells are this much wider than the largest eps (fp32 rounding of the distance test)
 MAX_CELLS_PER_AXIS = 1 << 20
+REG_LABELS = 64             # csrc/radius_grid.h keeps rows of up to this many labels in registers: no bitmap
+MAX_BITMAP_BYTES = 1 << 30  # of the [n_valid, ceil(I / 32)] rows of labels in reach (more than REG_LABELS labels)
+MAX_LABELS = 1 << 15        # the [I, I] tables are indexed with ints
 LAST = {"rounds": 0, "launches": 0}   # of the most recent dbscan() call (tools/bench_dbscan.py, the chain test)
 
 # instantiation_eval's settings (util/train_utils.py:558-563): faces (classes below 6) and edges
@@ -39,9 +47,9 @@ FACE_SETTINGS = (0.1, 5, 50)
 EDGE_SETTINGS = (0.15, 3, 20)
 
 
-def _gpu(t, name):
+def _gpu(t, who, name):
     if not getattr(t, "is_cuda", False):
-        raise RuntimeError(f"dbscan: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {getattr(t, 'device', type(t).__name__)}")
+        raise RuntimeError(f"{who}: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {getattr(t, 'device', type(t).__name__)}")
 
 
 def _per_group(value, n_groups, dtype, name):
@@ -76,29 +84,109 @@ def _settings(eps, min_samples, n_groups):
     return (g1 if g1 is not None else g2), e, m
 
 
-def _check_inputs(xyz, group):
-    _gpu(xyz, "xyz")
+def _check_tensors(who, xyz, label, noun):
+    """xyz [N, 3] fp32 and its per-point `noun` ("group" / "label") int32 / int64 [N] or None, on one GPU"""
+    _gpu(xyz, who, "xyz")
+    if label is not None:
+        _gpu(label, who, noun)
+        if label.device != xyz.device:
+            raise RuntimeError(f"{who}: {noun} is on {label.device}, xyz on {xyz.device}")
     if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise ValueError(f"dbscan: xyz must be [N, 3], got {tuple(xyz.shape)}")
+        raise ValueError(f"{who}: xyz must be [N, 3], got {tuple(xyz.shape)}")
     if xyz.dtype != torch.float32:
-        raise TypeError(f"dbscan: xyz must be float32, got {xyz.dtype}")
-    if group is not None:
-        _gpu(group, "group")
-        if group.device != xyz.device:
-            raise RuntimeError(f"dbscan: group is on {group.device}, xyz on {xyz.device}")
-        if group.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"dbscan: group must be int32 / int64, got {group.dtype}")
-        if group.dim() != 1 or group.shape[0] != xyz.shape[0]:
-            raise ValueError(f"dbscan: group must be [N] = [{xyz.shape[0]}], got {tuple(group.shape)}")
+        raise TypeError(f"{who}: xyz must be float32, got {xyz.dtype}")
+    if label is not None:
+        if label.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{who}: {noun} must be int32 / int64, got {label.dtype}")
+        if label.dim() != 1 or label.shape[0] != xyz.shape[0]:
+            raise ValueError(f"{who}: {noun} must be [N] = [{xyz.shape[0]}], got {tuple(label.shape)}")
 
 
-def _call(name, ref, *args):
-    LAST["launches"] += 1
-    if ref.device.index == torch.cuda.current_device():
-        _lib.call(name, *args, device=ref.device)
-    else:
-        with torch.cuda.device(ref.device):
-            _lib.call(name, *args, device=ref.device)
+def _radius(who, radius):
+    """-> (fp32(radius), its fp32 square, rounded once), both finite and > 0"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: radius must be a number, got {type(radius).__name__}")
+    with np.errstate(all="ignore"):
+        r = np.float32(radius)
+        if not np.isfinite(radius) or not radius > 0 or not np.isfinite(r * r) or not r * r > 0:
+            raise ValueError(f"{who}: radius must be finite and > 0, also when squared in fp32, got {radius}")
+    return r, np.float32(r * r)
+
+
+def _label_count(who, n_labels, name="n_labels"):
+    if n_labels is None:
+        return None
+    if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+        raise TypeError(f"{who}: {name} must be an int, got {type(n_labels).__name__}")
+    if n_labels < 0:
+        raise ValueError(f"{who}: {name} must be >= 0, got {n_labels}")
+    if n_labels > MAX_LABELS:
+        raise ValueError(f"{who}: {n_labels} labels: at most {MAX_LABELS}")
+    return int(n_labels)
+
+
+def _label_range(who, n_labels, l_min, l_max, name="n_labels"):
+    """-> the number of labels (n_labels, or l_max + 1), with every label in -1 .. that number - 1"""
+    if n_labels is None:
+        n_labels = _label_count(who, max(l_max + 1, 0), name)
+    if l_min < -1 or l_max >= n_labels:
+        raise ValueError(f"{who}: label values must be in -1 .. {n_labels - 1}, got {l_min} .. {l_max}")
+    return n_labels
+
+
+def _row_words(who, n_valid, n_labels):
+    """-> words of a row of labels in reach; the rows of n_valid points must fit MAX_BITMAP_BYTES where they are kept in memory"""
+    words = (n_labels + 31) // 32
+    if n_labels > REG_LABELS and n_valid * words * 4 > MAX_BITMAP_BYTES:
+        raise ValueError(f"{who}: the bitmap of {n_valid} points x {n_labels} labels takes {n_valid * words * 4} bytes, more than {MAX_BITMAP_BYTES}")
+    return words
+
+
+def _launch(counter, dev, name, *args):
+    """one library launch on `dev`, counted in `counter` (LAST, LAST_CONTACTS or LAST_MERGE)"""
+    counter["launches"] += 1
+    with contextlib.nullcontext() if dev.index == torch.cuda.current_device() else torch.cuda.device(dev):
+        _lib.call(name, *args, device=dev)
+
+
+def _scan(who, xyz, label):
+    """The one read-back up front: the label (group) range, the points that take part (label >= 0) and their bounding box
+    -> (member bool [N], l_min, l_max, n_valid, origin float64 [3], top float64 [3]); ValueError for non-finite coordinates."""
+    member = label >= 0
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=xyz.device)
+    lo = torch.where(member[:, None], xyz, inf).amin(0)
+    hi = torch.where(member[:, None], xyz, -inf).amax(0)
+    finite = torch.isfinite(xyz).all()
+    head = torch.cat([label.min()[None].double(), label.max()[None].double(), member.sum()[None].double(), finite[None].double(),
+                      lo.double(), hi.double()]).cpu().numpy()
+    if not head[3]:
+        raise ValueError(f"{who}: xyz must be finite")
+    return member, int(head[0]), int(head[1]), int(head[2]), head[4:7], head[7:10]
+
+
+def _dims(who, n_groups, origin, top, cell):
+    """-> the grid's cells per axis [nx, ny, nz]; ValueError when n_groups such grids do not fit the 64-bit cell keys"""
+    dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
+    if max(dims) > MAX_CELLS_PER_AXIS or n_groups * dims[0] * dims[1] * dims[2] >= 2 ** 61:
+        raise ValueError(f"{who}: the cloud spans {dims} cells of edge {cell:g}: too many for the 64-bit cell keys")
+    return dims
+
+
+def _grid(launch, xyz, group, n_groups, n_valid, origin, cell, dims):
+    """The fixed-radius grid of csrc/radius_grid.h over the points with a group in 0 .. n_groups-1: cell keys, torch's stable sort, the
+    nine runs per point -> (pts float32 [n_valid, 4] = x, y, z, original index as bits, in the grid's order; order int64 [N]: the sort's
+    permutation, the n_valid points that take part first; sorted_group int32 [n_valid]; ranges int32 [18, n_valid])."""
+    dev, n = xyz.device, xyz.shape[0]
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    launch("pointops2_dbscan_keys_launcher", n, n_groups, ptr(xyz), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
+           ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
+    skeys, order = torch.sort(keys, stable=True)
+    pts = torch.empty(n_valid, 4, dtype=torch.float32, device=dev)
+    sgroup = torch.empty(n_valid, dtype=torch.int32, device=dev)
+    ranges = torch.empty(18, n_valid, dtype=torch.int32, device=dev)
+    launch("pointops2_dbscan_prepare_launcher", n, n_valid, dims[0], dims[1], dims[2], ptr(xyz), ptr(skeys), ptr(order), ptr(pts), ptr(sgroup),
+           ptr(ranges))
+    return pts, order, sgroup, ranges
 
 
 def dbscan(xyz, eps, min_samples, group=None):
@@ -110,7 +198,7 @@ def dbscan(xyz, eps, min_samples, group=None):
     Raises before any launch: RuntimeError for a CPU tensor, ValueError / TypeError for a wrong shape or dtype, ValueError for
     eps <= 0, min_samples < 1, a group outside -1 .. G-1 or non-finite coordinates.  RuntimeError when the component loop has not
     settled after MAX_ROUNDS rounds."""
-    _check_inputs(xyz, group)
+    _check_tensors("dbscan", xyz, group, "group")
     n_groups, eps_h, ms_h = _settings(eps, min_samples, 1 if group is None else None)
     dev, n = xyz.device, xyz.shape[0]
     LAST["rounds"], LAST["launches"] = 0, 0
@@ -123,21 +211,11 @@ def dbscan(xyz, eps, min_samples, group=None):
         group = torch.zeros(n, dtype=torch.int32, device=dev)
     group = group.to(torch.int32).contiguous()
 
-    # one read-back up front: the group range, the points that take part and their bounding box
-    member = group >= 0
-    inf = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
-    lo = torch.where(member[:, None], xyz, inf).amin(0)
-    hi = torch.where(member[:, None], xyz, -inf).amax(0)
-    finite = torch.isfinite(xyz).all()
-    head = torch.cat([group.min()[None].double(), group.max()[None].double(), member.sum()[None].double(), finite[None].double(),
-                      lo.double(), hi.double()]).cpu().numpy()
-    g_min, g_max, n_valid, all_finite = int(head[0]), int(head[1]), int(head[2]), bool(head[3])
+    _, g_min, g_max, n_valid, origin, top = _scan("dbscan", xyz, group)
     if n_groups is None:
         n_groups = max(g_max + 1, 1)
     if g_min < -1 or g_max >= n_groups:
         raise ValueError(f"dbscan: group values must be in -1 .. {n_groups - 1}, got {g_min} .. {g_max}")
-    if not all_finite:
-        raise ValueError("dbscan: xyz must be finite")
     eps_h = np.broadcast_to(eps_h, (n_groups,)).astype(np.float32)
     ms_h = np.broadcast_to(ms_h, (n_groups,)).astype(np.int32)
 
@@ -148,31 +226,21 @@ def dbscan(xyz, eps, min_samples, group=None):
         return labels, core.bool(), n_clusters
 
     cell = float(np.float32(eps_h.max())) * CELL_MARGIN
-    origin, top = head[4:7], head[7:10]
-    dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
-    if max(dims) > MAX_CELLS_PER_AXIS or n_groups * dims[0] * dims[1] * dims[2] >= 2 ** 61:
-        raise ValueError(f"dbscan: the cloud spans {dims} cells of edge {cell:g}: too many for the 64-bit cell keys")
+    dims = _dims("dbscan", n_groups, origin, top, cell)
     eps2 = torch.from_numpy(eps_h * eps_h).to(dev)          # fp32 product, rounded once
     ms = torch.from_numpy(ms_h).to(dev)
 
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
-    _call("pointops2_dbscan_keys_launcher", xyz, n, n_groups, ptr(xyz), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
-          ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
-    skeys, order = torch.sort(keys, stable=True)
-    pts = torch.empty(n_valid, 4, dtype=torch.float32, device=dev)
-    sgroup = torch.empty(n_valid, dtype=torch.int32, device=dev)
-    ranges = torch.empty(18, n_valid, dtype=torch.int32, device=dev)
-    _call("pointops2_dbscan_prepare_launcher", xyz, n, n_valid, dims[0], dims[1], dims[2], ptr(xyz), ptr(skeys), ptr(order), ptr(pts),
-          ptr(sgroup), ptr(ranges))
+    call = functools.partial(_launch, LAST, dev)
+    pts, _, sgroup, ranges = _grid(call, xyz, group, n_groups, n_valid, origin, cell, dims)
     score = torch.empty(n_valid, dtype=torch.uint8, device=dev)
     parent = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    _call("pointops2_dbscan_core_launcher", xyz, n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(ms), ptr(score), ptr(core),
-          ptr(parent))
+    call("pointops2_dbscan_core_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(ms), ptr(score), ptr(core),
+         ptr(parent))
 
     changed = torch.zeros(1, dtype=torch.int32, device=dev)
     for rounds in range(1, MAX_ROUNDS + 1):
-        _call("pointops2_dbscan_round_launcher", xyz, n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
-              ptr(changed))
+        call("pointops2_dbscan_round_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
+             ptr(changed))
         LAST["launches"] += 1                                # (a round is two kernels)
         LAST["rounds"] = rounds
         if int(changed.item()) == 0:                         # the one small read-back per round
@@ -192,8 +260,8 @@ def dbscan(xyz, eps, min_samples, group=None):
         starts = torch.cumsum(counts, 0) - counts
         number = torch.arange(roots.numel(), device=dev) - starts[sorted_group]
         cluster_of_root[roots[by_group]] = number.to(torch.int32)
-    _call("pointops2_dbscan_label_launcher", xyz, n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
-          ptr(cluster_of_root), ptr(labels))
+    call("pointops2_dbscan_label_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
+         ptr(cluster_of_root), ptr(labels))
     return labels, core.bool(), n_clusters
 
 
@@ -220,8 +288,8 @@ def instances(coord, shift, pred, eps=None, min_samples=None, min_points=None):
     scalars or per-class sequences of one length C > max(pred); None = the reference's settings: classes below 6 eps 0.1,
     min_samples 5, min_points 50, the others 0.15, 3, 20.
     -> (instance int32 [N]: the instance of every point or -1, instance_class int32 [I], instance_size int32 [I])."""
-    _check_inputs(coord, pred)
-    _gpu(shift, "shift")
+    _check_tensors("dbscan", coord, pred, "group")
+    _gpu(shift, "dbscan", "shift")
     if shift.shape != coord.shape or shift.dtype != torch.float32:
         raise ValueError(f"dbscan: shift must be float32 {tuple(coord.shape)}, got {shift.dtype} {tuple(shift.shape)}")
     if shift.device != coord.device:
@@ -256,9 +324,6 @@ def instances(coord, shift, pred, eps=None, min_samples=None, min_points=None):
 
 
 # ---- contacts between labelled point sets, and the grouping of face instances into objects built on them (csrc/contacts.hip) ----
-MAX_BITMAP_BYTES = 1 << 30  # of the [n_valid, ceil(I / 32)] rows of labels in reach (more than 64 labels)
-MAX_LABELS = 1 << 15        # the two [I, I] tables are indexed with ints
-REG_LABELS = 64             # csrc/contacts.hip keeps rows of up to this many labels in registers: no bitmap
 # instantiation_eval's settings (util/train_utils.py:600, :629-631): the two face classes beside edge class 6 + c
 EDGE_FACES = ((0, 1), (0, 2), (1, 2), (0, 3), (1, 3), (0, 4), (2, 4), (3, 4), (1, 5), (2, 5), (3, 5), (4, 5))
 CONTACT_RADIUS = 0.08
@@ -266,43 +331,11 @@ CONTACT_SHARE = 0.5
 LAST_CONTACTS = {"launches": 0, "readbacks": 0}   # of the most recent contacts() / objects() call (tools/bench_contacts.py)
 
 
-def _check_labelled(xyz, label, who):
-    if not getattr(xyz, "is_cuda", False) or not getattr(label, "is_cuda", False):
-        bad = xyz if not getattr(xyz, "is_cuda", False) else label
-        raise RuntimeError(f"{who}: expected GPU tensors (the pointops2 HIP path has no CPU fallback), got {getattr(bad, 'device', type(bad).__name__)}")
-    if label.device != xyz.device:
-        raise RuntimeError(f"{who}: label is on {label.device}, xyz on {xyz.device}")
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise ValueError(f"{who}: xyz must be [N, 3], got {tuple(xyz.shape)}")
-    if xyz.dtype != torch.float32:
-        raise TypeError(f"{who}: xyz must be float32, got {xyz.dtype}")
-    if label.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{who}: label must be int32 / int64, got {label.dtype}")
-    if label.dim() != 1 or label.shape[0] != xyz.shape[0]:
-        raise ValueError(f"{who}: label must be [N] = [{xyz.shape[0]}], got {tuple(label.shape)}")
-
-
-def _positive_finite(value, who, name):
-    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
-        raise TypeError(f"{who}: {name} must be a number, got {type(value).__name__}")
-    if not np.isfinite(value) or not value > 0 or not np.isfinite(np.float32(value)) or not np.float32(value) > 0:
-        raise ValueError(f"{who}: {name} must be finite and > 0, got {value}")
-    return np.float32(value)
-
-
 def _contacts(xyz, label, radius, n_labels, want_min, who):
     """-> (count int32 [I, I], min_d2 float32 [I, I] or None, I)"""
-    _check_labelled(xyz, label, who)
-    r = _positive_finite(radius, who, "radius")
-    with np.errstate(all="ignore"):
-        if not np.isfinite(r * r) or not r * r > 0:
-            raise ValueError(f"{who}: radius must be finite and > 0 when squared in fp32, got {radius}")
-    if n_labels is not None:
-        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
-            raise TypeError(f"{who}: n_labels must be an int, got {type(n_labels).__name__}")
-        if n_labels < 0:
-            raise ValueError(f"{who}: n_labels must be >= 0, got {n_labels}")
-        n_labels = int(n_labels)
+    _check_tensors(who, xyz, label, "label")
+    r, r2 = _radius(who, radius)
+    n_labels = _label_count(who, n_labels)
     dev, n = xyz.device, xyz.shape[0]
     LAST_CONTACTS["launches"], LAST_CONTACTS["readbacks"] = 0, 0
 
@@ -315,57 +348,20 @@ def _contacts(xyz, label, radius, n_labels, want_min, who):
     xyz = xyz.contiguous()
     label = label.to(torch.int32).contiguous()
 
-    # one read-back up front: the label range, the points that take part and their bounding box
-    member = label >= 0
-    inf = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
-    lo = torch.where(member[:, None], xyz, inf).amin(0)
-    hi = torch.where(member[:, None], xyz, -inf).amax(0)
-    finite = torch.isfinite(xyz).all()
-    head = torch.cat([label.min()[None].double(), label.max()[None].double(), member.sum()[None].double(), finite[None].double(),
-                      lo.double(), hi.double()]).cpu().numpy()
     LAST_CONTACTS["readbacks"] += 1
-    l_min, l_max, n_valid, all_finite = int(head[0]), int(head[1]), int(head[2]), bool(head[3])
-    if n_labels is None:
-        n_labels = max(l_max + 1, 0)
-    if l_min < -1 or l_max >= n_labels:
-        raise ValueError(f"{who}: label values must be in -1 .. {n_labels - 1}, got {l_min} .. {l_max}")
-    if not all_finite:
-        raise ValueError(f"{who}: xyz must be finite")
-    words = (n_labels + 31) // 32
-    if n_labels > REG_LABELS and n_valid * words * 4 > MAX_BITMAP_BYTES:
-        raise ValueError(f"{who}: the bitmap of {n_valid} points x {n_labels} labels takes {n_valid * words * 4} bytes, more than {MAX_BITMAP_BYTES}")
-    if n_labels > MAX_LABELS:
-        raise ValueError(f"{who}: {n_labels} labels: the tables hold at most {MAX_LABELS} x {MAX_LABELS} entries")
+    member, l_min, l_max, n_valid, origin, top = _scan(who, xyz, label)
+    n_labels = _label_range(who, n_labels, l_min, l_max)
+    words = _row_words(who, n_valid, n_labels)
     if n_valid == 0 or n_labels == 0:
         return tables(n_labels)
     cell = float(r) * CELL_MARGIN
-    origin, top = head[4:7], head[7:10]
-    dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
-    if max(dims) > MAX_CELLS_PER_AXIS or dims[0] * dims[1] * dims[2] >= 2 ** 61:
-        raise ValueError(f"{who}: the cloud spans {dims} cells of edge {cell:g}: too many for the 64-bit cell keys")
+    dims = _dims(who, 1, origin, top, cell)
     count, min_d2, _ = tables(n_labels)
-
-    def call(name, *args):
-        LAST_CONTACTS["launches"] += 1
-        if dev.index == torch.cuda.current_device():
-            _lib.call(name, *args, device=dev)
-        else:
-            with torch.cuda.device(dev):
-                _lib.call(name, *args, device=dev)
-
+    call = functools.partial(_launch, LAST_CONTACTS, dev)
     group = member.to(torch.int32) - 1                       # one group: 0 for a labelled point, -1 for the others
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
-    call("pointops2_dbscan_keys_launcher", n, 1, ptr(xyz), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
-         ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
-    skeys, order = torch.sort(keys, stable=True)
-    pts = torch.empty(n_valid, 4, dtype=torch.float32, device=dev)
-    sgroup = torch.empty(n_valid, dtype=torch.int32, device=dev)
-    ranges = torch.empty(18, n_valid, dtype=torch.int32, device=dev)
-    call("pointops2_dbscan_prepare_launcher", n, n_valid, dims[0], dims[1], dims[2], ptr(xyz), ptr(skeys), ptr(order), ptr(pts), ptr(sgroup),
-         ptr(ranges))
+    pts, order, _, ranges = _grid(call, xyz, group, 1, n_valid, origin, cell, dims)
     slabel = label[order[:n_valid]].contiguous()
     bitmap = torch.zeros(n_valid, words, dtype=torch.int32, device=dev) if n_labels > REG_LABELS else None
-    r2 = np.float32(r * r)                                   # fp32 product, rounded once
     call("pointops2_contacts_count_launcher", n_valid, n_labels, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(bitmap), ptr(count))
     if want_min:
         llabel, by_label = torch.sort(slabel, stable=True)   # ascending label; inside a label the grid's order, which keeps tiles compact
@@ -473,7 +469,7 @@ def objects(coord, instance, instance_class, instance_size=None, radius=CONTACT_
     rotating merge loop) and the Open3D clean-up of every support (:716-720) are not reproduced; the OBB merging of test.py:294-326 is
     the next step, merge_objects, on this function's output.
     Raises as contacts() does; ValueError for an instance_class / instance_size that is not [I]."""
-    _check_labelled(coord, instance, "objects")
+    _check_tensors("objects", coord, instance, "label")
     dev = coord.device
     if not isinstance(instance_class, torch.Tensor) or instance_class.dim() != 1 or instance_class.dtype not in (torch.int32, torch.int64):
         raise ValueError("objects: instance_class must be an int32 / int64 tensor [I]")
@@ -504,34 +500,13 @@ MERGE_MIN_NEIGHBORS = 10    # test.py:312
 LAST_MERGE = {"launches": 0, "readbacks": 0}   # of the most recent label_boxes() / merge_objects() call (tools/bench_merge.py)
 
 
-def _merge_call(dev, name, *args):
-    LAST_MERGE["launches"] += 1
-    if dev.index == torch.cuda.current_device():
-        _lib.call(name, *args, device=dev)
-    else:
-        with torch.cuda.device(dev):
-            _lib.call(name, *args, device=dev)
-
-
-def _label_count(n_labels, who, name="n_labels"):
-    if n_labels is None:
-        return None
-    if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
-        raise TypeError(f"{who}: {name} must be an int, got {type(n_labels).__name__}")
-    if n_labels < 0:
-        raise ValueError(f"{who}: {name} must be >= 0, got {n_labels}")
-    if n_labels > MAX_LABELS:
-        raise ValueError(f"{who}: {n_labels} labels: at most {MAX_LABELS}")
-    return int(n_labels)
-
-
 def _boxes(xyz, label, n_labels, dev):
     """the launch of label_boxes on checked, contiguous inputs -> (lo, hi, size)"""
     lo = torch.full((n_labels, 3), float("inf"), dtype=torch.float32, device=dev)
     hi = torch.full((n_labels, 3), float("-inf"), dtype=torch.float32, device=dev)
     size = torch.zeros(n_labels, dtype=torch.int32, device=dev)
     if xyz.shape[0] > 0 and n_labels > 0:
-        _merge_call(dev, "pointops2_label_boxes_launcher", xyz.shape[0], n_labels, ptr(xyz), ptr(label), ptr(lo), ptr(hi), ptr(size))
+        _launch(LAST_MERGE, dev, "pointops2_label_boxes_launcher", xyz.shape[0], n_labels, ptr(xyz), ptr(label), ptr(lo), ptr(hi), ptr(size))
     return lo, hi, size
 
 
@@ -543,8 +518,8 @@ def label_boxes(xyz, label, n_labels=None):
     values, csrc/boxes.hip); -0.0 counts as +0.0, so compare by value.  A label without a point keeps +inf / -inf / 0.
     Raises before any launch: RuntimeError for a CPU tensor or mismatched devices; TypeError / ValueError for a wrong dtype or shape, a
     label outside -1 .. I-1, non-finite coordinates or I > MAX_LABELS.  N = 0 or I = 0 launches nothing."""
-    _check_labelled(xyz, label, "label_boxes")
-    n_labels = _label_count(n_labels, "label_boxes")
+    _check_tensors("label_boxes", xyz, label, "label")
+    n_labels = _label_count("label_boxes", n_labels)
     dev, n = xyz.device, xyz.shape[0]
     LAST_MERGE["launches"], LAST_MERGE["readbacks"] = 0, 0
     if n == 0:
@@ -554,10 +529,7 @@ def label_boxes(xyz, label, n_labels=None):
     head = torch.cat([label.min()[None].long(), label.max()[None].long(), torch.isfinite(xyz).all()[None].long()]).cpu().numpy()
     LAST_MERGE["readbacks"] += 1
     l_min, l_max, all_finite = int(head[0]), int(head[1]), bool(head[2])
-    if n_labels is None:
-        n_labels = _label_count(max(l_max + 1, 0), "label_boxes")
-    if l_min < -1 or l_max >= n_labels:
-        raise ValueError(f"label_boxes: label values must be in -1 .. {n_labels - 1}, got {l_min} .. {l_max}")
+    n_labels = _label_range("label_boxes", n_labels, l_min, l_max)
     if not all_finite:
         raise ValueError("label_boxes: xyz must be finite")
     return _boxes(xyz, label, n_labels, dev)
@@ -658,7 +630,7 @@ def merge_objects(coord, obj, n_objects=None, radius=MERGE_RADIUS, overlap=MERGE
 
     The reference builds two trimesh boxes and one dense cdist per pair of sets in every rotation.  Here the device computes, once: the
     box and size of every object (label_boxes), the row of objects within `radius` of every point (csrc/boxes.hip on the grid of
-    csrc/dbscan.hip; strict <, as `< pc_thre`), and - with torch - the table of distinct (object, row) patterns of the border points with
+    csrc/radius_grid.h; strict <, as `< pc_thre`), and - with torch - the table of distinct (object, row) patterns of the border points with
     their counts.  ONE read-back of boxes, sizes and patterns later merge_sets runs the whole loop on the host; two read-backs in all
     (LAST_MERGE), whatever the number of objects.  Distances are evaluated in fp32 as ((dx*dx) + (dy*dy)) + (dz*dz) < fp32(radius)^2
     (the reference: float64 cdist), so a pair within about 1e-6 of the radius may fall on the other side.  Not reproduced: the Open3D
@@ -666,12 +638,9 @@ def merge_objects(coord, obj, n_objects=None, radius=MERGE_RADIUS, overlap=MERGE
     taken as the box of the bounds (min / max per axis), its published behaviour, which no fixture here pins.
     Raises as contacts() does, before any launch.  N = 0 or no point in an object: no set, nothing launched."""
     who = "merge_objects"
-    _check_labelled(coord, obj, who)
-    r = _positive_finite(radius, who, "radius")
-    with np.errstate(all="ignore"):
-        if not np.isfinite(r * r) or not r * r > 0:
-            raise ValueError(f"{who}: radius must be finite and > 0 when squared in fp32, got {radius}")
-    n_objects = _label_count(n_objects, who, "n_objects")
+    _check_tensors(who, coord, obj, "label")
+    r, r2 = _radius(who, radius)
+    n_objects = _label_count(who, n_objects, "n_objects")
     merge_sets(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0), np.zeros(0), np.zeros((0, 0), np.int32), np.zeros(0), overlap, min_neighbors)  # the settings
     dev, n = coord.device, coord.shape[0]
     LAST_MERGE["launches"], LAST_MERGE["readbacks"] = 0, 0
@@ -685,35 +654,17 @@ def merge_objects(coord, obj, n_objects=None, radius=MERGE_RADIUS, overlap=MERGE
     coord = coord.contiguous()
     label = obj.to(torch.int32).contiguous()
 
-    # one read-back up front: the object range, the points that take part and their bounding box
-    member = label >= 0
-    inf = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
-    lo_all = torch.where(member[:, None], coord, inf).amin(0)
-    hi_all = torch.where(member[:, None], coord, -inf).amax(0)
-    finite = torch.isfinite(coord).all()
-    head = torch.cat([label.min()[None].double(), label.max()[None].double(), member.sum()[None].double(), finite[None].double(),
-                      lo_all.double(), hi_all.double()]).cpu().numpy()
     LAST_MERGE["readbacks"] += 1
-    l_min, l_max, n_valid, all_finite = int(head[0]), int(head[1]), int(head[2]), bool(head[3])
-    if n_objects is None:
-        n_objects = _label_count(max(l_max + 1, 0), who, "n_objects")
-    if l_min < -1 or l_max >= n_objects:
-        raise ValueError(f"{who}: label values must be in -1 .. {n_objects - 1}, got {l_min} .. {l_max}")
-    if not all_finite:
-        raise ValueError(f"{who}: xyz must be finite")
-    words = (n_objects + 31) // 32
-    if n_objects > REG_LABELS and n_valid * words * 4 > MAX_BITMAP_BYTES:
-        raise ValueError(f"{who}: the bitmap of {n_valid} points x {n_objects} labels takes {n_valid * words * 4} bytes, more than {MAX_BITMAP_BYTES}")
+    member, l_min, l_max, n_valid, origin, top = _scan(who, coord, label)
+    n_objects = _label_range(who, n_objects, l_min, l_max, "n_objects")
+    words = _row_words(who, n_valid, n_objects)
     if n_valid == 0 or n_objects == 0:
         return nothing(n_objects)
     cell = float(r) * CELL_MARGIN
-    origin, top = head[4:7], head[7:10]
-    dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
-    if max(dims) > MAX_CELLS_PER_AXIS or dims[0] * dims[1] * dims[2] >= 2 ** 61:
-        raise ValueError(f"{who}: the cloud spans {dims} cells of edge {cell:g}: too many for the 64-bit cell keys")
+    dims = _dims(who, 1, origin, top, cell)
 
     lo, hi, size = _boxes(coord, label, n_objects, dev)
-    slabel, rows = _reach_rows(coord, label, member, n, n_valid, n_objects, origin, cell, dims, np.float32(r * r), dev)
+    slabel, rows = _reach_rows(coord, label, member, n, n_valid, n_objects, origin, cell, dims, r2, dev)
     pat, pat_count = _patterns(slabel, rows)
 
     # the one final read-back: boxes, sizes and patterns as one array of 32-bit words
@@ -729,33 +680,16 @@ def merge_objects(coord, obj, n_objects=None, radius=MERGE_RADIUS, overlap=MERGE
     return table[label.long()], table[:n_objects], torch.from_numpy(boxes).to(dev), len(sets)
 
 
-def _merge_grid(coord, label, member, n, n_valid, origin, cell, dims, dev):
-    """the fixed-radius grid of csrc/dbscan.hip over the labelled points -> (pts [n_valid, 4], sorted_label [n_valid], ranges [18, n_valid])"""
-    group = member.to(torch.int32) - 1                       # one group: 0 for a labelled point, -1 for the others
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
-    _merge_call(dev, "pointops2_dbscan_keys_launcher", n, 1, ptr(coord), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
-                ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
-    skeys, order = torch.sort(keys, stable=True)
-    pts = torch.empty(n_valid, 4, dtype=torch.float32, device=dev)
-    sgroup = torch.empty(n_valid, dtype=torch.int32, device=dev)
-    ranges = torch.empty(18, n_valid, dtype=torch.int32, device=dev)
-    _merge_call(dev, "pointops2_dbscan_prepare_launcher", n, n_valid, dims[0], dims[1], dims[2], ptr(coord), ptr(skeys), ptr(order), ptr(pts),
-                ptr(sgroup), ptr(ranges))
-    return pts, label[order[:n_valid]].contiguous(), ranges
-
-
-def _rows_on_grid(pts, slabel, ranges, n_objects, r2, dev):
-    """-> rows int32 [n_valid, words] in the grid's order: the objects within reach of every point, its own left out"""
-    n_valid = slabel.shape[0]
-    rows = torch.zeros(n_valid, (n_objects + 31) // 32, dtype=torch.int32, device=dev)
-    _merge_call(dev, "pointops2_reach_rows_launcher", n_valid, n_objects, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(rows))
-    return rows
-
-
 def _reach_rows(coord, label, member, n, n_valid, n_objects, origin, cell, dims, r2, dev):
-    """grid keys, prepare and the reach rows -> (sorted_label int32 [n_valid], rows int32 [n_valid, words]), both in the grid's order"""
-    pts, slabel, ranges = _merge_grid(coord, label, member, n, n_valid, origin, cell, dims, dev)
-    return slabel, _rows_on_grid(pts, slabel, ranges, n_objects, r2, dev)
+    """the grid over the labelled points and the reach rows on it -> (sorted_label int32 [n_valid], rows int32 [n_valid, words]: the objects
+    within reach of every point, its own left out), both in the grid's order"""
+    call = functools.partial(_launch, LAST_MERGE, dev)
+    group = member.to(torch.int32) - 1                       # one group: 0 for a point in an object, -1 for the others
+    pts, order, _, ranges = _grid(call, coord, group, 1, n_valid, origin, cell, dims)
+    slabel = label[order[:n_valid]].contiguous()
+    rows = torch.zeros(n_valid, (n_objects + 31) // 32, dtype=torch.int32, device=dev)
+    call("pointops2_reach_rows_launcher", n_valid, n_objects, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(rows))
+    return slabel, rows
 
 
 def _patterns(slabel, rows):

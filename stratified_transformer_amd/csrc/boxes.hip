@@ -13,13 +13,13 @@
 // words per label in LDS, walks its share of the points and flushes only the entries it touched, one global atomic each; above that the
 // atomics go straight to global memory.  Minima, maxima and integer counts do not depend on the order: exact and reproducible.
 //
-// reach_rows: the fixed-radius walk of contacts.hip on the same prepared grid (dbscan.hip's key and prepare kernels, one group), the same
-// strict d2 < r2 and the same fp32 expression ((dx*dx) + (dy*dy)) + (dz*dz) (built with -ffp-contract=off).  Instead of adding to a count
-// table a thread STORES its point's row of ceil(I / 32) words - bit b = some point of label b within reach - with the point's own bit
+// reach_rows: the fixed-radius walk of radius_grid.h (labels_in_reach, as contacts.hip's count) on the same prepared grid (dbscan.hip's
+// key and prepare kernels, one group), the same strict d2 < r2 and the same fp32 expression ((dx*dx) + (dy*dy)) + (dz*dz) (built with
+// -ffp-contract=off).  Instead of adding to a count table a thread STORES its point's row of ceil(I / 32) words - bit b = some point of label b within reach - with the point's own bit
 // cleared.  Up to 64 labels the row is built in two registers and stored once; above that in the point's own row of the caller's zeroed
 // array, which no other thread touches: no atomics, plain vector stores.
 // No kernel waits on another workgroup; ranges are clamped, labels outside [0, n_labels) skipped, nothing is followed outside its array.
-#include "common.h"
+#include "radius_grid.h"
 
 namespace p2 {
 namespace {
@@ -29,9 +29,6 @@ constexpr int LB_TILE = 2048;          // points of one workgroup per trip: a ta
 constexpr int LB_MAX_GRID = 1024;
 constexpr int LB_LDS_LABELS = 1024;    // 7 words per label: 28 KB of LDS
 constexpr int LB_WORDS = 7;            // lo[3], hi[3], size
-constexpr int RR_BLOCK = 256;
-constexpr int RR_ROWS = 9;             // (dy, dz) rows of three x-adjacent cells each, as prepared by dbscan.hip
-constexpr int RR_REG_LABELS = 64;      // rows of up to this many labels stay in registers
 
 // order-preserving signed image of an fp32 bit pattern, and its own inverse
 __device__ __forceinline__ int ordered(int bits) { return bits >= 0 ? bits : bits ^ 0x7fffffff; }
@@ -95,10 +92,10 @@ __global__ __launch_bounds__(LB_BLOCK) void label_boxes_kernel(int n, int n_labe
 }
 
 template <bool REG>
-__global__ __launch_bounds__(RR_BLOCK) void reach_rows_kernel(int n_valid, int n_labels, int words, const float4 *__restrict__ pts,
+__global__ __launch_bounds__(RG_BLOCK) void reach_rows_kernel(int n_valid, int n_labels, int words, const float4 *__restrict__ pts,
                                                               const int *__restrict__ slabel, const int *__restrict__ ranges, float r2,
                                                               unsigned *__restrict__ rows) {
-    const int p = blockIdx.x * RR_BLOCK + threadIdx.x;
+    const int p = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (p >= n_valid) return;
     unsigned *row = rows + (size_t)p * words;
     const int a = slabel[p];
@@ -110,28 +107,7 @@ __global__ __launch_bounds__(RR_BLOCK) void reach_rows_kernel(int n_valid, int n
         return;
     }
     unsigned bits0 = 0, bits1 = 0;
-    const float4 me = pts[p];
-#pragma unroll 1
-    for (int r = 0; r < RR_ROWS; r++) {
-        const int lo = max(ranges[(size_t)(2 * r) * n_valid + p], 0);
-        const int hi = min(ranges[(size_t)(2 * r + 1) * n_valid + p], n_valid);
-        for (int q = lo; q < hi; q++) {
-            const float4 o = pts[q];
-            const float dx = me.x - o.x, dy = me.y - o.y, dz = me.z - o.z;
-            const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
-            if (!(d2 < r2)) continue;
-            const int b = slabel[q];
-            if ((unsigned)b >= (unsigned)n_labels) continue;
-            const unsigned bit = 1u << (b & 31);
-            if (REG) {
-                if (b < 32) bits0 |= bit;
-                else bits1 |= bit;
-            } else {
-                const unsigned v = row[b >> 5];
-                if (!(v & bit)) row[b >> 5] = v | bit;
-            }
-        }
-    }
+    labels_in_reach<REG>(p, n_valid, n_labels, pts, slabel, ranges, r2, bits0, bits1, row);
     const unsigned own = ~(1u << (a & 31));
     if (REG) {
         if (a < 32) bits0 &= own;
@@ -175,8 +151,8 @@ void pointops2_reach_rows_launcher(int n_valid, int n_labels, const float *pts, 
     if (n_valid == 0 || n_labels == 0) return;
     if (pts == nullptr || sorted_label == nullptr || ranges == nullptr || rows == nullptr) { set_error("reach_rows: a NULL array"); return; }
     const int words = div_up(n_labels, 32);
-    const dim3 grid(div_up(n_valid, RR_BLOCK)), block(RR_BLOCK);
-    if (n_labels <= RR_REG_LABELS)
+    const dim3 grid(div_up(n_valid, RG_BLOCK)), block(RG_BLOCK);
+    if (n_labels <= RG_REG_LABELS)
         hipLaunchKernelGGL(reach_rows_kernel<true>, grid, block, 0, st, n_valid, n_labels, words, reinterpret_cast<const float4 *>(pts),
                            sorted_label, ranges, r2, rows);
     else

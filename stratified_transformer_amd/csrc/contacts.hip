@@ -10,11 +10,11 @@
 // every operation rounded on its own (the library is built with -ffp-contract=off), r2 = r * r rounded once by the caller.
 // (xp - xq) and (xq - xp) differ in sign only, so d2(p, q) == d2(q, p) bit for bit.
 //
-// count: the fixed-radius walk of dbscan.hip (its key and prepare kernels are reused as they are: one group, label -1 outside it; cells
-// of edge r * (1 + 2^-7), so every pair the fp32 test accepts is at most one cell apart).  One thread per point in sorted order; a
-// candidate within reach sets bit b in the point's OWN row of labels - two registers for up to 64 labels, otherwise a row of the
-// caller's zeroed [n_valid, ceil(I / 32)] bitmap that no other thread touches, so the row needs no atomics.  After the walk the thread
-// adds its set bits to count with integer atomicAdd: sums of ones, independent of the order in which threads run.
+// count: the fixed-radius walk of radius_grid.h on the grid that dbscan.hip's key and prepare kernels build (reused as they are: one
+// group, label -1 outside it; cells of edge r * (1 + 2^-7), so every pair the fp32 test accepts is at most one cell apart).  One thread
+// per point in sorted order; labels_in_reach sets bit b in the point's OWN row of labels - two registers for up to 64 labels, otherwise
+// a row of the caller's zeroed [n_valid, ceil(I / 32)] bitmap that no other thread touches, so the row needs no atomics.  After the walk
+// the thread adds its set bits to count with integer atomicAdd: sums of ones, independent of the order in which threads run.
 //
 // min_d2: the grid cannot answer it - two sets further apart than a cell never meet in a walk, and their distance is asked for all the
 // same - so it is a tiled sweep over all pairs of the points sorted BY LABEL.  A thread owns one p, the workgroup stages 256 q at a time
@@ -24,48 +24,24 @@
 // The entries only ever fall, so a stale read costs a redundant atomic, never a wrong result, and a minimum does not depend on the
 // order.  d2 is symmetric, so only q-chunks that reach p's tile or lie behind it are swept and both [a, b] and [b, a] are written.
 // No kernel waits on another workgroup; ranges, labels and indices are clamped or skipped, never followed outside their arrays.
-#include "common.h"
+#include "radius_grid.h"
 
 namespace p2 {
 namespace {
 
-constexpr int CT_BLOCK = 256;
-constexpr int CT_ROWS = 9;        // (dy, dz) rows of three x-adjacent cells each, as prepared by dbscan.hip
-constexpr int CT_REG_LABELS = 64; // rows of up to this many labels stay in registers
-constexpr int CT_CHUNK = 4096;    // q of one workgroup of the all-pairs sweep (a multiple of CT_BLOCK)
+constexpr int CT_CHUNK = 4096;    // q of one workgroup of the all-pairs sweep (a multiple of RG_BLOCK)
 
 template <bool REG>
-__global__ __launch_bounds__(CT_BLOCK) void contacts_count_kernel(int n_valid, int n_labels, int words, const float4 *__restrict__ pts,
+__global__ __launch_bounds__(RG_BLOCK) void contacts_count_kernel(int n_valid, int n_labels, int words, const float4 *__restrict__ pts,
                                                                   const int *__restrict__ slabel, const int *__restrict__ ranges, float r2,
                                                                   unsigned *__restrict__ bitmap, int *__restrict__ count) {
-    const int p = blockIdx.x * CT_BLOCK + threadIdx.x;
+    const int p = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (p >= n_valid) return;
     const int a = slabel[p];
     if ((unsigned)a >= (unsigned)n_labels) return;
     unsigned bits0 = 0, bits1 = 0;
     unsigned *row = REG ? nullptr : bitmap + (size_t)p * words;
-    const float4 me = pts[p];
-#pragma unroll 1
-    for (int r = 0; r < CT_ROWS; r++) {
-        const int lo = max(ranges[(size_t)(2 * r) * n_valid + p], 0);
-        const int hi = min(ranges[(size_t)(2 * r + 1) * n_valid + p], n_valid);
-        for (int q = lo; q < hi; q++) {
-            const float4 o = pts[q];
-            const float dx = me.x - o.x, dy = me.y - o.y, dz = me.z - o.z;
-            const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
-            if (!(d2 < r2)) continue;
-            const int b = slabel[q];
-            if ((unsigned)b >= (unsigned)n_labels) continue;
-            const unsigned bit = 1u << (b & 31);
-            if (REG) {
-                if (b < 32) bits0 |= bit;
-                else bits1 |= bit;
-            } else {
-                const unsigned v = row[b >> 5];
-                if (!(v & bit)) row[b >> 5] = v | bit;
-            }
-        }
-    }
+    labels_in_reach<REG>(p, n_valid, n_labels, pts, slabel, ranges, r2, bits0, bits1, row);
     int *mine = count + (size_t)a * n_labels;
     for (int w = 0; w < words; w++) {
         unsigned v = REG ? (w == 0 ? bits0 : bits1) : row[w];
@@ -98,11 +74,11 @@ __device__ __forceinline__ void flush_min(int a, int b, float v, int n_labels, i
     if (a != b) lower_entry(min_bits, (size_t)b * n_labels + a, v);
 }
 
-// lpts [n_valid] = {x, y, z, label as bits}, ascending label.  grid.x: tiles of CT_BLOCK p, grid.y: chunks of CT_CHUNK q
-__global__ __launch_bounds__(CT_BLOCK) void contacts_min_kernel(int n_valid, int n_labels, const float4 *__restrict__ lpts,
+// lpts [n_valid] = {x, y, z, label as bits}, ascending label.  grid.x: tiles of RG_BLOCK p, grid.y: chunks of CT_CHUNK q
+__global__ __launch_bounds__(RG_BLOCK) void contacts_min_kernel(int n_valid, int n_labels, const float4 *__restrict__ lpts,
                                                                 int *__restrict__ min_bits) {
-    __shared__ float4 tile[CT_BLOCK];
-    const int p0 = blockIdx.x * CT_BLOCK, q0 = blockIdx.y * CT_CHUNK;
+    __shared__ float4 tile[RG_BLOCK];
+    const int p0 = blockIdx.x * RG_BLOCK, q0 = blockIdx.y * CT_CHUNK;
     const int q1 = min(q0 + CT_CHUNK, n_valid);
     if (q1 <= p0) return;                                                            // (whole workgroup) the mirrored pairs are swept
     const int p = p0 + threadIdx.x;
@@ -111,12 +87,12 @@ __global__ __launch_bounds__(CT_BLOCK) void contacts_min_kernel(int n_valid, int
     const int a = valid ? __float_as_int(me.w) : -1;
     int cur_b = -1;
     float cur = __builtin_inff();
-    for (int t0 = q0; t0 < q1; t0 += CT_BLOCK) {
+    for (int t0 = q0; t0 < q1; t0 += RG_BLOCK) {
         const int q = t0 + threadIdx.x;
         __syncthreads();
         tile[threadIdx.x] = lpts[q < q1 ? q : q1 - 1];
         __syncthreads();
-        const int len = min(CT_BLOCK, q1 - t0);
+        const int len = min(RG_BLOCK, q1 - t0);
         for (int j = 0; j < len; j++) {
             const float4 o = tile[j];
             const int b = __float_as_int(o.w);
@@ -147,8 +123,8 @@ void pointops2_contacts_count_launcher(int n_valid, int n_labels, const float *p
     if (n_valid == 0 || n_labels == 0) return;
     if ((double)n_labels * n_labels >= 2147483648.0) { set_error("contacts_count: n_labels * n_labels does not fit an int"); return; }
     const int words = div_up(n_labels, 32);
-    const dim3 grid(div_up(n_valid, CT_BLOCK)), block(CT_BLOCK);
-    if (n_labels <= CT_REG_LABELS) {
+    const dim3 grid(div_up(n_valid, RG_BLOCK)), block(RG_BLOCK);
+    if (n_labels <= RG_REG_LABELS) {
         hipLaunchKernelGGL(contacts_count_kernel<true>, grid, block, 0, st, n_valid, n_labels, words, reinterpret_cast<const float4 *>(pts),
                            sorted_label, ranges, r2, bitmap, count);
     } else {
@@ -166,7 +142,7 @@ void pointops2_contacts_min_launcher(int n_valid, int n_labels, const float *lab
     if ((double)n_labels * n_labels >= 2147483648.0) { set_error("contacts_min: n_labels * n_labels does not fit an int"); return; }
     const int chunks = div_up(n_valid, CT_CHUNK);
     if (chunks > 65535) { set_error("contacts_min: more than 65535 * 4096 points"); return; }
-    hipLaunchKernelGGL(contacts_min_kernel, dim3(div_up(n_valid, CT_BLOCK), chunks), dim3(CT_BLOCK), 0, st, n_valid, n_labels,
+    hipLaunchKernelGGL(contacts_min_kernel, dim3(div_up(n_valid, RG_BLOCK), chunks), dim3(RG_BLOCK), 0, st, n_valid, n_labels,
                        reinterpret_cast<const float4 *>(label_pts), reinterpret_cast<int *>(min_d2));
     check_launch();
 }

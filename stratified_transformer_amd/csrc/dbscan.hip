@@ -10,18 +10,9 @@
 // every operation rounded on its own (the library is built with -ffp-contract=off), compared with eps2 = eps * eps rounded once.
 // (xi - xj) and (xj - xi) differ in sign only, so the relation is symmetric.
 //
-// Grid.  Cells of edge `cell` (cluster.py: max eps, widened by 2^-7 so that a pair the fp32 test accepts is never more than one cell
-// apart; cell coordinates are taken in double).  A point's key is ((group * nz + cz) * ny + cy) * nx + cx, so the group is part of
-// the cell: points of other groups are never even candidates.  Points outside every group get the largest key and sort behind the
-// n_valid points that take part.  The caller sorts the keys (a torch sort, as index.hip and dataprep.hip leave their sorts to it).
-// x runs fastest in the key, so the three cells cx-1 .. cx+1 of one (cy, cz) row are ONE run of the sorted points: prepare_kernel
-// finds the nine runs of every point with binary searches over the sorted keys (no dense cell table - a sparse cloud costs nothing)
-// and stores them once; the three walks below (count, hook, label) reuse them.
-//
-// Walk.  One thread per point IN SORTED ORDER, no LDS: the lanes of a wave sit in the same cell or in adjacent ones, so they step
-// through the same candidate rows at the same time and a candidate's 16-byte record {x, y, z, original index} is one broadcast load
-// served by L1 / L2 (100k points are 1.6 MB).  Staging a cell's rows in LDS would save nothing that the cache does not already serve,
-// and one wave per cell would leave most lanes idle on the sparse cells of a class's boundary.
+// Grid and walk: radius_grid.h (the cells, the keys, the nine prepared runs per point and the one-thread-per-point walk over them, shared
+// with contacts.hip and boxes.hip).  The key and prepare kernels that build the grid are here; the three walks below (count, hook,
+// label) are for_each_in_reach<true> with eps2 of the point's group.
 //
 // Components.  parent[] lives in ORIGINAL index space (parent[i] <= i always, -1 for a non-core point), so a root is the smallest
 // core index of its tree and rule 3's numbering needs no second pass.  A round is two kernels:
@@ -32,13 +23,11 @@
 // hooked to), so the number of trees at least halves per round: log2(n) rounds and one that reports no change, where plain
 // neighbour-to-neighbour propagation would need as many rounds as the longest chain has points.  The host reads `changed` back once
 // per round and caps the rounds (cluster.py).  The final labels are unique minima, so they do not depend on thread order.
-#include "common.h"
+#include "radius_grid.h"
 
 namespace p2 {
 namespace {
 
-constexpr int DB_BLOCK = 256;
-constexpr int DB_ROWS = 9;  // (dy, dz) rows of three x-adjacent cells each
 constexpr long long DB_NO_KEY = 0x7fffffffffffffffLL;
 
 struct DbGrid {
@@ -53,9 +42,9 @@ __device__ __forceinline__ int cell_coord(float x, double origin, double cell, i
     return (int)t;
 }
 
-__global__ __launch_bounds__(DB_BLOCK) void dbscan_keys_kernel(int n, int n_groups, const float *__restrict__ xyz,
+__global__ __launch_bounds__(RG_BLOCK) void dbscan_keys_kernel(int n, int n_groups, const float *__restrict__ xyz,
                                                                const int *__restrict__ group, DbGrid gr, long long *__restrict__ keys) {
-    const int i = blockIdx.x * DB_BLOCK + threadIdx.x;
+    const int i = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (i >= n) return;
     const int g = group[i];
     long long key = DB_NO_KEY;
@@ -80,11 +69,11 @@ __device__ __forceinline__ int key_bound(const long long *__restrict__ skeys, in
     return lo;
 }
 
-__global__ __launch_bounds__(DB_BLOCK) void dbscan_prepare_kernel(int n, int n_valid, int nx, int ny, int nz, const float *__restrict__ xyz,
+__global__ __launch_bounds__(RG_BLOCK) void dbscan_prepare_kernel(int n, int n_valid, int nx, int ny, int nz, const float *__restrict__ xyz,
                                                                   const long long *__restrict__ skeys, const long long *__restrict__ order,
                                                                   float4 *__restrict__ pts, int *__restrict__ sgroup,
                                                                   int *__restrict__ ranges) {
-    const int p = blockIdx.x * DB_BLOCK + threadIdx.x;
+    const int p = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (p >= n_valid) return;
     long long i = order[p];
     i = i < 0 ? 0 : i >= n ? n - 1 : i;  // (a permutation of [0, n): never followed outside xyz whatever it holds)
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(DB_BLOCK) void dbscan_prepare_kernel(int n, int n_v
     sgroup[p] = (int)g;
     const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx < nx - 1 ? cx + 1 : nx - 1;
 #pragma unroll
-    for (int r = 0; r < DB_ROWS; r++) {
+    for (int r = 0; r < RG_ROWS; r++) {
         const int y = cy + r % 3 - 1, z = cz + r / 3 - 1;
         int lo = 0, hi = 0;
         if (y >= 0 && y < ny && z >= 0 && z < nz) {
@@ -112,34 +101,16 @@ __global__ __launch_bounds__(DB_BLOCK) void dbscan_prepare_kernel(int n, int n_v
     }
 }
 
-// f(q, j) for every neighbour of sorted point p (rule 1; p itself included): q its sorted position, j its original index
-template <typename F>
-__device__ __forceinline__ void for_each_neighbour(int p, int n_valid, const float4 *__restrict__ pts, const int *__restrict__ ranges,
-                                                   float eps2, F f) {
-    const float4 me = pts[p];
-#pragma unroll 1
-    for (int r = 0; r < DB_ROWS; r++) {
-        const int lo = max(ranges[(size_t)(2 * r) * n_valid + p], 0);
-        const int hi = min(ranges[(size_t)(2 * r + 1) * n_valid + p], n_valid);
-        for (int q = lo; q < hi; q++) {
-            const float4 o = pts[q];
-            const float dx = me.x - o.x, dy = me.y - o.y, dz = me.z - o.z;
-            const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
-            if (d2 <= eps2) f(q, __float_as_int(o.w));
-        }
-    }
-}
-
-__global__ __launch_bounds__(DB_BLOCK) void dbscan_core_kernel(int n, int n_valid, const float4 *__restrict__ pts,
+__global__ __launch_bounds__(RG_BLOCK) void dbscan_core_kernel(int n, int n_valid, const float4 *__restrict__ pts,
                                                                const int *__restrict__ sgroup, const int *__restrict__ ranges,
                                                                const float *__restrict__ eps2, const int *__restrict__ min_samples,
                                                                unsigned char *__restrict__ core_s, unsigned char *__restrict__ core,
                                                                int *__restrict__ parent) {
-    const int p = blockIdx.x * DB_BLOCK + threadIdx.x;
+    const int p = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (p >= n_valid) return;
     const int g = sgroup[p], i = __float_as_int(pts[p].w);
     int count = 0;
-    for_each_neighbour(p, n_valid, pts, ranges, eps2[g], [&](int, int) { count++; });
+    for_each_in_reach<true>(p, n_valid, pts, ranges, eps2[g], [&](int, int) { count++; });
     const bool is_core = count >= min_samples[g];
     core_s[p] = is_core;
     if ((unsigned)i < (unsigned)n) {
@@ -148,17 +119,17 @@ __global__ __launch_bounds__(DB_BLOCK) void dbscan_core_kernel(int n, int n_vali
     }
 }
 
-__global__ __launch_bounds__(DB_BLOCK) void dbscan_hook_kernel(int n, int n_valid, const float4 *__restrict__ pts,
+__global__ __launch_bounds__(RG_BLOCK) void dbscan_hook_kernel(int n, int n_valid, const float4 *__restrict__ pts,
                                                                const int *__restrict__ sgroup, const int *__restrict__ ranges,
                                                                const float *__restrict__ eps2, const unsigned char *__restrict__ core_s,
                                                                int *parent, int *changed) {
-    const int p = blockIdx.x * DB_BLOCK + threadIdx.x;
+    const int p = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (p >= n_valid || !core_s[p]) return;
     const int i = __float_as_int(pts[p].w);
     if ((unsigned)i >= (unsigned)n) return;
     int mine = parent[i];
     bool hooked = false;
-    for_each_neighbour(p, n_valid, pts, ranges, eps2[sgroup[p]], [&](int q, int j) {
+    for_each_in_reach<true>(p, n_valid, pts, ranges, eps2[sgroup[p]], [&](int q, int j) {
         if (!core_s[q] || (unsigned)j >= (unsigned)n) return;
         const int theirs = parent[j];
         if (theirs == mine || (unsigned)theirs >= (unsigned)n || (unsigned)mine >= (unsigned)n) return;
@@ -170,8 +141,8 @@ __global__ __launch_bounds__(DB_BLOCK) void dbscan_hook_kernel(int n, int n_vali
     if (hooked) *changed = 1;
 }
 
-__global__ __launch_bounds__(DB_BLOCK) void dbscan_jump_kernel(int n, int *parent) {
-    const int i = blockIdx.x * DB_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(RG_BLOCK) void dbscan_jump_kernel(int n, int *parent) {
+    const int i = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (i >= n) return;
     int x = parent[i];
     if ((unsigned)x >= (unsigned)n) return;  // not a core point
@@ -183,12 +154,12 @@ __global__ __launch_bounds__(DB_BLOCK) void dbscan_jump_kernel(int n, int *paren
     parent[i] = x;
 }
 
-__global__ __launch_bounds__(DB_BLOCK) void dbscan_label_kernel(int n, int n_valid, const float4 *__restrict__ pts,
+__global__ __launch_bounds__(RG_BLOCK) void dbscan_label_kernel(int n, int n_valid, const float4 *__restrict__ pts,
                                                                 const int *__restrict__ sgroup, const int *__restrict__ ranges,
                                                                 const float *__restrict__ eps2, const unsigned char *__restrict__ core_s,
                                                                 const int *__restrict__ parent, const int *__restrict__ cluster_of_root,
                                                                 int *__restrict__ labels) {
-    const int p = blockIdx.x * DB_BLOCK + threadIdx.x;
+    const int p = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (p >= n_valid) return;
     const int i = __float_as_int(pts[p].w);
     if ((unsigned)i >= (unsigned)n) return;
@@ -198,7 +169,7 @@ __global__ __launch_bounds__(DB_BLOCK) void dbscan_label_kernel(int n, int n_val
         if ((unsigned)root < (unsigned)n) label = cluster_of_root[root];
     } else {
         int best = 0x7fffffff;
-        for_each_neighbour(p, n_valid, pts, ranges, eps2[sgroup[p]], [&](int q, int j) {
+        for_each_in_reach<true>(p, n_valid, pts, ranges, eps2[sgroup[p]], [&](int q, int j) {
             if (!core_s[q] || (unsigned)j >= (unsigned)n) return;
             const int root = parent[j];
             if ((unsigned)root >= (unsigned)n) return;
@@ -229,7 +200,7 @@ void pointops2_dbscan_keys_launcher(int n, int n_groups, const float *xyz, const
     if (n_groups < 1 || nx < 1 || ny < 1 || nz < 1 || !(cell > 0.0)) { set_error("dbscan_keys: need n_groups, nx, ny, nz >= 1 and cell > 0"); return; }
     if ((double)n_groups * nx * ny * nz >= 4.0e18) { set_error("dbscan_keys: n_groups * nx * ny * nz does not fit the 64-bit cell keys"); return; }
     const DbGrid gr{ox, oy, oz, cell, nx, ny, nz};
-    hipLaunchKernelGGL(dbscan_keys_kernel, dim3(div_up(n, DB_BLOCK)), dim3(DB_BLOCK), 0, st, n, n_groups, xyz, group, gr, keys);
+    hipLaunchKernelGGL(dbscan_keys_kernel, dim3(div_up(n, RG_BLOCK)), dim3(RG_BLOCK), 0, st, n, n_groups, xyz, group, gr, keys);
     check_launch();
 }
 
@@ -239,7 +210,7 @@ void pointops2_dbscan_prepare_launcher(int n, int n_valid, int nx, int ny, int n
     if (const char *bad = dbscan_bad_counts(n, n_valid)) { set_error(bad); return; }
     if (n_valid == 0) return;
     if (nx < 1 || ny < 1 || nz < 1) { set_error("dbscan_prepare: need nx, ny, nz >= 1"); return; }
-    hipLaunchKernelGGL(dbscan_prepare_kernel, dim3(div_up(n_valid, DB_BLOCK)), dim3(DB_BLOCK), 0, st, n, n_valid, nx, ny, nz, xyz, sorted_keys,
+    hipLaunchKernelGGL(dbscan_prepare_kernel, dim3(div_up(n_valid, RG_BLOCK)), dim3(RG_BLOCK), 0, st, n, n_valid, nx, ny, nz, xyz, sorted_keys,
                        order, reinterpret_cast<float4 *>(pts), sorted_group, ranges);
     check_launch();
 }
@@ -249,7 +220,7 @@ void pointops2_dbscan_core_launcher(int n, int n_valid, const float *pts, const 
     const hipStream_t st = begin_launch().stream;
     if (const char *bad = dbscan_bad_counts(n, n_valid)) { set_error(bad); return; }
     if (n_valid == 0) return;
-    hipLaunchKernelGGL(dbscan_core_kernel, dim3(div_up(n_valid, DB_BLOCK)), dim3(DB_BLOCK), 0, st, n, n_valid,
+    hipLaunchKernelGGL(dbscan_core_kernel, dim3(div_up(n_valid, RG_BLOCK)), dim3(RG_BLOCK), 0, st, n, n_valid,
                        reinterpret_cast<const float4 *>(pts), sorted_group, ranges, eps2, min_samples, sorted_core, core, parent);
     check_launch();
 }
@@ -260,9 +231,9 @@ void pointops2_dbscan_round_launcher(int n, int n_valid, const float *pts, const
     if (const char *bad = dbscan_bad_counts(n, n_valid)) { set_error(bad); return; }
     if (hipMemsetAsync(changed, 0, sizeof(int), st) != hipSuccess) { check_launch(); return; }
     if (n_valid == 0) return;
-    hipLaunchKernelGGL(dbscan_hook_kernel, dim3(div_up(n_valid, DB_BLOCK)), dim3(DB_BLOCK), 0, st, n, n_valid,
+    hipLaunchKernelGGL(dbscan_hook_kernel, dim3(div_up(n_valid, RG_BLOCK)), dim3(RG_BLOCK), 0, st, n, n_valid,
                        reinterpret_cast<const float4 *>(pts), sorted_group, ranges, eps2, sorted_core, parent, changed);
-    hipLaunchKernelGGL(dbscan_jump_kernel, dim3(div_up(n, DB_BLOCK)), dim3(DB_BLOCK), 0, st, n, parent);
+    hipLaunchKernelGGL(dbscan_jump_kernel, dim3(div_up(n, RG_BLOCK)), dim3(RG_BLOCK), 0, st, n, parent);
     check_launch();
 }
 
@@ -271,7 +242,7 @@ void pointops2_dbscan_label_launcher(int n, int n_valid, const float *pts, const
     const hipStream_t st = begin_launch().stream;
     if (const char *bad = dbscan_bad_counts(n, n_valid)) { set_error(bad); return; }
     if (n_valid == 0) return;
-    hipLaunchKernelGGL(dbscan_label_kernel, dim3(div_up(n_valid, DB_BLOCK)), dim3(DB_BLOCK), 0, st, n, n_valid,
+    hipLaunchKernelGGL(dbscan_label_kernel, dim3(div_up(n_valid, RG_BLOCK)), dim3(RG_BLOCK), 0, st, n, n_valid,
                        reinterpret_cast<const float4 *>(pts), sorted_group, ranges, eps2, sorted_core, parent, cluster_of_root, labels);
     check_launch();
 }

@@ -15,6 +15,8 @@ The host reference is the literal loop of tests/merge_oracle.py (per pair of set
 what the reference's cdist does) on the same machine, on a scene of `--host-points` points, where one pair's matrix still fits;
 `small_*` are the device's times on that same scene and `small_agrees` says whether both give the same sets and boxes."""
 import argparse
+import ctypes
+import functools
 import json
 import os
 import statistics
@@ -29,6 +31,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_contacts import box, device_ms  # noqa: E402
 from stratified_transformer_amd import cluster  # noqa: E402
+from stratified_transformer_amd._lib import ptr  # noqa: E402
 
 
 def make_scene(points, spacing, seed=0):
@@ -62,11 +65,23 @@ def parts_ms(coord, obj, n_objects, reps, warmup):
     cell = float(r) * cluster.CELL_MARGIN
     origin = coord[member].amin(0).double().cpu().numpy()
     top = coord[member].amax(0).double().cpu().numpy()
-    dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
+    dims = cluster._dims("bench_merge", 1, origin, top, cell)
+    call = functools.partial(cluster._launch, cluster.LAST_MERGE, dev)
+    words = (n_objects + 31) // 32
+
+    def grid():
+        pts, order, _, ranges = cluster._grid(call, coord, member.to(torch.int32) - 1, 1, n_valid, origin, cell, dims)
+        return pts, label[order[:n_valid]].contiguous(), ranges
+
+    def reach_rows():
+        rows = torch.zeros(n_valid, words, dtype=torch.int32, device=dev)
+        call("pointops2_reach_rows_launcher", n_valid, n_objects, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(np.float32(r * r)), ptr(rows))
+        return rows
+
     out = {}
     out["boxes_ms"], _, (lo, hi, size) = device_ms(lambda: cluster._boxes(coord, label, n_objects, dev), reps, warmup)
-    out["grid_ms"], _, (pts, slabel, ranges) = device_ms(lambda: cluster._merge_grid(coord, label, member, n, n_valid, origin, cell, dims, dev), reps, warmup)
-    out["rows_ms"], _, rows = device_ms(lambda: cluster._rows_on_grid(pts, slabel, ranges, n_objects, np.float32(r * r), dev), reps, warmup)
+    out["grid_ms"], _, (pts, slabel, ranges) = device_ms(grid, reps, warmup)
+    out["rows_ms"], _, rows = device_ms(reach_rows, reps, warmup)
     out["unique_ms"], _, (pat, count) = device_ms(lambda: cluster._patterns(slabel, rows), reps, warmup)
     tables = (lo.cpu().numpy(), hi.cpu().numpy(), size.cpu().numpy(), pat[:, 0].cpu().numpy(), pat[:, 1:].cpu().numpy(), count.cpu().numpy())
     times = []
