@@ -88,6 +88,53 @@ def _variant_scene(case):
     return blocks, variants, L, h
 
 
+def _expand_cells(plan):
+    """the pair list a cell plan stands for, in (query, tile order): arrays (query, key, r0, r1, r2)"""
+    nC = plan.n_cells
+    qstart, kbase, pbase = (_np(t) for t in (plan.cell_qstart, plan.cell_kbase, plan.cell_pbase))
+    order, keys, relp = _np(plan.cell_order), _np(plan.cell_keys), _np(plan.relp).view(np.uint32)
+    rows = []
+    for c in range(nC):
+        nq, nk = qstart[c + 1] - qstart[c], kbase[c + 1] - kbase[c]
+        tile = relp[pbase[c]: pbase[c] + nq * nk].reshape(nq, nk)
+        qi = np.repeat(order[qstart[c]: qstart[c + 1]], nk).reshape(nq, nk)
+        kj = np.tile(keys[kbase[c]: kbase[c + 1]], nq).reshape(nq, nk)
+        keep = (tile >> 31) == 0
+        rows.append(np.stack([qi[keep], kj[keep], tile[keep] & 255, (tile[keep] >> 8) & 255, (tile[keep] >> 16) & 255], 1))
+    allp = np.concatenate(rows).astype(np.int64)
+    return allp[np.argsort(allp[:, 0], kind="stable")]
+
+
+def check_cell_plan_is_the_pair_list(blk, L, cap):
+    """Every (query, key, rel-pos index clamped to [0, L)) of the block's CSR pair list appears exactly once in the cell tiles of its
+    plan, in the same per-query order - a pair the list holds twice is there twice; each query and each cell id exactly once; the work
+    order is a permutation, largest tile first; the pieces of a parent share one key list.  Returns the expanded tiles
+    (query, key, r0, r1, r2), int64 [M, 5]."""
+    plan = blk.cells
+    n = plan.n_points
+    if cap:
+        assert np.diff(_np(plan.cell_qstart)[: plan.n_cells + 1]).max() <= cap
+    got = _expand_cells(plan)
+    i0, i1, rel = _np(blk.index_0).astype(np.int64), _np(blk.index_1).astype(np.int64), np.clip(_np(blk.rel_idx), 0, L - 1)
+    assert got.shape[0] == i0.shape[0]
+    assert np.array_equal(got[:, 0], i0) and np.array_equal(got[:, 1], i1) and np.array_equal(got[:, 2:], rel)
+    assert np.array_equal(np.sort(_np(plan.cell_order)), np.arange(n))
+    perm = _np(plan.cell_perm)[: plan.n_cells]
+    assert np.array_equal(np.sort(perm), np.arange(plan.n_cells))
+    tiles = np.diff(_np(plan.cell_pbase)[: plan.n_cells + 1])
+    assert np.all(np.diff(tiles[perm]) <= 0) and tiles.sum() == plan.n_pairs
+    assert np.diff(_np(plan.cell_kbase)[: plan.n_cells + 1]).max() == plan.nk_max
+    # parents: the uncut cells; the pieces of a parent are consecutive cell ids with one key list (contiguous tiles)
+    pf, kb, keys = _np(plan.parent_first)[: plan.n_parents + 1], _np(plan.cell_kbase), _np(plan.cell_keys)
+    assert pf[0] == 0 and pf[-1] == plan.n_cells and np.all(np.diff(pf) > 0)
+    if not cap:
+        assert plan.n_parents == plan.n_cells
+    for a, b in zip(pf[:-1], pf[1:]):
+        for piece in range(a + 1, b):
+            assert np.array_equal(keys[kb[piece]: kb[piece + 1]], keys[kb[a]: kb[a + 1]])
+    return got
+
+
 def _pair_list(blk, L):
     """index_0, index_1, offsets, rel_idx (clamped as the model asserts it) of a block, numpy"""
     return (_np(blk.index_0).astype(np.int32), _np(blk.index_1), _np(blk.offsets), np.clip(_np(blk.rel_idx), 0, L - 1).astype(np.int32))

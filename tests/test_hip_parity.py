@@ -11,7 +11,8 @@ import pytest
 import torch
 
 from oracle import pointops_ref as ref
-from tests.cell_edges import _CELL_GRADS, _CELL_VARIANT_SCENES, _cell_launch, _cell_nk, _cell_operands, _cell_plans, _cell_scene, _oracle_attention
+from tests.cell_edges import (_CELL_GRADS, _CELL_VARIANT_SCENES, _cell_launch, _cell_nk, _cell_operands, _cell_plans, _cell_scene, _oracle_attention,
+                              check_cell_plan_is_the_pair_list)
 from tests.util import dev, random_csr_problem, window_problem
 
 pytestmark = pytest.mark.gpu
@@ -1038,23 +1039,6 @@ def test_fused_window_attention_matches_the_operator_chain(P, case):
 
 
 # ---- window-centric ("cell") attention: csrc/index.hip cells + csrc/cell_attn.hip ----------------------
-def _expand_cells(plan):
-    """the pair list a cell plan stands for, in (query, tile order): arrays (query, key, r0, r1, r2)"""
-    nC = plan.n_cells
-    qstart, kbase, pbase = (_np(t) for t in (plan.cell_qstart, plan.cell_kbase, plan.cell_pbase))
-    order, keys, relp = _np(plan.cell_order), _np(plan.cell_keys), _np(plan.relp).view(np.uint32)
-    rows = []
-    for c in range(nC):
-        nq, nk = qstart[c + 1] - qstart[c], kbase[c + 1] - kbase[c]
-        tile = relp[pbase[c]: pbase[c] + nq * nk].reshape(nq, nk)
-        qi = np.repeat(order[qstart[c]: qstart[c + 1]], nk).reshape(nq, nk)
-        kj = np.tile(keys[kbase[c]: kbase[c + 1]], nq).reshape(nq, nk)
-        keep = (tile >> 31) == 0
-        rows.append(np.stack([qi[keep], kj[keep], tile[keep] & 255, (tile[keep] >> 8) & 255, (tile[keep] >> 16) & 255], 1))
-    allp = np.concatenate(rows).astype(np.int64)
-    return allp[np.argsort(allp[:, 0], kind="stable")]
-
-
 @pytest.mark.parametrize("n,nbatch,w,quant,cap", [(6000, 1, 0.16, 0.01, 0), (5000, 3, 0.32, 0.02, 8), (900, 2, 0.64, 0.04, 4), (6000, 1, 0.16, 0.01, 16)])
 def test_cell_plan_is_the_pair_list(n, nbatch, w, quant, cap):
     """Every (query, key, rel-pos index) of the CSR pair list - itself bit-identical to the oracle's restatement of
@@ -1063,27 +1047,8 @@ def test_cell_plan_is_the_pair_list(n, nbatch, w, quant, cap):
     L = 2 * int((2 * w + 1e-4) // quant)
     _, _, even, odd = _cell_scene(n, nbatch, w, quant, seed=n, L=L, cap=cap)
     for blk in (even, odd):
-        plan = blk.cells
-        if cap:
-            assert np.diff(_np(plan.cell_qstart)[: plan.n_cells + 1]).max() <= cap
-        got = _expand_cells(plan)
-        i0, i1, rel = _np(blk.index_0).astype(np.int64), _np(blk.index_1).astype(np.int64), np.clip(_np(blk.rel_idx), 0, L - 1)
-        assert got.shape[0] == i0.shape[0]
-        assert np.array_equal(got[:, 0], i0) and np.array_equal(got[:, 1], i1) and np.array_equal(got[:, 2:], rel)
-        assert np.array_equal(np.sort(_np(plan.cell_order)), np.arange(n))
-        perm = _np(plan.cell_perm)[: plan.n_cells]
-        assert np.array_equal(np.sort(perm), np.arange(plan.n_cells))
-        tiles = np.diff(_np(plan.cell_pbase)[: plan.n_cells + 1])
-        assert np.all(np.diff(tiles[perm]) <= 0) and tiles.sum() == plan.n_pairs
-        assert np.diff(_np(plan.cell_kbase)[: plan.n_cells + 1]).max() == plan.nk_max
-        # parents: the uncut cells; the pieces of a parent are consecutive cell ids with one key list (contiguous tiles)
-        pf, kb, keys = _np(plan.parent_first)[: plan.n_parents + 1], _np(plan.cell_kbase), _np(plan.cell_keys)
-        assert pf[0] == 0 and pf[-1] == plan.n_cells and np.all(np.diff(pf) > 0)
-        if not cap:
-            assert plan.n_parents == plan.n_cells
-        for a, b in zip(pf[:-1], pf[1:]):
-            for piece in range(a + 1, b):
-                assert np.array_equal(keys[kb[piece]: kb[piece + 1]], keys[kb[a]: kb[a + 1]])
+        assert blk.cells.n_points == n
+        check_cell_plan_is_the_pair_list(blk, L, cap)
 
 
 @pytest.mark.parametrize("case", ["s3dis_stage0_h3", "batch3_h6_L64", "scannet_L80_h3", "big_cells_two_chunks_h2", "coarse_h12"])
