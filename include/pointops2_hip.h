@@ -41,8 +41,8 @@ const char *pointops2_last_error(void);
 /* library/ABI version, bumped when a signature changes (3: pointops2_launch_opts replaces the per-fact setters; 5: the packed
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
  * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points, the two
- * pointops2_contacts_*_launcher and pointops2_label_boxes_launcher / pointops2_reach_rows_launcher after them - a caller that needs
- * them looks the symbols up. */
+ * pointops2_contacts_*_launcher, pointops2_label_boxes_launcher / pointops2_reach_rows_launcher and the three
+ * pointops2_supports_*_launcher after them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -525,6 +525,33 @@ void pointops2_contacts_min_launcher(int n_valid, int n_labels, const float *lab
 void pointops2_label_boxes_launcher(int n, int n_labels, const float *xyz, const int *label, float *lo, float *hi, int *size);
 void pointops2_reach_rows_launcher(int n_valid, int n_labels, const float *pts, const int *sorted_label, const int *ranges, float r2,
                                    unsigned *rows);
+
+/* ---- The clean-up of every box support (util/train_utils.py:716-723: Open3D's voxel_down_sample(0.04), then
+ * remove_radius_outlier(nb_points = 3, radius = 0.1), per support) ----
+ * Per object, independent of every other object (stratified_transformer_amd/cluster.py: clean_supports drives the steps and owns every
+ * buffer; the sort between keys and means is the caller's, and it must be STABLE):
+ *   keys:  xyz [n, 3] float, object [n] in any order, lo [n_objects, 3] (float) = the componentwise minimum of every object's points, as
+ *          pointops2_label_boxes_launcher writes it.  keys [n] (long long) = ((o * nz + vz) * ny + vy) * nx + vx with
+ *          v = floor((double(p) - (double(lo[o]) - voxel * 0.5)) / voxel) per axis, in float64 with a true division, clamped to the
+ *          axis; a point whose object is outside [0, n_objects) gets the largest key.  The caller chooses nx, ny, nz so that no object
+ *          spans more voxels (floor(extent of the scene / voxel) + 2) and n_objects * nx * ny * nz < 2^61.
+ *   means: sorted_keys [n] and order [n] (long long) = the keys in ascending order and the stable sort's permutation, the n_valid points of
+ *          the objects first; slot [n_valid] (long long) = the number of voxel heads before every sorted position (a position is a head
+ *          when its key differs from its predecessor's), n_voxels their total.  The head's thread walks its run: mean [n_voxels, 3]
+ *          (float) = the float64 sum of the voxel's points in ascending original index, from 0.0, divided by their number as a double and
+ *          rounded once to float; mean_object / mean_size [n_voxels] (int) = the voxel's object and its number of points.  No atomics: the
+ *          result does not depend on the order in which threads run.  A run is walked by one thread however long it is.
+ *   count: behind pointops2_dbscan_keys_launcher / _prepare_launcher run on the means with group = object and a cell of at least
+ *          r * (1 + 2^-7): pts and ranges as prepare wrote them.  keep [n_means] (unsigned char), by ORIGINAL index of the mean: 1 when
+ *          the number of means q of the same object with d2(p, q) < r2 (strict; p itself counts) is greater than nb_points, in fp32 with
+ *          d2 = ((dx*dx) + (dy*dy)) + (dz*dz), dx = xp - xq, no fused operation - the test of pointops2_reach_rows_launcher.
+ * No kernel waits on another workgroup; ranges are clamped, indices and slots checked, never followed outside the arrays.  n = 0,
+ * n_valid = 0, n_voxels = 0 or n_means = 0 launches nothing; a NULL array records an error. */
+void pointops2_supports_keys_launcher(int n, int n_objects, const float *xyz, const int *object, const float *lo, double voxel, int nx, int ny,
+                                      int nz, long long *keys);
+void pointops2_supports_means_launcher(int n, int n_valid, int n_voxels, const float *xyz, const int *object, const long long *sorted_keys,
+                                       const long long *order, const long long *slot, float *mean, int *mean_object, int *mean_size);
+void pointops2_supports_count_launcher(int n_means, const float *pts, const int *ranges, float r2, int nb_points, unsigned char *keep);
 
 /* ---- Whole-scene evaluation: the crop cover and the vote of the reference's test loop (test_backup.py:238-251, :278-281) ----
  * One crop of a part of n points (stratified_transformer_amd/evaluate.py drives the loop and owns every buffer):

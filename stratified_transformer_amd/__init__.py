@@ -6,8 +6,8 @@ windowed sparse-attention hot path, behind the reference's own o
     stratified_transformer_amd.compat          providers of the third-party names the model imports
                                                (torch_scatter.scatter_softmax, torch_geometric.nn.voxel_grid, ...)
     stratified_transformer_amd.cluster         the steps behind the model: dbscan / instances on csrc/dbscan.hip, contacts / objects on csrc/contacts.hip,
-                                               label_boxes / merge_objects on csrc/boxes.hip and the host-side box_detection
-                                               (all seven also exported here)
+                                               label_boxes / merge_objects on csrc/boxes.hip, clean_supports / box_supports on
+                                               csrc/supports.hip and the host-side box_detection (all nine also exported here)
     stratified_transformer_amd.evaluate        whole-scene evaluation on csrc/evaltile.hip: crop cover, votes, IoU (scene_eval also exported here)
     stratified_transformer_amd.layers          installable fast BasicLayer.forward / WindowAttention.forward (same signatures)
     include/pointops2_hip.h                    the C ABI underneath (libpointops2_hip.so)
@@ -17,13 +17,14 @@ model/stratified_transformer.py imports and runs unmodified under PyTorch-ROCm.
 """
 import sys
 
-__all__ = ["install", "build", "dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "scene_eval"]
+__all__ = ["install", "build", "dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "scene_eval",
+           "clean_supports", "box_supports"]
 
 
 def __getattr__(name):
-    # dbscan / instances / contacts / objects / label_boxes / merge_objects / box_detection live in .cluster, which needs torch: bound on
-    # first use, as every other submodule is imported on demand
-    if name in ("dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection"):
+    # dbscan / instances / contacts / objects / label_boxes / merge_objects / box_detection / clean_supports / box_supports live in
+    # .cluster, which needs torch: bound on first use, as every other submodule is imported on demand
+    if name in ("dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "clean_supports", "box_supports"):
         from . import cluster
         return getattr(cluster, name)
     if name == "scene_eval":

@@ -108,6 +108,9 @@ SIGNATURES = {
     "pointops2_contacts_min_launcher": [I, I, P, P],
     "pointops2_label_boxes_launcher": [I, I, P, P, P, P, P],
     "pointops2_reach_rows_launcher": [I, I, P, P, P, F, P],
+    "pointops2_supports_keys_launcher": [I, I, P, P, P, D, I, I, I, P],
+    "pointops2_supports_means_launcher": [I, I, I, P, P, P, P, P, P, P, P],
+    "pointops2_supports_count_launcher": [I, P, P, F, I, P],
     "pointops2_evaltile_seed_dist_launcher": [I, I, P, P, P, P, P, P],
     "pointops2_evaltile_update_launcher": [I, I, I, P, P, P, P, P],
     "pointops2_evaltile_vote_launcher": [I, I, I, I, P, P, P, P, P],

@@ -20,8 +20,12 @@ The step behind that, the OBB merging of test.py:294-326 (test_iou.py:373-406), 
 csrc/boxes.hip; `merge_sets` is its rotating loop on plain host arrays, `box_detection` the score test_iou.py:455-464 takes from the
 merged boxes (util/evaluation.py).  trimesh is not needed (and not imported).
 
-dbscan, contacts / objects and merge_objects stand on ONE fixed-radius grid: `_scan` (the read-back up front), `_dims` and `_grid` (cell
-keys, torch's sort, the nine prepared runs per point) build it here, csrc/radius_grid.h walks it on the device for all three.
+Between the two the reference cleans every support with Open3D (util/train_utils.py:716-723: voxel means, then radius outliers):
+`clean_supports` on csrc/supports.hip; `box_supports` is instances -> objects -> clean_supports in one call, what `instantiation_eval`
+returns.  Open3D is not needed (and not imported).
+
+dbscan, contacts / objects, clean_supports and merge_objects stand on ONE fixed-radius grid: `_scan` (the read-back up front), `_dims` and `_grid` (cell
+keys, torch's sort, the nine prepared runs per point) build it here, csrc/radius_grid.h walks it on the device for all of them.
 """
 import contextlib
 import ctypes
@@ -466,8 +470,8 @@ def objects(coord, instance, instance_class, instance_size=None, radius=CONTACT_
     quadratic min_d2 sweep is not run).  Two deliberate departures from the reference: with no link at all it raises IndexError
     (pair_list[0], :670) - here the result is zero objects; its merge loop runs len + 100 iterations (:666) and equals the components
     only when that reaches its fixed point - here the result is always the components.  The reference's list order (an artefact of the
-    rotating merge loop) and the Open3D clean-up of every support (:716-720) are not reproduced; the OBB merging of test.py:294-326 is
-    the next step, merge_objects, on this function's output.
+    rotating merge loop) is not reproduced; the Open3D clean-up of every support (:716-720) is clean_supports, on this function's
+    output; the OBB merging of test.py:294-326 is the step behind that, merge_objects.
     Raises as contacts() does; ValueError for an instance_class / instance_size that is not [I]."""
     _check_tensors("objects", coord, instance, "label")
     dev = coord.device
@@ -500,13 +504,13 @@ MERGE_MIN_NEIGHBORS = 10    # test.py:312
 LAST_MERGE = {"launches": 0, "readbacks": 0}   # of the most recent label_boxes() / merge_objects() call (tools/bench_merge.py)
 
 
-def _boxes(xyz, label, n_labels, dev):
-    """the launch of label_boxes on checked, contiguous inputs -> (lo, hi, size)"""
+def _boxes(xyz, label, n_labels, dev, counter=LAST_MERGE):
+    """the launch of label_boxes on checked, contiguous inputs, counted in `counter` -> (lo, hi, size)"""
     lo = torch.full((n_labels, 3), float("inf"), dtype=torch.float32, device=dev)
     hi = torch.full((n_labels, 3), float("-inf"), dtype=torch.float32, device=dev)
     size = torch.zeros(n_labels, dtype=torch.int32, device=dev)
     if xyz.shape[0] > 0 and n_labels > 0:
-        _launch(LAST_MERGE, dev, "pointops2_label_boxes_launcher", xyz.shape[0], n_labels, ptr(xyz), ptr(label), ptr(lo), ptr(hi), ptr(size))
+        _launch(counter, dev, "pointops2_label_boxes_launcher", xyz.shape[0], n_labels, ptr(xyz), ptr(label), ptr(lo), ptr(hi), ptr(size))
     return lo, hi, size
 
 
@@ -747,3 +751,173 @@ def box_detection(pred_box, gt_box, overlap_threshold=0.5):
     precision = len(tp) / (len(tp) + len(fp)) if tp or fp else None
     recall = len(tp) / (len(tp) + fn) if len(tp) + fn else None
     return tp, fp, fn, precision, recall
+
+
+# ---- the clean-up of every support behind the grouping (util/train_utils.py:716-723), on csrc/supports.hip ----
+SUPPORT_VOXEL = 0.04        # util/train_utils.py:717 voxel_down_sample(voxel_size=0.04)
+SUPPORT_RADIUS = 0.1        # util/train_utils.py:718 remove_radius_outlier(nb_points=3, radius=0.1)
+SUPPORT_NB_POINTS = 3
+LAST_SUPPORTS = {"launches": 0, "readbacks": 0}   # of the most recent clean_supports() / box_supports() call (tools/bench_supports.py)
+
+
+def _support_settings(who, voxel, radius, nb_points):
+    """-> (voxel as a float, fp32(radius), its fp32 square, nb_points as an int), validated"""
+    r, r2 = _radius(who, radius)
+    if isinstance(voxel, bool) or not isinstance(voxel, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: voxel must be a number, got {type(voxel).__name__}")
+    if not np.isfinite(voxel) or not voxel > 0:
+        raise ValueError(f"{who}: voxel must be finite and > 0, got {voxel}")
+    if isinstance(nb_points, bool) or not isinstance(nb_points, (int, np.integer)) or nb_points < 0 or nb_points >= 2 ** 31:
+        raise ValueError(f"{who}: nb_points must be an int >= 0, got {nb_points!r}")
+    return float(voxel), r, r2, int(nb_points)
+
+
+def _voxel_dims(who, n_objects, origin, top, voxel):
+    """-> the voxels per axis [nx, ny, nz] that no object of the scene exceeds: an object's voxel origin lies half a voxel below its own
+    minimum, so its points reach at most floor(extent / voxel + 0.5) <= floor(scene extent / voxel) + 1; ValueError when the keys of
+    n_objects such blocks do not fit 64 bits"""
+    with np.errstate(all="ignore"):
+        extent = np.floor((np.asarray(top, np.float64) - np.asarray(origin, np.float64)) / voxel)
+    if not np.all(extent < MAX_CELLS_PER_AXIS):
+        raise ValueError(f"{who}: the cloud spans {extent.tolist()} voxels of edge {voxel:g}: too many for the 64-bit voxel keys")
+    dims = [int(e) + 2 for e in extent]
+    if max(dims) > MAX_CELLS_PER_AXIS or n_objects * dims[0] * dims[1] * dims[2] >= 2 ** 61:
+        raise ValueError(f"{who}: {n_objects} objects in a cloud of {dims} voxels of edge {voxel:g}: too many for the 64-bit voxel keys")
+    return dims
+
+
+def _voxel_means(call, coord, label, n_objects, n_valid, lo, voxel, dims):
+    """voxel keys from every object's own minimum `lo` (device), torch's stable sort, the head flags and their scan
+    -> (sorted_keys int64 [N], order int64 [N], slot int64 [n_valid], n_voxels: a 0-d device tensor - the caller reads it back)"""
+    n = coord.shape[0]
+    keys = torch.empty(n, dtype=torch.int64, device=coord.device)
+    call("pointops2_supports_keys_launcher", n, n_objects, ptr(coord), ptr(label), ptr(lo), ctypes.c_double(voxel), dims[0], dims[1], dims[2],
+         ptr(keys))
+    skeys, order = torch.sort(keys, stable=True)
+    head = torch.ones(n_valid, dtype=torch.int64, device=coord.device)
+    head[1:] = skeys[1:n_valid] != skeys[:n_valid - 1]
+    slot = torch.cumsum(head, 0) - 1                         # the exclusive count of heads, at a head
+    return skeys, order, slot, slot[-1] + 1
+
+
+def _means(call, coord, label, n_valid, n_voxels, skeys, order, slot):
+    """-> (mean float32 [V, 3], mean_object int32 [V], mean_size int32 [V]) in the order of the keys: object, then vz, vy, vx"""
+    dev = coord.device
+    mean = torch.empty(n_voxels, 3, dtype=torch.float32, device=dev)
+    mean_object = torch.empty(n_voxels, dtype=torch.int32, device=dev)
+    mean_size = torch.empty(n_voxels, dtype=torch.int32, device=dev)
+    call("pointops2_supports_means_launcher", coord.shape[0], n_valid, n_voxels, ptr(coord), ptr(label), ptr(skeys), ptr(order), ptr(slot),
+         ptr(mean), ptr(mean_object), ptr(mean_size))
+    return mean, mean_object, mean_size
+
+
+def _inliers(call, pts, ranges, r2, nb_points):
+    """-> keep uint8 [V] by original index of the mean: more than nb_points means of its object within reach, itself included"""
+    n_means = pts.shape[0]
+    keep = torch.zeros(n_means, dtype=torch.uint8, device=pts.device)
+    call("pointops2_supports_count_launcher", n_means, ptr(pts), ptr(ranges), ctypes.c_float(r2), nb_points, ptr(keep))
+    return keep
+
+
+def _survivors(keep, mean_object, n_objects):
+    """-> (kept: 0-d int64 on the device, alive bool [O]: the objects with a surviving mean); the caller reads kept and alive.sum() back"""
+    per_object = torch.zeros(n_objects, dtype=torch.int64, device=keep.device).index_add_(0, mean_object.long(), keep.long())
+    return keep.sum(), per_object > 0
+
+
+def _compact(mean, mean_object, keep, alive, n_kept, n_alive):
+    """the kept means in their order, their objects renumbered over the surviving objects -> (points, object, source); sizes from the host,
+    so no step waits for the device"""
+    dev, n_means = mean.device, mean.shape[0]
+    keep = keep.bool()
+    at = torch.where(keep, torch.cumsum(keep.long(), 0) - 1, torch.full((), n_kept, dtype=torch.int64, device=dev))
+    index = torch.empty(n_kept + 1, dtype=torch.int64, device=dev).index_copy_(0, at, torch.arange(n_means, device=dev))[:n_kept]  # (the last slot takes the rest)
+    number = torch.cumsum(alive.long(), 0) - 1
+    to = torch.where(alive, number, torch.full((), n_alive, dtype=torch.int64, device=dev))
+    source = torch.empty(n_alive + 1, dtype=torch.int64, device=dev).index_copy_(0, to, torch.arange(alive.shape[0], device=dev))[:n_alive]
+    return mean[index], number[mean_object[index].long()].to(torch.int32), source.to(torch.int32)
+
+
+def clean_supports(coord, obj, n_objects=None, voxel=SUPPORT_VOXEL, radius=SUPPORT_RADIUS, nb_points=SUPPORT_NB_POINTS):
+    """The clean-up that `instantiation_eval` gives every support before it returns it (util/train_utils.py:716-723: Open3D's
+    voxel_down_sample(voxel_size=0.04), then remove_radius_outlier(nb_points=3, radius=0.1); a support left empty is dropped), on the
+    output of objects(): coord [N, 3] fp32 and obj int32 / int64 [N] in -1 .. O-1 (GPU; -1 = in no object), O = n_objects or obj.max() + 1
+    -> (points float32 [K, 3], object int32 [K] in 0 .. O'-1, source int32 [O']: the original number of every surviving object,
+    n_objects int = O').  points / object feed merge_objects(points, object, n_objects) unchanged.
+
+    Per object, independently of all others (csrc/supports.hip):
+      1. voxel index: origin = double(lo) - voxel * 0.5 per axis, lo the OBJECT's own componentwise minimum (label_boxes; Open3D:
+         GetMinBound() - voxel_size * 0.5); v = floor((double(p) - origin) / voxel), all in float64 with a true division;
+      2. every occupied voxel gives one point: the float64 sum of its points in ascending original index, from 0.0, divided by their number
+         as a double, rounded ONCE to fp32 - the departure: Open3D keeps doubles, every later step here takes fp32;
+      3. a mean is kept when MORE than nb_points means of its object lie at d2 < fp32(radius)^2 of it, itself included; fp32,
+         d2 = ((dx*dx) + (dy*dy)) + (dz*dz), as every radius test of this module;
+      4. output order: ascending object, then ascending voxel (vz, vy, vx), vx fastest; an object with no surviving mean is dropped and the
+         others are renumbered 0 .. O'-1 in ascending original number.
+    UNPINNED - Open3D is on no machine the tests run on, no fixture records it: the half-voxel origin, floor, the mean in double and the
+    self-inclusive count > nb_points are Open3D's published behaviour; whether its radius search is strict or inclusive at exactly
+    `radius` is not known - strict here, as everywhere in this module; its output order is a hash map's iteration order and unspecified -
+    ours is rule 4.
+    Three read-backs whatever the number of objects (LAST_SUPPORTS): the range / bounding box up front, the number of voxels, the numbers
+    of kept means and surviving objects.  The boxes stay on the device.
+    Raises before any launch: RuntimeError for a CPU tensor or mismatched devices; TypeError / ValueError for a wrong dtype or shape, a
+    label outside -1 .. O-1, non-finite coordinates, voxel or radius not finite and > 0, nb_points not an int >= 0, O > MAX_LABELS;
+    ValueError when O * nx * ny * nz >= 2^61 for the voxels (or the cells of the radius grid) of the scene's box, or an axis exceeds
+    MAX_CELLS_PER_AXIS.  N = 0, no point in an object or no surviving mean: empty tensors, nothing launched where nothing is to do."""
+    who = "clean_supports"
+    _check_tensors(who, coord, obj, "label")
+    voxel, r, r2, nb_points = _support_settings(who, voxel, radius, nb_points)
+    n_objects = _label_count(who, n_objects, "n_objects")
+    dev, n = coord.device, coord.shape[0]
+    LAST_SUPPORTS["launches"], LAST_SUPPORTS["readbacks"] = 0, 0
+
+    def nothing():
+        return (torch.zeros(0, 3, dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                torch.zeros(0, dtype=torch.int32, device=dev), 0)
+
+    if n == 0:
+        return nothing()
+    coord = coord.contiguous()
+    label = obj.to(torch.int32).contiguous()
+
+    LAST_SUPPORTS["readbacks"] += 1
+    _, l_min, l_max, n_valid, origin, top = _scan(who, coord, label)
+    n_objects = _label_range(who, n_objects, l_min, l_max, "n_objects")
+    if n_valid == 0 or n_objects == 0:
+        return nothing()
+    vdims = _voxel_dims(who, n_objects, origin, top, voxel)
+    cell = float(r) * CELL_MARGIN
+    dims = _dims(who, n_objects, origin, top, cell)
+
+    call = functools.partial(_launch, LAST_SUPPORTS, dev)
+    lo, _, _ = _boxes(coord, label, n_objects, dev, LAST_SUPPORTS)
+    skeys, order, slot, n_voxels = _voxel_means(call, coord, label, n_objects, n_valid, lo, voxel, vdims)
+    n_voxels = int(n_voxels.item())
+    LAST_SUPPORTS["readbacks"] += 1
+    mean, mean_object, _ = _means(call, coord, label, n_valid, n_voxels, skeys, order, slot)
+
+    # the means lie inside the scene's box (a mean of fp32 values, rounded to fp32, does not leave their range), so its grid serves
+    pts, _, _, ranges = _grid(call, mean, mean_object, n_objects, n_voxels, origin, cell, dims)
+    keep = _inliers(call, pts, ranges, r2, nb_points)
+    kept, alive = _survivors(keep, mean_object, n_objects)
+    n_kept, n_alive = (int(v) for v in torch.stack([kept, alive.sum()]).cpu().numpy())
+    LAST_SUPPORTS["readbacks"] += 1
+    if n_kept == 0:
+        return nothing()
+    return _compact(mean, mean_object, keep, alive, n_kept, n_alive) + (n_alive,)
+
+
+def box_supports(coord, shift, pred, eps=None, min_samples=None, min_points=None, contact_radius=CONTACT_RADIUS, share=CONTACT_SHARE,
+                 face_classes=FACE_CLASSES, edge_faces=None, voxel=SUPPORT_VOXEL, radius=SUPPORT_RADIUS, nb_points=SUPPORT_NB_POINTS):
+    """What `instantiation_eval` (util/train_utils.py:547-737) returns, in one call: instances() -> objects() -> clean_supports().
+    coord, shift [N, 3] fp32 and pred int32 / int64 [N] on the GPU; eps, min_samples, min_points as instances() takes them,
+    contact_radius (objects' radius), share, face_classes, edge_faces as objects() does, voxel, radius, nb_points as clean_supports().
+    -> (points float32 [K, 3], object int32 [K], source int32 [O'], n_objects int - clean_supports' tuple: the cleaned supports, which
+        feed merge_objects(points, object, n_objects) unchanged -, instance int32 [N], point_object int32 [N]: the per-point results of
+        the first two steps, point_object in objects()' numbering, which `source` maps the cleaned objects back to).
+    LAST, LAST_CONTACTS and LAST_SUPPORTS hold the counters of the three steps.  Raises as they do; the clean-up's settings are checked
+    before the first step."""
+    _support_settings("clean_supports", voxel, radius, nb_points)
+    instance, instance_class, instance_size = instances(coord, shift, pred, eps, min_samples, min_points)
+    point_object, _, n_objects = objects(coord, instance, instance_class, instance_size, contact_radius, share, face_classes, edge_faces)
+    return clean_supports(coord, point_object, n_objects, voxel, radius, nb_points) + (instance, point_object)
