@@ -572,7 +572,12 @@ void pointops2_supports_count_launcher(int n_means, const float *pts, const int 
  * -1 by the caller) takes the largest row number per point and is back at -1 when the call has run.  An index outside [0, n_points)
  * sets status[0] = 2 (device int) and its row is skipped.  Bitwise reproducible; no [m, classes] temporary.  m = 0 is a no-op.
  * n < 1, voxel_max outside [1, n], n_points < 1, classes outside [1, 64], an unknown row_type or a NULL array record an error and
- * launch nothing.  No kernel waits on another workgroup; no index is followed outside its array. */
+ * launch nothing.  No kernel waits on another workgroup; no index is followed outside its array.
+ * Vote with shifts (the fork's test_iou.py:284-285): pointops2_evaltile_vote_shift_launcher is the vote above with a second accumulator -
+ * the row that writes pred[idx[r], :] also does pred_shift[idx[r], 0:3] += float(shift[r, 0:3]) (shift [m, 3] of shift_row_type
+ * POINTOPS2_ROWS_F32, _F16 or _BF16, chosen independently of row_type; converted exactly, one fp32 add; pred_shift fp32 [n_points, 3]).
+ * One winner per point serves both tensors (the last position, as above); a losing row or a bad index writes to neither.  Every
+ * classes in [1, 64] writes all three components.  Same validation, errors, status and stamp contract as the vote; no float atomics. */
 int pointops2_evaltile_max_parts(void);
 void pointops2_evaltile_seed_dist_launcher(int n, int is_f64, const void *coord, const double *priority, double *part_value, int *part_index,
                                            long long *seed, void *dist);
@@ -580,6 +585,8 @@ void pointops2_evaltile_update_launcher(int n, int voxel_max, int is_f64, const 
                                         unsigned char *covered, int *report);
 void pointops2_evaltile_vote_launcher(int m, int classes, int n_points, int row_type, const void *logits, const long long *idx, int *stamp,
                                       float *pred, int *status);
+void pointops2_evaltile_vote_shift_launcher(int m, int classes, int n_points, int row_type, const void *logits, int shift_row_type, const void *shift,
+                                            const long long *idx, int *stamp, float *pred, float *pred_shift, int *status);
 
 #ifdef __cplusplus
 }

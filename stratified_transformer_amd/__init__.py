@@ -7,8 +7,10 @@ windowed sparse-attention hot path, behind the reference's own o
                                                (torch_scatter.scatter_softmax, torch_geometric.nn.voxel_grid, ...)
     stratified_transformer_amd.cluster         the steps behind the model: dbscan / instances on csrc/dbscan.hip, contacts / objects on csrc/contacts.hip,
                                                label_boxes / merge_objects on csrc/boxes.hip, clean_supports / box_supports on
-                                               csrc/supports.hip and the host-side box_detection (all nine also exported here)
-    stratified_transformer_amd.evaluate        whole-scene evaluation on csrc/evaltile.hip: crop cover, votes, IoU (scene_eval also exported here)
+                                               csrc/supports.hip, the host-side box_detection and detect_boxes = box_supports + merge_objects
+                                               (all ten also exported here)
+    stratified_transformer_amd.evaluate        whole-scene evaluation on csrc/evaltile.hip: crop cover, votes with shifts, IoU; the fork's
+                                               detection pass in one call (scene_eval, scene_predict, dense_points, detect_scene also exported here)
     stratified_transformer_amd.layers          installable fast BasicLayer.forward / WindowAttention.forward (same signatures)
     include/pointops2_hip.h                    the C ABI underneath (libpointops2_hip.so)
 
@@ -18,18 +20,19 @@ model/stratified_transformer.py imports and runs unmodified under PyTorch-ROCm.
 import sys
 
 __all__ = ["install", "build", "dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "scene_eval",
-           "clean_supports", "box_supports"]
+           "clean_supports", "box_supports", "scene_predict", "dense_points", "detect_boxes", "detect_scene"]
 
 
 def __getattr__(name):
-    # dbscan / instances / contacts / objects / label_boxes / merge_objects / box_detection / clean_supports / box_supports live in
-    # .cluster, which needs torch: bound on first use, as every other submodule is imported on demand
-    if name in ("dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "clean_supports", "box_supports"):
+    # dbscan / instances / contacts / objects / label_boxes / merge_objects / box_detection / clean_supports / box_supports / detect_boxes
+    # live in .cluster, which needs torch: bound on first use, as every other submodule is imported on demand
+    if name in ("dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "clean_supports", "box_supports",
+                "detect_boxes"):
         from . import cluster
         return getattr(cluster, name)
-    if name == "scene_eval":
+    if name in ("scene_eval", "scene_predict", "dense_points", "detect_scene"):
         from . import evaluate
-        return evaluate.scene_eval
+        return getattr(evaluate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

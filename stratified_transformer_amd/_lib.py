@@ -114,6 +114,7 @@ SIGNATURES = {
     "pointops2_evaltile_seed_dist_launcher": [I, I, P, P, P, P, P, P],
     "pointops2_evaltile_update_launcher": [I, I, I, P, P, P, P, P],
     "pointops2_evaltile_vote_launcher": [I, I, I, I, P, P, P, P, P],
+    "pointops2_evaltile_vote_shift_launcher": [I, I, I, I, P, I, P, P, P, P, P, P],
 }
 # entry points with a non-void result
 RESULTS = {

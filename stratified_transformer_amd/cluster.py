@@ -921,3 +921,35 @@ def box_supports(coord, shift, pred, eps=None, min_samples=None, min_points=None
     instance, instance_class, instance_size = instances(coord, shift, pred, eps, min_samples, min_points)
     point_object, _, n_objects = objects(coord, instance, instance_class, instance_size, contact_radius, share, face_classes, edge_faces)
     return clean_supports(coord, point_object, n_objects, voxel, radius, nb_points) + (instance, point_object)
+
+
+# ---- the whole pass behind the model: supports, then boxes (test_iou.py:356-422) ----
+def detect_settings(voxel=SUPPORT_VOXEL, radius=SUPPORT_RADIUS, nb_points=SUPPORT_NB_POINTS, merge_radius=MERGE_RADIUS, overlap=MERGE_OVERLAP,
+                    min_neighbors=MERGE_MIN_NEIGHBORS, **instance_settings):
+    """detect_boxes' settings that can be checked without the scene - the clean-up's and the merge's - raise here as their steps would, and
+    a keyword that detect_boxes does not take raises TypeError.  The per-class settings of instances() and the settings of objects() need
+    the scene's classes and are checked by those steps, before their own first launch."""
+    unknown = sorted(set(instance_settings) - {"eps", "min_samples", "min_points", "contact_radius", "share", "face_classes", "edge_faces"})
+    if unknown:
+        raise TypeError(f"detect_boxes: unexpected settings {unknown}")
+    _support_settings("clean_supports", voxel, radius, nb_points)
+    _radius("merge_objects", merge_radius)
+    merge_sets(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0), np.zeros(0), np.zeros((0, 0), np.int32), np.zeros(0), overlap, min_neighbors)
+
+
+def detect_boxes(coord, shift, pred, eps=None, min_samples=None, min_points=None, contact_radius=CONTACT_RADIUS, share=CONTACT_SHARE,
+                 face_classes=FACE_CLASSES, edge_faces=None, voxel=SUPPORT_VOXEL, radius=SUPPORT_RADIUS, nb_points=SUPPORT_NB_POINTS,
+                 merge_radius=MERGE_RADIUS, overlap=MERGE_OVERLAP, min_neighbors=MERGE_MIN_NEIGHBORS):
+    """From the model's per-point outputs to the predicted boxes (test_iou.py:356-422) in one call: box_supports(), then
+    merge_objects(points, object, n_objects) on its cleaned supports.  coord, shift [N, 3] fp32 and pred int32 / int64 [N] on the GPU; the
+    settings up to nb_points are box_supports', merge_radius / overlap / min_neighbors are merge_objects' radius / overlap / min_neighbors.
+    -> (boxes float32 [S, 6] = lo | hi per merged set, the reference's pred_box; points float32 [K, 3]: the cleaned support points;
+        merged int32 [K]: the set of every support point; n_sets int = S; instance int32 [N], point_object int32 [N]: box_supports' per-point
+        results).
+    Pure composition: no step of its own, it raises as its parts do; the clean-up's and the merge's settings are checked before the first
+    launch.  Fewer than two supports are not a special case: their zero or one boxes are returned."""
+    detect_settings(voxel=voxel, radius=radius, nb_points=nb_points, merge_radius=merge_radius, overlap=overlap, min_neighbors=min_neighbors)
+    points, obj, _, n_objects, instance, point_object = box_supports(coord, shift, pred, eps, min_samples, min_points, contact_radius, share,
+                                                                      face_classes, edge_faces, voxel, radius, nb_points)
+    merged, _, boxes, n_sets = merge_objects(points, obj, n_objects, merge_radius, overlap, min_neighbors)
+    return boxes, points, merged, n_sets, instance, point_object

@@ -17,6 +17,18 @@
 // point (integer atomicMax, order-independent), vote_add_kernel lets row r write when stamp[idx[r]] == r and resets the stamp to
 // -1 for the next call.  (A losing row reads either the winner's number or -1: neither is its own.)  A row is spread over LPR
 // lanes of one wave, one class per lane: the max and the sum are xor butterflies, so the result does not depend on the launch.
+//
+// Vote with shifts (the fork's second accumulator, test_iou.py:284-285, :337-338): `pred[idx, :] += softmax(logits)` and
+// `pred_shift[idx, :] += shift` are two indexed assignments over the same idx, so one winner per point serves both.  The choice is ONE
+// fused kernel, vote_shift_add_kernel, not a second small one: whether row r wins is known only while stamp[idx[r]] still holds r, and
+// the winner's reset to -1 is what makes the next call work - a second kernel would either need the reset moved into it (the
+// shift-less path, which must stay as it is, resets in vote_add_kernel) or a second stamp pass.  Fused, every lane of the row reads
+// the stamp in one wave-wide load that precedes the reset in program order (a row never straddles a wave: LPR divides 64), and the
+// row's idx and stamp are read once for both tensors.  The shift components ride on lanes 0..2 of the row: LPR is at least 8, so
+// these lanes exist whatever `classes` is - `classes` of 1 or 2 leaves them without a logit (inactive in the softmax, -inf / 0 as any
+// lane beyond `classes`), but they are lanes of a writer row all the same.  The softmax is vote_add_kernel's, operation for
+// operation; the shift is converted to fp32 (exact from f16 / bf16) and added with one fp32 add.  The shift's storage type is a
+// run-time argument (a wave-uniform branch around one load), so the kernel is instantiated per lane width and logit type only.
 #include <hip/hip_fp16.h>
 #include "common.h"
 
@@ -186,6 +198,56 @@ void launch_vote_add(hipStream_t st, int m, int classes, int n_points, const voi
         hipLaunchKernelGGL((vote_add_kernel<64, T>), dim3(div_up(m, ET_BLOCK / 64)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
 }
 
+__device__ __forceinline__ float shift_value(const void *p, int type, size_t k) {
+    if (type == POINTOPS2_ROWS_F32) return ((const float *)p)[k];
+    if (type == POINTOPS2_ROWS_F16) return __half2float(((const __half *)p)[k]);
+    return __uint_as_float((unsigned)((const unsigned short *)p)[k] << 16);  // bf16
+}
+
+// vote_add_kernel with the second accumulator: the writer row also adds its three shift components, on lanes 0..2 of the row
+template <int LPR, typename T>
+__global__ __launch_bounds__(ET_BLOCK) void vote_shift_add_kernel(int m, int classes, int n_points, const T *__restrict__ logits, int shift_type,
+                                                                  const void *__restrict__ shift, const long long *__restrict__ idx, int *stamp,
+                                                                  float *__restrict__ pred, float *__restrict__ pred_shift) {
+    static_assert(LPR >= 3 && WAVE % LPR == 0, "a row holds the three shift lanes and stays inside one wave");
+    const int r = blockIdx.x * (ET_BLOCK / LPR) + threadIdx.x / LPR, c = threadIdx.x % LPR;
+    long long i = -1;
+    if (r < m) i = idx[r];
+    const bool writer = i >= 0 && i < n_points && stamp[i] == r;  // every lane of the row, before lane 0 resets the stamp below
+    const bool active = writer && c < classes;
+    float x = active ? logit_value(logits, (size_t)r * classes + c) : -INFINITY;
+    float mx = x;
+#pragma unroll
+    for (int s = 1; s < LPR; s <<= 1) mx = fmaxf(mx, __shfl_xor(mx, s, WAVE));
+    const float e = active ? expf(x - mx) : 0.0f;
+    float sum = e;
+#pragma unroll
+    for (int s = 1; s < LPR; s <<= 1) sum += __shfl_xor(sum, s, WAVE);
+    if (active) pred[(size_t)i * classes + c] += e / sum;
+    if (writer && c < 3) pred_shift[(size_t)i * 3 + c] += shift_value(shift, shift_type, (size_t)r * 3 + c);
+    if (writer && c == 0) stamp[i] = -1;
+}
+
+template <typename T>
+void launch_vote_shift_add(hipStream_t st, int m, int classes, int n_points, const void *logits, int shift_type, const void *shift,
+                           const long long *idx, int *stamp, float *pred, float *pred_shift) {
+    const T *lg = (const T *)logits;
+    if (classes <= 8)
+        hipLaunchKernelGGL((vote_shift_add_kernel<8, T>), dim3(div_up(m, ET_BLOCK / 8)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
+                           shift, idx, stamp, pred, pred_shift);
+    else if (classes <= 16)
+        hipLaunchKernelGGL((vote_shift_add_kernel<16, T>), dim3(div_up(m, ET_BLOCK / 16)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
+                           shift, idx, stamp, pred, pred_shift);
+    else if (classes <= 32)
+        hipLaunchKernelGGL((vote_shift_add_kernel<32, T>), dim3(div_up(m, ET_BLOCK / 32)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
+                           shift, idx, stamp, pred, pred_shift);
+    else
+        hipLaunchKernelGGL((vote_shift_add_kernel<64, T>), dim3(div_up(m, ET_BLOCK / 64)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
+                           shift, idx, stamp, pred, pred_shift);
+}
+
+inline bool known_row_type(int t) { return t == POINTOPS2_ROWS_F32 || t == POINTOPS2_ROWS_F16 || t == POINTOPS2_ROWS_BF16; }
+
 }  // namespace
 }  // namespace p2
 
@@ -239,6 +301,23 @@ void pointops2_evaltile_vote_launcher(int m, int classes, int n_points, int row_
     if (row_type == POINTOPS2_ROWS_F32) launch_vote_add<float>(st, m, classes, n_points, logits, idx, stamp, pred);
     else if (row_type == POINTOPS2_ROWS_F16) launch_vote_add<__half>(st, m, classes, n_points, logits, idx, stamp, pred);
     else launch_vote_add<unsigned short>(st, m, classes, n_points, logits, idx, stamp, pred);
+    check_launch();
+}
+
+void pointops2_evaltile_vote_shift_launcher(int m, int classes, int n_points, int row_type, const void *logits, int shift_row_type, const void *shift,
+                                            const long long *idx, int *stamp, float *pred, float *pred_shift, int *status) {
+    const hipStream_t st = begin_launch().stream;
+    if (m < 0 || n_points < 1 || classes < 1 || classes > 64) { set_error("evaltile_vote_shift: need m >= 0, n_points >= 1 and 1 <= classes <= 64"); return; }
+    if (!known_row_type(row_type) || !known_row_type(shift_row_type)) {
+        set_error("evaltile_vote_shift: row_type and shift_row_type must be POINTOPS2_ROWS_F32, _F16 or _BF16");
+        return;
+    }
+    if (m == 0) return;
+    if (!logits || !shift || !idx || !stamp || !pred || !pred_shift || !status) { set_error("evaltile_vote_shift: a NULL array"); return; }
+    hipLaunchKernelGGL(vote_stamp_kernel, dim3(div_up(m, ET_BLOCK)), dim3(ET_BLOCK), 0, st, m, n_points, idx, stamp, status);
+    if (row_type == POINTOPS2_ROWS_F32) launch_vote_shift_add<float>(st, m, classes, n_points, logits, shift_row_type, shift, idx, stamp, pred, pred_shift);
+    else if (row_type == POINTOPS2_ROWS_F16) launch_vote_shift_add<__half>(st, m, classes, n_points, logits, shift_row_type, shift, idx, stamp, pred, pred_shift);
+    else launch_vote_shift_add<unsigned short>(st, m, classes, n_points, logits, shift_row_type, shift, idx, stamp, pred, pred_shift);
     check_launch();
 }
 

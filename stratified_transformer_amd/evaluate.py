@@ -10,11 +10,17 @@ Kept quirk of the reference: `pred[idx_part, :] += pred_part` (:281) is an index
 appears more than once in one batch (overlapping crops of one batch: the normal case) only one of its rows is added.  CPU torch lets
 the row at the last position write, and so does SceneVotes.add; CUDA may pick any of them.
 
+The DCF fork's detection pass (test_iou.py / test.py) is here as well: its model returns (logits, shift) and its loop keeps a second
+accumulator, `pred_shift[idx_part, :] += shift_part` - SceneVotes(..., shifts=True) and scene_predict, on the fused vote of
+csrc/evaltile.hip -; dense_points is its loader's outlier filter, detect_scene the whole pass from the scene to the boxes and their score.
+
 Not covered: the test-time transforms (host numpy callables; the caller sums scene_eval over them), file reading / writing, the
-meters and the logging, and the fork's DCF evaluation."""
+meters and the logging, the fork's accumulation of the score over scenes and its .obj exports."""
+import collections
+
 import torch
 
-from . import _lib, pointops
+from . import _lib, cluster, pointops
 from ._lib import ptr
 from .dataprep import _coord, voxelize
 
@@ -101,35 +107,81 @@ def crop_cover(coord, voxel_max, priority=None):
 class SceneVotes:
     """The per-point vote tensor of test_backup.py:231, :278-283.  add(logits, idx): pred[idx, :] += softmax(logits, -1) with the
     reference's indexed-assignment semantics - when an index repeats inside one call only the row at its LAST position writes.
-    logits [m, classes] f32 / f16 / bf16 (arithmetic fp32), idx int64 [m], on the GPU.  result(): pred / (pred.sum(-1)[:, None] + 1e-8)."""
+    logits [m, classes] f32 / f16 / bf16 (arithmetic fp32), idx int64 [m], on the GPU.  result(): pred / (pred.sum(-1)[:, None] + 1e-8);
+    labels(): the arg-max of the raw votes, int64 [n_points] (the fork's `pred.max(1)[1]`, test_iou.py:343).
 
-    def __init__(self, n_points, classes, device="cuda"):
+    shifts=True: the fork's second accumulator (test_iou.py:267, :285, :338) - the object also owns `shift`, float32 [n_points, 3], and is a
+    SceneShiftVotes, whose add(logits, idx, shift) takes the model's shift rows [m, 3] (f32 / f16 / bf16, independent of the logits' type)
+    and does `shift[idx, :] += shift_rows` under the same rule in the same kernel: the row that writes the votes of a point writes its
+    shift.  Without shifts nothing changes: the same launcher, the same kernels."""
+
+    def __new__(cls, n_points=None, classes=None, device="cuda", shifts=False):
+        return object.__new__(SceneShiftVotes if shifts and cls is SceneVotes else cls)
+
+    def __init__(self, n_points, classes, device="cuda", shifts=False):
         n_points, classes = int(n_points), int(classes)
         if n_points < 1 or not 1 <= classes <= MAX_CLASSES:
             raise ValueError(f"SceneVotes: need n_points >= 1 and 1 <= classes <= {MAX_CLASSES}, got {n_points}, {classes}")
         self.pred = torch.zeros(n_points, classes, dtype=torch.float32, device=device)
         self._stamp = torch.full((n_points,), -1, dtype=torch.int32, device=device)   # largest row number per point inside a call
         self._status = torch.zeros(1, dtype=torch.int32, device=device)
+        self.shift = torch.zeros(n_points, 3, dtype=torch.float32, device=device) if shifts else None
 
-    def add(self, logits, idx):
+    def _rows(self, logits, idx):
         _gpu(logits, "SceneVotes.add: logits")
         _gpu(idx, "SceneVotes.add: idx")
-        n_points, classes = self.pred.shape
+        classes = self.pred.shape[1]
         if logits.dim() != 2 or logits.shape[1] != classes or logits.dtype not in _lib.ROW_TYPES:
             raise ValueError(f"SceneVotes.add: logits must be [m, {classes}] float32 / float16 / bfloat16, got {logits.dtype} {tuple(logits.shape)}")
         if idx.dtype != torch.int64 or idx.shape != (logits.shape[0],):
             raise ValueError(f"SceneVotes.add: idx must be int64 [{logits.shape[0]}], got {idx.dtype} {tuple(idx.shape)}")
         if logits.device != self.pred.device or idx.device != self.pred.device:
             raise RuntimeError(f"SceneVotes.add: logits on {logits.device}, idx on {idx.device}, the votes on {self.pred.device}")
-        logits, idx = logits.detach().contiguous(), idx.contiguous()
+        return logits.detach().contiguous(), idx.contiguous()
+
+    def add(self, logits, idx):
+        logits, idx = self._rows(logits, idx)
+        n_points, classes = self.pred.shape
         with torch.cuda.device(self.pred.device):
             _lib.call("pointops2_evaltile_vote_launcher", logits.shape[0], classes, n_points, _lib.ROW_TYPES[logits.dtype], ptr(logits), ptr(idx),
                       ptr(self._stamp), ptr(self.pred), ptr(self._status), device=self.pred.device)
 
-    def result(self):
+    def _check(self):
         if int(self._status.item()) != 0:
             raise IndexError(f"SceneVotes: an index given to add() was outside [0, {self.pred.shape[0]})")
+
+    def result(self):
+        self._check()
         return self.pred / (self.pred.sum(-1)[:, None] + 1e-8)
+
+    def labels(self):
+        self._check()
+        return self.pred.max(1)[1]
+
+
+class SceneShiftVotes(SceneVotes):
+    """SceneVotes(..., shifts=True): the votes and the summed shifts of the fork's test loop.  add() needs the shift rows."""
+
+    def __init__(self, n_points, classes, device="cuda", shifts=True):
+        if not shifts:
+            raise ValueError("SceneVotes: a SceneShiftVotes has shifts; SceneVotes(..., shifts=False) is the object without")
+        super().__init__(n_points, classes, device, True)
+
+    def add(self, logits, idx, shift=None):
+        if shift is None:
+            raise ValueError("SceneVotes.add: this object was built with shifts=True: add(logits, idx, shift) needs the shift rows [m, 3]")
+        _gpu(shift, "SceneVotes.add: shift")
+        logits, idx = self._rows(logits, idx)
+        if shift.dim() != 2 or shift.shape != (logits.shape[0], 3) or shift.dtype not in _lib.ROW_TYPES:
+            raise ValueError(f"SceneVotes.add: shift must be [{logits.shape[0]}, 3] float32 / float16 / bfloat16, got {shift.dtype} {tuple(shift.shape)}")
+        if shift.device != self.pred.device:
+            raise RuntimeError(f"SceneVotes.add: shift on {shift.device}, the votes on {self.pred.device}")
+        shift = shift.detach().contiguous()
+        n_points, classes = self.pred.shape
+        with torch.cuda.device(self.pred.device):
+            _lib.call("pointops2_evaltile_vote_shift_launcher", logits.shape[0], classes, n_points, _lib.ROW_TYPES[logits.dtype], ptr(logits),
+                      _lib.ROW_TYPES[shift.dtype], ptr(shift), ptr(idx), ptr(self._stamp), ptr(self.pred), ptr(self.shift), ptr(self._status),
+                      device=self.pred.device)
 
 
 def intersection_and_union(output, target, K, ignore_index=255):
@@ -173,19 +225,27 @@ def scene_eval(model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size,
     under torch.no_grad() (a tuple result: its first element - the fork returns (out, shift)), and SceneVotes.add collects
     softmax(logits).  priority: one float64 [n_part] tensor per part (or None), replaying the draws of :239.
     The caller sums the result over its transforms, takes the arg-max and calls intersection_and_union."""
+    return _scene_votes("scene_eval", False, model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size, max_num_neighbors, batch_size_test,
+                        feat_div, concat_xyz, priority).result()
+
+
+def _scene_votes(who, shifts, model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size, max_num_neighbors, batch_size_test, feat_div,
+                 concat_xyz, priority):
+    """the tiling, normalisation, batching and ball_query that scene_eval and scene_predict share -> the filled SceneVotes.
+    shifts False: model_fn's logits (a tuple result: its first element) are voted; True: model_fn must return (logits, shift)."""
     coord = _coord(coord)
-    _gpu(feat, "scene_eval: feat")
+    _gpu(feat, f"{who}: feat")
     if feat.dim() != 2 or feat.shape[0] != coord.shape[0] or feat.device != coord.device:
-        raise ValueError(f"scene_eval: feat must be [{coord.shape[0]}, C] on {coord.device}, got {tuple(feat.shape)} on {feat.device}")
+        raise ValueError(f"{who}: feat must be [{coord.shape[0]}, C] on {coord.device}, got {tuple(feat.shape)} on {feat.device}")
     if int(batch_size_test) < 1:
-        raise ValueError("scene_eval: batch_size_test must be >= 1")
+        raise ValueError(f"{who}: batch_size_test must be >= 1")
     dev = coord.device
-    votes = SceneVotes(coord.shape[0], classes, dev)
+    votes = SceneVotes(coord.shape[0], classes, dev, shifts)
     if voxel_size:
         coord = coord - coord.min(0)[0]
     parts = scene_parts(coord, voxel_size)
     if priority is not None and len(priority) != parts.shape[0]:
-        raise ValueError(f"scene_eval: {len(priority)} priorities for {parts.shape[0]} parts")
+        raise ValueError(f"{who}: {len(priority)} priorities for {parts.shape[0]} parts")
     items = []   # (idx, coord, feat) of every crop, in the order of idx_list
     for i in range(parts.shape[0]):
         idx_part = parts[i]
@@ -208,5 +268,78 @@ def scene_eval(model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size,
             if concat_xyz:
                 feat_b = torch.cat([feat_b, coord_b], 1)
             out = model_fn(feat_b, coord_b, offset, batch, neighbor_idx)
-            votes.add(out[0] if isinstance(out, (tuple, list)) else out, idx_b)
-    return votes.result()
+            if shifts:
+                if not isinstance(out, (tuple, list)) or len(out) != 2:
+                    raise TypeError(f"{who}: model_fn must return the pair (logits, shift), got {type(out).__name__}"
+                                    + (f" of {len(out)}" if isinstance(out, (tuple, list)) else ""))
+                votes.add(out[0], idx_b, out[1])
+            else:
+                votes.add(out[0] if isinstance(out, (tuple, list)) else out, idx_b)
+    return votes
+
+
+def scene_predict(model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size, max_num_neighbors=34, batch_size_test=5, feat_div=255.0,
+                  concat_xyz=False, priority=None):
+    """The fork's test loop up to its two accumulators (test_iou.py:266-338; the same lines in test.py), on the device:
+    -> (votes float32 [N, classes], shift float32 [N, 3]).  Tiling, normalisation, batching and ball_query are scene_eval's, argument for
+    argument; model_fn(feat, coord, offset, batch, neighbor_idx) must return the pair (logits [m, classes], shift [m, 3]), each f32 / f16 /
+    bf16 - anything else raises TypeError.  Per batch `pred[idx, :] += softmax(logits)` and `pred_shift[idx, :] += shift` (:337-338), both
+    with SceneVotes' last-writer rule inside a batch.
+
+    The votes are RAW: the fork has the normalisation of :340 commented out and takes `pred.max(1)[1]` of the sums (:343).
+    Kept quirk: the shift of a point that k batches visited is the SUM of its k predictions, not their mean - the fork adds `pred_shift`
+    to the coordinates as it is (:344, :356), so a point in two overlapping crops moves by both predictions."""
+    votes = _scene_votes("scene_predict", True, model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size, max_num_neighbors,
+                         batch_size_test, feat_div, concat_xyz, priority)
+    votes._check()
+    return votes.pred, votes.shift
+
+
+def dense_points(coord, eps=0.1, min_samples=5, min_points=50):
+    """The loader's outlier filter (test_iou.py:147-151, test.py:122): one DBSCAN of the whole scene; the clusters with MORE than
+    min_points points are kept, concatenated cluster by cluster; noise is dropped.  coord [N, 3] f32 / f64 on the GPU (clustered in fp32
+    by cluster.dbscan) -> (coord_kept [K, 3] in coord's dtype, index int64 [K] into coord: ascending cluster number, then ascending
+    original index - the reference's order).  N = 0: nothing is launched; nothing kept: empty tensors."""
+    coord = _coord(coord)
+    if isinstance(min_points, bool) or not isinstance(min_points, int) or min_points < 0:
+        raise ValueError(f"dense_points: min_points must be an int >= 0, got {min_points!r}")
+    none = torch.empty(0, dtype=torch.int64, device=coord.device)
+    if coord.shape[0] == 0:
+        cluster._settings(eps, min_samples, 1)
+        return coord[:0], none
+    labels, _, n_clusters = cluster.dbscan(coord.float(), eps, min_samples)
+    if int(n_clusters.sum().item()) == 0:
+        return coord[:0], none
+    labels = labels.long()
+    size = torch.bincount(labels[labels >= 0])
+    kept = torch.nonzero((labels >= 0) & (size[labels.clamp(min=0)] > min_points)).flatten()      # ascending original index
+    if kept.numel() == 0:
+        return coord[:0], none
+    index = kept[torch.sort(labels[kept], stable=True)[1]]
+    return coord[index], index
+
+
+DetectedScene = collections.namedtuple("DetectedScene", ["boxes", "label", "shift", "points", "merged", "n_sets", "score"])
+
+
+def detect_scene(model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size, max_num_neighbors=34, batch_size_test=5, feat_div=255.0,
+                 concat_xyz=False, priority=None, gt_box=None, overlap_threshold=0.25, **cluster_settings):
+    """The fork's detection pass for one scene (test_iou.py:266-464) in one call on device tensors:
+        scene_predict -> label = arg-max of the raw votes (:343), shift = the summed shifts
+        cluster.detect_boxes(coord.float(), shift, label, **cluster_settings)     instantiation_eval (:356) and the merging loop (:373-422)
+        cluster.box_detection(boxes, gt_box, overlap_threshold)                   when gt_box is given; 0.25 is the fork's (:268)
+    The arguments up to `priority` are scene_predict's; cluster_settings are detect_boxes' keywords.
+    -> DetectedScene(boxes float32 [S, 6] = lo | hi, label int64 [N], shift float32 [N, 3], points float32 [K, 3]: the cleaned support
+       points, merged int32 [K]: the merged set (= row of boxes) of every support point, n_sets = S, score: box_detection's tuple or None).
+
+    Two departures from the fork.  It subtracts the minimum before the loop and adds it back (:344), so it detects on
+    `(coord - min) + min` in the array's dtype; here detection runs on the original coordinates cast to fp32.  And it `return`s from
+    its whole test function when instantiation_eval finds fewer than two supports (:357-358); here the boxes of the zero or one
+    supports are returned (and scored)."""
+    cluster.detect_settings(**cluster_settings)              # a wrong setting raises before the scene goes through the model
+    votes, shift = scene_predict(model_fn, coord, feat, voxel_size, voxel_max, classes, grid_size, max_num_neighbors, batch_size_test, feat_div,
+                                 concat_xyz, priority)
+    label = votes.max(1)[1]
+    boxes, points, merged, n_sets, _, _ = cluster.detect_boxes(coord.float(), shift, label, **cluster_settings)
+    score = None if gt_box is None else cluster.box_detection(boxes, gt_box, overlap_threshold)
+    return DetectedScene(boxes, label, shift, points, merged, n_sets, score)
