@@ -24,12 +24,15 @@ Between the two the reference cleans every support with Open3D (util/train_utils
 `clean_supports` on csrc/supports.hip; `box_supports` is instances -> objects -> clean_supports in one call, what `instantiation_eval`
 returns.  Open3D is not needed (and not imported).
 
-dbscan, contacts / objects, clean_supports and merge_objects stand on ONE fixed-radius grid: `_scan` (the read-back up front), `_dims` and `_grid` (cell
-keys, torch's sort, the nine prepared runs per point) build it here, csrc/radius_grid.h walks it on the device for all of them.
+dbscan, contacts / objects, clean_supports and merge_objects stand on ONE fixed-radius grid: `_dims` and `_grid` (cell keys, torch's sort,
+the nine prepared runs per point) build it here, csrc/radius_grid.h walks it on the device for all of them.  Every public call opens a
+`_Call`: its `launch` and `read` are the library launch and the device-to-host transfer, counted in the stage's LAST_* where they happen.
+The stages on a labelled cloud share the prologue `_labelled` (with `_scan`, the read-back up front) and the one-group grid `_label_grid`.
 """
+import collections
 import contextlib
 import ctypes
-import functools
+import itertools
 
 import numpy as np
 import torch
@@ -43,7 +46,7 @@ MAX_CELLS_PER_AXIS = 1 << 20
 REG_LABELS = 64             # csrc/radius_grid.h keeps rows of up to this many labels in registers: no bitmap
 MAX_BITMAP_BYTES = 1 << 30  # of the [n_valid, ceil(I / 32)] rows of labels in reach (more than REG_LABELS labels)
 MAX_LABELS = 1 << 15        # the [I, I] tables are indexed with ints
-LAST = {"rounds": 0, "launches": 0}   # of the most recent dbscan() call (tools/bench_dbscan.py, the chain test)
+LAST = {"rounds": 0, "launches": 0}   # of the most recent dbscan() call (tools/bench_dbscan.py, the chain test); no "readbacks": see _Call.read
 
 # instantiation_eval's settings (util/train_utils.py:558-563): faces (classes below 6) and edges
 FACE_CLASSES = 6
@@ -75,8 +78,9 @@ def _per_group(value, n_groups, dtype, name):
     return a.shape[0], a.astype(dtype)
 
 
-def _settings(eps, min_samples, n_groups):
-    """-> (G or None when both are scalars, eps f32 [G] or scalar, min_samples i32 [G] or scalar), validated"""
+def dbscan_settings(eps, min_samples, n_groups):
+    """dbscan's checks of eps and min_samples (scalars, or sequences / tensors of length n_groups; None = take the length from them)
+    -> (G or None when both are scalars, eps f32 [G] or scalar, min_samples i32 [G] or scalar), validated"""
     g1, e = _per_group(eps, n_groups, np.float32, "eps")
     g2, m = _per_group(min_samples, n_groups, np.int32, "min_samples")
     if g1 is not None and g2 is not None and g1 != g2:
@@ -106,9 +110,19 @@ def _check_tensors(who, xyz, label, noun):
             raise ValueError(f"{who}: {noun} must be [N] = [{xyz.shape[0]}], got {tuple(label.shape)}")
 
 
+def _is_real(x):
+    """a Python or numpy real number; a bool is none"""
+    return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))
+
+
+def _is_int(x):
+    """a Python or numpy integer; a bool is none"""
+    return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+
+
 def _radius(who, radius):
     """-> (fp32(radius), its fp32 square, rounded once), both finite and > 0"""
-    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+    if not _is_real(radius):
         raise TypeError(f"{who}: radius must be a number, got {type(radius).__name__}")
     with np.errstate(all="ignore"):
         r = np.float32(radius)
@@ -120,22 +134,13 @@ def _radius(who, radius):
 def _label_count(who, n_labels, name="n_labels"):
     if n_labels is None:
         return None
-    if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+    if not _is_int(n_labels):
         raise TypeError(f"{who}: {name} must be an int, got {type(n_labels).__name__}")
     if n_labels < 0:
         raise ValueError(f"{who}: {name} must be >= 0, got {n_labels}")
     if n_labels > MAX_LABELS:
         raise ValueError(f"{who}: {n_labels} labels: at most {MAX_LABELS}")
     return int(n_labels)
-
-
-def _label_range(who, n_labels, l_min, l_max, name="n_labels"):
-    """-> the number of labels (n_labels, or l_max + 1), with every label in -1 .. that number - 1"""
-    if n_labels is None:
-        n_labels = _label_count(who, max(l_max + 1, 0), name)
-    if l_min < -1 or l_max >= n_labels:
-        raise ValueError(f"{who}: label values must be in -1 .. {n_labels - 1}, got {l_min} .. {l_max}")
-    return n_labels
 
 
 def _row_words(who, n_valid, n_labels):
@@ -146,51 +151,117 @@ def _row_words(who, n_valid, n_labels):
     return words
 
 
-def _launch(counter, dev, name, *args):
-    """one library launch on `dev`, counted in `counter` (LAST, LAST_CONTACTS or LAST_MERGE)"""
-    counter["launches"] += 1
-    with contextlib.nullcontext() if dev.index == torch.cuda.current_device() else torch.cuda.device(dev):
-        _lib.call(name, *args, device=dev)
+class _Call:
+    """One public call: the tensor checks (they give the device), who raises, and the stage's LAST_* dictionary, reset here.  Every
+    library launch of this module goes through `launch`, every device-to-host transfer through `read`; each counts itself."""
+
+    def __init__(self, who, counter, xyz, label, noun="label"):
+        _check_tensors(who, xyz, label, noun)
+        self.who, self.dev, self.counter = who, xyz.device, counter
+        for key in counter:
+            counter[key] = 0
+
+    def count(self, key):
+        if key in self.counter:
+            self.counter[key] += 1
+
+    def launch(self, name, *args):
+        self.count("launches")
+        with contextlib.nullcontext() if self.dev.index == torch.cuda.current_device() else torch.cuda.device(self.dev):
+            _lib.call(name, *args, device=self.dev)
+
+    def read(self, *tensors):
+        """ONE transfer: the tensors (of one dtype) concatenated, brought to the host and split again -> a numpy array per tensor, in its
+        shape.  Counted where the stage keeps "readbacks": LAST does not - dbscan's measure is its rounds, its scan up front is uncounted."""
+        self.count("readbacks")
+        if len(tensors) == 1:
+            return [tensors[0].cpu().numpy()]
+        flat = torch.cat([t.reshape(-1) for t in tensors]).cpu().numpy()
+        ends = list(itertools.accumulate(t.numel() for t in tensors))
+        return [flat[end - t.numel():end].reshape(tuple(t.shape)) for end, t in zip(ends, tensors)]
 
 
-def _scan(who, xyz, label):
+def _scan(call, xyz, label):
     """The one read-back up front: the label (group) range, the points that take part (label >= 0) and their bounding box
-    -> (member bool [N], l_min, l_max, n_valid, origin float64 [3], top float64 [3]); ValueError for non-finite coordinates."""
+    -> (member bool [N], l_min, l_max, n_valid, finite: whether every coordinate is, origin float64 [3], top float64 [3])."""
     member = label >= 0
     inf = torch.tensor(float("inf"), dtype=torch.float32, device=xyz.device)
     lo = torch.where(member[:, None], xyz, inf).amin(0)
     hi = torch.where(member[:, None], xyz, -inf).amax(0)
-    finite = torch.isfinite(xyz).all()
-    head = torch.cat([label.min()[None].double(), label.max()[None].double(), member.sum()[None].double(), finite[None].double(),
-                      lo.double(), hi.double()]).cpu().numpy()
-    if not head[3]:
-        raise ValueError(f"{who}: xyz must be finite")
-    return member, int(head[0]), int(head[1]), int(head[2]), head[4:7], head[7:10]
+    l_min, l_max, n_valid, finite, origin, top = call.read(label.min().double(), label.max().double(), member.sum().double(),
+                                                           torch.isfinite(xyz).all().double(), lo.double(), hi.double())
+    return member, int(l_min), int(l_max), int(n_valid), bool(finite), origin, top
 
 
-def _dims(who, n_groups, origin, top, cell):
-    """-> the grid's cells per axis [nx, ny, nz]; ValueError when n_groups such grids do not fit the 64-bit cell keys"""
+# a labelled cloud as the stages take it: xyz and label (int32) contiguous, member = label >= 0, n_valid labelled points in the box origin .. top
+_Labelled = collections.namedtuple("_Labelled", "xyz label member n_labels n_valid origin top dev n")
+
+
+def _labelled(call, xyz, label, n_labels, name="n_labels"):
+    """The prologue of every stage on a labelled cloud, behind the call's tensor checks and the stage's settings: the label count, N = 0
+    (nothing is read, n_valid = 0), the copies, the one read-back up front, the label range, then finite coordinates -> _Labelled.
+    The caller returns its empty result when n_valid == 0 or n_labels == 0; `readbacks` 0 / 1 tells no point from no labelled point."""
+    n_labels = _label_count(call.who, n_labels, name)
+    n = xyz.shape[0]
+    if n == 0:
+        return _Labelled(xyz, label, None, n_labels or 0, 0, None, None, call.dev, 0)
+    xyz = xyz.contiguous()
+    label = label.to(torch.int32).contiguous()
+    member, l_min, l_max, n_valid, finite, origin, top = _scan(call, xyz, label)
+    if n_labels is None:
+        n_labels = _label_count(call.who, max(l_max + 1, 0), name)
+    if l_min < -1 or l_max >= n_labels:
+        raise ValueError(f"{call.who}: label values must be in -1 .. {n_labels - 1}, got {l_min} .. {l_max}")
+    if not finite:
+        raise ValueError(f"{call.who}: xyz must be finite")
+    return _Labelled(xyz, label, member, n_labels, n_valid, origin, top, call.dev, n)
+
+
+def _dims(who, n_groups, origin, top, r):
+    """The cells of the grid for a largest radius r, CELL_MARGIN wider than it -> (cell edge, cells per axis [nx, ny, nz]); ValueError
+    when n_groups such grids do not fit the 64-bit cell keys"""
+    cell = float(r) * CELL_MARGIN
     dims = [int(np.floor((top[a] - origin[a]) / cell)) + 1 for a in range(3)]
     if max(dims) > MAX_CELLS_PER_AXIS or n_groups * dims[0] * dims[1] * dims[2] >= 2 ** 61:
         raise ValueError(f"{who}: the cloud spans {dims} cells of edge {cell:g}: too many for the 64-bit cell keys")
-    return dims
+    return cell, dims
 
 
-def _grid(launch, xyz, group, n_groups, n_valid, origin, cell, dims):
+def _grid(call, xyz, group, n_groups, n_valid, origin, cell, dims):
     """The fixed-radius grid of csrc/radius_grid.h over the points with a group in 0 .. n_groups-1: cell keys, torch's stable sort, the
     nine runs per point -> (pts float32 [n_valid, 4] = x, y, z, original index as bits, in the grid's order; order int64 [N]: the sort's
     permutation, the n_valid points that take part first; sorted_group int32 [n_valid]; ranges int32 [18, n_valid])."""
     dev, n = xyz.device, xyz.shape[0]
     keys = torch.empty(n, dtype=torch.int64, device=dev)
-    launch("pointops2_dbscan_keys_launcher", n, n_groups, ptr(xyz), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
-           ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
+    call.launch("pointops2_dbscan_keys_launcher", n, n_groups, ptr(xyz), ptr(group), ctypes.c_double(origin[0]), ctypes.c_double(origin[1]),
+                ctypes.c_double(origin[2]), ctypes.c_double(cell), dims[0], dims[1], dims[2], ptr(keys))
     skeys, order = torch.sort(keys, stable=True)
     pts = torch.empty(n_valid, 4, dtype=torch.float32, device=dev)
     sgroup = torch.empty(n_valid, dtype=torch.int32, device=dev)
     ranges = torch.empty(18, n_valid, dtype=torch.int32, device=dev)
-    launch("pointops2_dbscan_prepare_launcher", n, n_valid, dims[0], dims[1], dims[2], ptr(xyz), ptr(skeys), ptr(order), ptr(pts), ptr(sgroup),
-           ptr(ranges))
+    call.launch("pointops2_dbscan_prepare_launcher", n, n_valid, dims[0], dims[1], dims[2], ptr(xyz), ptr(skeys), ptr(order), ptr(pts),
+                ptr(sgroup), ptr(ranges))
     return pts, order, sgroup, ranges
+
+
+def _label_grid(call, p, r):
+    """the grid over the labelled points of p (_Labelled) for radius r, as ONE group; raises as _dims does, before its first launch
+    -> (pts float32 [n_valid, 4], sorted_label int32 [n_valid], ranges int32 [18, n_valid]), all in the grid's order"""
+    cell, dims = _dims(call.who, 1, p.origin, p.top, r)
+    return _member_grid(call, p.xyz, p.label, p.member, p.n_valid, p.origin, cell, dims)
+
+
+def _member_grid(call, xyz, label, member, n_valid, origin, cell, dims):
+    """_label_grid on cells that the caller has laid out"""
+    group = member.to(torch.int32) - 1                       # one group: 0 for a labelled point, -1 for the others
+    pts, order, _, ranges = _grid(call, xyz, group, 1, n_valid, origin, cell, dims)
+    return pts, label[order[:n_valid]].contiguous(), ranges
+
+
+def _lookup(values, label, dev):
+    """host values int32 [I] looked up per point, -1 for label -1 -> (per point int32 [N], the table on the device int32 [I + 1])"""
+    table = torch.from_numpy(np.concatenate([values, np.full(1, -1, np.int32)])).to(dev)                     # (the last entry serves -1)
+    return table[label.long()], table
 
 
 def dbscan(xyz, eps, min_samples, group=None):
@@ -202,10 +273,10 @@ def dbscan(xyz, eps, min_samples, group=None):
     Raises before any launch: RuntimeError for a CPU tensor, ValueError / TypeError for a wrong shape or dtype, ValueError for
     eps <= 0, min_samples < 1, a group outside -1 .. G-1 or non-finite coordinates.  RuntimeError when the component loop has not
     settled after MAX_ROUNDS rounds."""
-    _check_tensors("dbscan", xyz, group, "group")
-    n_groups, eps_h, ms_h = _settings(eps, min_samples, 1 if group is None else None)
-    dev, n = xyz.device, xyz.shape[0]
-    LAST["rounds"], LAST["launches"] = 0, 0
+    # not on _labelled: G comes from eps / min_samples and `group` may be None, which would be a second path inside the shared prologue
+    call = _Call("dbscan", LAST, xyz, group, "group")
+    n_groups, eps_h, ms_h = dbscan_settings(eps, min_samples, 1 if group is None else None)
+    dev, n = call.dev, xyz.shape[0]
     if n == 0:
         g = n_groups if n_groups is not None else 1
         return (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.bool, device=dev),
@@ -215,7 +286,9 @@ def dbscan(xyz, eps, min_samples, group=None):
         group = torch.zeros(n, dtype=torch.int32, device=dev)
     group = group.to(torch.int32).contiguous()
 
-    _, g_min, g_max, n_valid, origin, top = _scan("dbscan", xyz, group)
+    _, g_min, g_max, n_valid, finite, origin, top = _scan(call, xyz, group)
+    if not finite:
+        raise ValueError("dbscan: xyz must be finite")
     if n_groups is None:
         n_groups = max(g_max + 1, 1)
     if g_min < -1 or g_max >= n_groups:
@@ -229,25 +302,23 @@ def dbscan(xyz, eps, min_samples, group=None):
     if n_valid == 0:
         return labels, core.bool(), n_clusters
 
-    cell = float(np.float32(eps_h.max())) * CELL_MARGIN
-    dims = _dims("dbscan", n_groups, origin, top, cell)
+    cell, dims = _dims("dbscan", n_groups, origin, top, np.float32(eps_h.max()))
     eps2 = torch.from_numpy(eps_h * eps_h).to(dev)          # fp32 product, rounded once
     ms = torch.from_numpy(ms_h).to(dev)
 
-    call = functools.partial(_launch, LAST, dev)
     pts, _, sgroup, ranges = _grid(call, xyz, group, n_groups, n_valid, origin, cell, dims)
     score = torch.empty(n_valid, dtype=torch.uint8, device=dev)
     parent = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    call("pointops2_dbscan_core_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(ms), ptr(score), ptr(core),
-         ptr(parent))
+    call.launch("pointops2_dbscan_core_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(ms), ptr(score), ptr(core),
+                ptr(parent))
 
     changed = torch.zeros(1, dtype=torch.int32, device=dev)
     for rounds in range(1, MAX_ROUNDS + 1):
-        call("pointops2_dbscan_round_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
-             ptr(changed))
-        LAST["launches"] += 1                                # (a round is two kernels)
+        call.launch("pointops2_dbscan_round_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
+                    ptr(changed))
+        call.count("launches")                               # (a round is two kernels)
         LAST["rounds"] = rounds
-        if int(changed.item()) == 0:                         # the one small read-back per round
+        if int(changed.item()) == 0:                         # the one small read-back per round: LAST["rounds"] is its count, so not through call.read
             break
     else:
         raise RuntimeError(f"dbscan: the component loop has not settled after {MAX_ROUNDS} rounds")
@@ -264,8 +335,8 @@ def dbscan(xyz, eps, min_samples, group=None):
         starts = torch.cumsum(counts, 0) - counts
         number = torch.arange(roots.numel(), device=dev) - starts[sorted_group]
         cluster_of_root[roots[by_group]] = number.to(torch.int32)
-    call("pointops2_dbscan_label_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
-         ptr(cluster_of_root), ptr(labels))
+    call.launch("pointops2_dbscan_label_launcher", n, n_valid, ptr(pts), ptr(sgroup), ptr(ranges), ptr(eps2), ptr(score), ptr(parent),
+                ptr(cluster_of_root), ptr(labels))
     return labels, core.bool(), n_clusters
 
 
@@ -303,11 +374,12 @@ def instances(coord, shift, pred, eps=None, min_samples=None, min_points=None):
     lengths = {l for l in map(_length, (eps, min_samples, min_points)) if l is not None}
     if len(lengths) > 1:
         raise ValueError(f"dbscan: eps, min_samples and min_points must agree on the number of classes, got {sorted(lengths)}")
+    # (the two .item() of this function are outside any counted stage: dbscan, which it calls, owns LAST and resets it)
     n_classes = lengths.pop() if lengths else (max(int(pred.max().item()) + 1, 1) if n > 0 else 1)
     eps_h = _class_settings(eps, n_classes, FACE_SETTINGS[0], EDGE_SETTINGS[0], np.float32, "eps")
     ms_h = _class_settings(min_samples, n_classes, FACE_SETTINGS[1], EDGE_SETTINGS[1], np.int32, "min_samples")
     mp_h = _class_settings(min_points, n_classes, FACE_SETTINGS[2], EDGE_SETTINGS[2], np.int32, "min_points")
-    _settings(eps_h, ms_h, n_classes)
+    dbscan_settings(eps_h, ms_h, n_classes)
     if n == 0:
         return empty, empty.clone(), empty.clone()
     labels, _, n_clusters = dbscan(coord + shift, eps_h, ms_h, pred)
@@ -335,43 +407,23 @@ CONTACT_SHARE = 0.5
 LAST_CONTACTS = {"launches": 0, "readbacks": 0}   # of the most recent contacts() / objects() call (tools/bench_contacts.py)
 
 
-def _contacts(xyz, label, radius, n_labels, want_min, who):
-    """-> (count int32 [I, I], min_d2 float32 [I, I] or None, I)"""
-    _check_tensors(who, xyz, label, "label")
-    r, r2 = _radius(who, radius)
-    n_labels = _label_count(who, n_labels)
-    dev, n = xyz.device, xyz.shape[0]
-    LAST_CONTACTS["launches"], LAST_CONTACTS["readbacks"] = 0, 0
-
-    def tables(i):
-        return (torch.zeros(i, i, dtype=torch.int32, device=dev),
-                torch.full((i, i), float("inf"), dtype=torch.float32, device=dev) if want_min else None, i)
-
-    if n == 0:
-        return tables(n_labels or 0)
-    xyz = xyz.contiguous()
-    label = label.to(torch.int32).contiguous()
-
-    LAST_CONTACTS["readbacks"] += 1
-    member, l_min, l_max, n_valid, origin, top = _scan(who, xyz, label)
-    n_labels = _label_range(who, n_labels, l_min, l_max)
-    words = _row_words(who, n_valid, n_labels)
-    if n_valid == 0 or n_labels == 0:
-        return tables(n_labels)
-    cell = float(r) * CELL_MARGIN
-    dims = _dims(who, 1, origin, top, cell)
-    count, min_d2, _ = tables(n_labels)
-    call = functools.partial(_launch, LAST_CONTACTS, dev)
-    group = member.to(torch.int32) - 1                       # one group: 0 for a labelled point, -1 for the others
-    pts, order, _, ranges = _grid(call, xyz, group, 1, n_valid, origin, cell, dims)
-    slabel = label[order[:n_valid]].contiguous()
-    bitmap = torch.zeros(n_valid, words, dtype=torch.int32, device=dev) if n_labels > REG_LABELS else None
-    call("pointops2_contacts_count_launcher", n_valid, n_labels, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(bitmap), ptr(count))
+def _contact_tables(call, p, r, r2, want_min):
+    """the tables of contacts() over the labelled cloud p (_Labelled): zeros / +inf when it holds no labelled point, else the grid, its walk
+    and - want_min - the sweep over all pairs -> (count int32 [I, I], min_d2 float32 [I, I] or None)"""
+    count = torch.zeros(p.n_labels, p.n_labels, dtype=torch.int32, device=p.dev)
+    min_d2 = torch.full((p.n_labels, p.n_labels), float("inf"), dtype=torch.float32, device=p.dev) if want_min else None
+    if p.n_valid == 0 or p.n_labels == 0:
+        return count, min_d2
+    words = _row_words(call.who, p.n_valid, p.n_labels)
+    pts, slabel, ranges = _label_grid(call, p, r)
+    bitmap = torch.zeros(p.n_valid, words, dtype=torch.int32, device=p.dev) if p.n_labels > REG_LABELS else None
+    call.launch("pointops2_contacts_count_launcher", p.n_valid, p.n_labels, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(bitmap),
+                ptr(count))
     if want_min:
         llabel, by_label = torch.sort(slabel, stable=True)   # ascending label; inside a label the grid's order, which keeps tiles compact
         label_pts = torch.cat([pts[by_label, :3], llabel.view(torch.float32)[:, None]], 1).contiguous()
-        call("pointops2_contacts_min_launcher", n_valid, n_labels, ptr(label_pts), ptr(min_d2))
-    return count, min_d2, n_labels
+        call.launch("pointops2_contacts_min_launcher", p.n_valid, p.n_labels, ptr(label_pts), ptr(min_d2))
+    return count, min_d2
 
 
 def contacts(xyz, label, radius, n_labels=None):
@@ -388,8 +440,20 @@ def contacts(xyz, label, radius, n_labels=None):
     radius <= 0 or non-finite, a label outside -1 .. I-1 or non-finite coordinates; ValueError when the rows of labels in reach
     (n_valid * ceil(I / 32) * 4 bytes, needed above 64 labels) would exceed MAX_BITMAP_BYTES = 1 GiB, when I > MAX_LABELS, or when the grid
     exceeds MAX_CELLS_PER_AXIS.  N = 0 or no labelled point: the tables of zeros / +inf, nothing launched."""
-    count, min_d2, _ = _contacts(xyz, label, radius, n_labels, True, "contacts")
-    return count, min_d2
+    call = _Call("contacts", LAST_CONTACTS, xyz, label)
+    r, r2 = _radius(call.who, radius)
+    return _contact_tables(call, _labelled(call, xyz, label, n_labels), r, r2, True)
+
+
+def _link_settings(share, face_classes, edge_faces):
+    """link_objects' settings -> (face_classes as an int, edge_faces as a tuple of pairs of ints), validated"""
+    if not _is_real(share) or not np.isfinite(share) or share < 0:
+        raise ValueError(f"objects: share must be a finite number >= 0, got {share!r}")
+    edge_faces = EDGE_FACES if edge_faces is None else tuple(tuple(int(f) for f in pair) for pair in edge_faces)
+    face_classes = int(face_classes)
+    if any(len(pair) != 2 or not all(0 <= f < face_classes for f in pair) for pair in edge_faces):
+        raise ValueError(f"objects: edge_faces must hold pairs of face classes below {face_classes}")
+    return face_classes, edge_faces
 
 
 def link_objects(count, size, instance_class, share=CONTACT_SHARE, face_classes=FACE_CLASSES, edge_faces=None):
@@ -404,18 +468,13 @@ def link_objects(count, size, instance_class, share=CONTACT_SHARE, face_classes=
       4. objects = the connected components over the linked face instances, two faces joined when one edge linked both; a face no edge
          linked is in no object, an edge that linked a single face makes it an object of its own;
       5. objects are numbered by ascending smallest face instance number; an edge instance gets the object of its first linked face."""
+    face_classes, edge_faces = _link_settings(share, face_classes, edge_faces)
     count = np.asarray(count)
     size = np.asarray(size).astype(np.int64).reshape(-1)
     cls = np.asarray(instance_class).astype(np.int64).reshape(-1)
     n_inst = cls.shape[0]
     if count.shape != (n_inst, n_inst) or size.shape != (n_inst,):
         raise ValueError(f"objects: count must be [I, I] and size [I] for the {n_inst} instances, got {count.shape} and {size.shape}")
-    if isinstance(share, bool) or not isinstance(share, (int, float, np.integer, np.floating)) or not np.isfinite(share) or share < 0:
-        raise ValueError(f"objects: share must be a finite number >= 0, got {share!r}")
-    edge_faces = EDGE_FACES if edge_faces is None else tuple(tuple(int(f) for f in pair) for pair in edge_faces)
-    face_classes = int(face_classes)
-    if any(len(pair) != 2 or not all(0 <= f < face_classes for f in pair) for pair in edge_faces):
-        raise ValueError(f"objects: edge_faces must hold pairs of face classes below {face_classes}")
     count = count.astype(np.int64)
     of_class = [np.nonzero(cls == c)[0] for c in range(face_classes)]             # ascending instance numbers
     parent = np.arange(n_inst)
@@ -473,27 +532,23 @@ def objects(coord, instance, instance_class, instance_size=None, radius=CONTACT_
     rotating merge loop) is not reproduced; the Open3D clean-up of every support (:716-720) is clean_supports, on this function's
     output; the OBB merging of test.py:294-326 is the step behind that, merge_objects.
     Raises as contacts() does; ValueError for an instance_class / instance_size that is not [I]."""
-    _check_tensors("objects", coord, instance, "label")
-    dev = coord.device
+    call = _Call("objects", LAST_CONTACTS, coord, instance)
+    dev = call.dev
     if not isinstance(instance_class, torch.Tensor) or instance_class.dim() != 1 or instance_class.dtype not in (torch.int32, torch.int64):
         raise ValueError("objects: instance_class must be an int32 / int64 tensor [I]")
     n_inst = instance_class.shape[0]
     if instance_size is not None and (not isinstance(instance_size, torch.Tensor) or tuple(instance_size.shape) != (n_inst,)
                                       or instance_size.dtype not in (torch.int32, torch.int64)):
         raise ValueError(f"objects: instance_size must be an int32 / int64 tensor [{n_inst}]")
-    link_objects(np.zeros((0, 0), np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64), share, face_classes, edge_faces)  # the settings
-    count, _, _ = _contacts(coord, instance, radius, n_inst, False, "objects")
-    n = coord.shape[0]
+    _link_settings(share, face_classes, edge_faces)
+    r, r2 = _radius(call.who, radius)
+    count, _ = _contact_tables(call, _labelled(call, coord, instance, n_inst), r, r2, False)
     if instance_size is None:
-        instance_size = torch.bincount(instance[instance >= 0].long(), minlength=n_inst) if n > 0 else torch.zeros(n_inst, dtype=torch.int64)
-    head = torch.cat([count.flatten().long(), instance_size.to(dev).long(), instance_class.to(dev).long()]).cpu().numpy()   # the one read-back
-    LAST_CONTACTS["readbacks"] += 1
-    object_of, n_objects = link_objects(head[:n_inst * n_inst].reshape(n_inst, n_inst), head[n_inst * n_inst:n_inst * n_inst + n_inst],
-                                        head[n_inst * n_inst + n_inst:], share, face_classes, edge_faces)
-    face_object = np.where(head[n_inst * n_inst + n_inst:] < int(face_classes), object_of, -1).astype(np.int32)
-    table = torch.from_numpy(np.concatenate([face_object, np.full(1, -1, np.int32)])).to(dev)                # (the last entry serves -1)
-    obj = table[instance.long()] if n > 0 else torch.empty(0, dtype=torch.int32, device=dev)
-    return obj, torch.from_numpy(object_of).to(dev), n_objects
+        instance_size = torch.bincount(instance[instance >= 0].long(), minlength=n_inst) if coord.shape[0] > 0 else torch.zeros(n_inst, dtype=torch.int64)
+    count_h, size_h, class_h = call.read(count.long(), instance_size.to(dev).long(), instance_class.to(dev).long())   # the one read-back
+    object_of, n_objects = link_objects(count_h, size_h, class_h, share, face_classes, edge_faces)
+    face_object = np.where(class_h < int(face_classes), object_of, -1).astype(np.int32)
+    return _lookup(face_object, instance, dev)[0], torch.from_numpy(object_of).to(dev), n_objects
 
 
 # ---- the OBB merging behind the grouping (test.py:294-326, the same loop at test_iou.py:373-406) and the box detection score that
@@ -504,13 +559,13 @@ MERGE_MIN_NEIGHBORS = 10    # test.py:312
 LAST_MERGE = {"launches": 0, "readbacks": 0}   # of the most recent label_boxes() / merge_objects() call (tools/bench_merge.py)
 
 
-def _boxes(xyz, label, n_labels, dev, counter=LAST_MERGE):
-    """the launch of label_boxes on checked, contiguous inputs, counted in `counter` -> (lo, hi, size)"""
-    lo = torch.full((n_labels, 3), float("inf"), dtype=torch.float32, device=dev)
-    hi = torch.full((n_labels, 3), float("-inf"), dtype=torch.float32, device=dev)
-    size = torch.zeros(n_labels, dtype=torch.int32, device=dev)
-    if xyz.shape[0] > 0 and n_labels > 0:
-        _launch(counter, dev, "pointops2_label_boxes_launcher", xyz.shape[0], n_labels, ptr(xyz), ptr(label), ptr(lo), ptr(hi), ptr(size))
+def _boxes(call, p):
+    """the launch of label_boxes on the labelled cloud p (_Labelled) -> (lo, hi, size)"""
+    lo = torch.full((p.n_labels, 3), float("inf"), dtype=torch.float32, device=p.dev)
+    hi = torch.full((p.n_labels, 3), float("-inf"), dtype=torch.float32, device=p.dev)
+    size = torch.zeros(p.n_labels, dtype=torch.int32, device=p.dev)
+    if p.n > 0 and p.n_labels > 0:
+        call.launch("pointops2_label_boxes_launcher", p.n, p.n_labels, ptr(p.xyz), ptr(p.label), ptr(lo), ptr(hi), ptr(size))
     return lo, hi, size
 
 
@@ -522,21 +577,8 @@ def label_boxes(xyz, label, n_labels=None):
     values, csrc/boxes.hip); -0.0 counts as +0.0, so compare by value.  A label without a point keeps +inf / -inf / 0.
     Raises before any launch: RuntimeError for a CPU tensor or mismatched devices; TypeError / ValueError for a wrong dtype or shape, a
     label outside -1 .. I-1, non-finite coordinates or I > MAX_LABELS.  N = 0 or I = 0 launches nothing."""
-    _check_tensors("label_boxes", xyz, label, "label")
-    n_labels = _label_count("label_boxes", n_labels)
-    dev, n = xyz.device, xyz.shape[0]
-    LAST_MERGE["launches"], LAST_MERGE["readbacks"] = 0, 0
-    if n == 0:
-        return _boxes(xyz, label, n_labels or 0, dev)
-    xyz = xyz.contiguous()
-    label = label.to(torch.int32).contiguous()
-    head = torch.cat([label.min()[None].long(), label.max()[None].long(), torch.isfinite(xyz).all()[None].long()]).cpu().numpy()
-    LAST_MERGE["readbacks"] += 1
-    l_min, l_max, all_finite = int(head[0]), int(head[1]), bool(head[2])
-    n_labels = _label_range("label_boxes", n_labels, l_min, l_max)
-    if not all_finite:
-        raise ValueError("label_boxes: xyz must be finite")
-    return _boxes(xyz, label, n_labels, dev)
+    call = _Call("label_boxes", LAST_MERGE, xyz, label)
+    return _boxes(call, _labelled(call, xyz, label, n_labels))
 
 
 def _overlaps(lo_a, hi_a, lo_b, hi_b, overlap):
@@ -558,6 +600,14 @@ def _overlaps(lo_a, hi_a, lo_b, hi_b, overlap):
     return inter / (extent_a[0] * extent_a[1] * extent_a[2]) > overlap, inter / (extent_b[0] * extent_b[1] * extent_b[2]) > overlap
 
 
+def _merge_settings(overlap, min_neighbors):
+    """merge_sets' settings, validated"""
+    if not _is_real(overlap) or not np.isfinite(overlap) or overlap < 0:
+        raise ValueError(f"merge_sets: overlap must be a finite number >= 0, got {overlap!r}")
+    if not _is_int(min_neighbors) or min_neighbors < 0:
+        raise ValueError(f"merge_sets: min_neighbors must be an int >= 0, got {min_neighbors!r}")
+
+
 def merge_sets(lo, hi, size, pat_object, pat_rows, pat_count, overlap=MERGE_OVERLAP, min_neighbors=MERGE_MIN_NEIGHBORS):
     """The rotating merge loop of test.py:294-326 on plain arrays - no GPU: lo / hi [O, 3] and size [O] (label_boxes), and the pattern
     table of the border points: pat_object [P], pat_rows [P, ceil(O / 32)] (bit b: an object-b point within the radius, own bit cleared),
@@ -574,6 +624,7 @@ def merge_sets(lo, hi, size, pat_object, pat_rows, pat_count, overlap=MERGE_OVER
     and target merges when its box overlaps and num_neighbor > min_neighbors.  Sets are numbered in the order of the loop's final list,
     the row order of the reference's pred_box (test_iou.py:409-423); an object of size 0 is in set -1.  With fewer than two objects the
     reference returns before the loop (test.py:277); here nothing merges and every object is its own set."""
+    _merge_settings(overlap, min_neighbors)
     lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
     size = np.asarray(size).astype(np.int64).reshape(-1)
     n_obj = size.shape[0]
@@ -591,10 +642,6 @@ def merge_sets(lo, hi, size, pat_object, pat_rows, pat_count, overlap=MERGE_OVER
         raise ValueError(f"merge_sets: pat_rows must be [P, {words}] and pat_count [P] for the {n_pat} patterns, got {pat_rows.shape} and {pat_count.shape}")
     if n_pat and (pat_object.min() < 0 or pat_object.max() >= n_obj):
         raise ValueError(f"merge_sets: pat_object must be in 0 .. {n_obj - 1}")
-    if isinstance(overlap, bool) or not isinstance(overlap, (int, float, np.integer, np.floating)) or not np.isfinite(overlap) or overlap < 0:
-        raise ValueError(f"merge_sets: overlap must be a finite number >= 0, got {overlap!r}")
-    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or min_neighbors < 0:
-        raise ValueError(f"merge_sets: min_neighbors must be an int >= 0, got {min_neighbors!r}")
 
     lo_l, hi_l = lo.tolist(), hi.tolist()                                           # Python floats: exact copies of the float64 values
 
@@ -641,59 +688,40 @@ def merge_objects(coord, obj, n_objects=None, radius=MERGE_RADIUS, overlap=MERGE
     clean-up that the reference has commented out around the boxes, the .obj exports, and trimesh itself - PointCloud.bounding_box is
     taken as the box of the bounds (min / max per axis), its published behaviour, which no fixture here pins.
     Raises as contacts() does, before any launch.  N = 0 or no point in an object: no set, nothing launched."""
-    who = "merge_objects"
-    _check_tensors(who, coord, obj, "label")
-    r, r2 = _radius(who, radius)
-    n_objects = _label_count(who, n_objects, "n_objects")
-    merge_sets(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0), np.zeros(0), np.zeros((0, 0), np.int32), np.zeros(0), overlap, min_neighbors)  # the settings
-    dev, n = coord.device, coord.shape[0]
-    LAST_MERGE["launches"], LAST_MERGE["readbacks"] = 0, 0
+    call = _Call("merge_objects", LAST_MERGE, coord, obj)
+    r, r2 = _radius(call.who, radius)
+    _merge_settings(overlap, min_neighbors)
+    p = _labelled(call, coord, obj, n_objects, "n_objects")
+    if p.n_valid == 0 or p.n_labels == 0:
+        return (torch.full((p.n,), -1, dtype=torch.int32, device=p.dev), torch.full((p.n_labels,), -1, dtype=torch.int32, device=p.dev),
+                torch.zeros(0, 6, dtype=torch.float32, device=p.dev), 0)
+    _row_words(call.who, p.n_valid, p.n_labels)
 
-    def nothing(o):
-        return (torch.full((n,), -1, dtype=torch.int32, device=dev), torch.full((o,), -1, dtype=torch.int32, device=dev),
-                torch.zeros(0, 6, dtype=torch.float32, device=dev), 0)
-
-    if n == 0:
-        return nothing(n_objects or 0)
-    coord = coord.contiguous()
-    label = obj.to(torch.int32).contiguous()
-
-    LAST_MERGE["readbacks"] += 1
-    member, l_min, l_max, n_valid, origin, top = _scan(who, coord, label)
-    n_objects = _label_range(who, n_objects, l_min, l_max, "n_objects")
-    words = _row_words(who, n_valid, n_objects)
-    if n_valid == 0 or n_objects == 0:
-        return nothing(n_objects)
-    cell = float(r) * CELL_MARGIN
-    dims = _dims(who, 1, origin, top, cell)
-
-    lo, hi, size = _boxes(coord, label, n_objects, dev)
-    slabel, rows = _reach_rows(coord, label, member, n, n_valid, n_objects, origin, cell, dims, r2, dev)
+    pts, slabel, ranges = _label_grid(call, p, r)
+    lo, hi, size = _boxes(call, p)
+    rows = _rows(call, pts, slabel, ranges, p.n_labels, r2)
     pat, pat_count = _patterns(slabel, rows)
+    tables = _merge_tables(call, lo, hi, size, pat, pat_count)
+    set_of, sets = merge_sets(*tables, overlap, min_neighbors)
+    boxes = np.array([np.concatenate([tables[0][s].min(0), tables[1][s].max(0)]) for s in sets], dtype=np.float32).reshape(len(sets), 6)
+    merged, table = _lookup(set_of, p.label, p.dev)
+    return merged, table[:p.n_labels], torch.from_numpy(boxes).to(p.dev), len(sets)
 
-    # the one final read-back: boxes, sizes and patterns as one array of 32-bit words
-    n_pat = pat.shape[0]
-    flat = torch.cat([lo.view(torch.int32).flatten(), hi.view(torch.int32).flatten(), size, pat.flatten(), pat_count.to(torch.int32)]).cpu().numpy()
-    LAST_MERGE["readbacks"] += 1
-    at = np.cumsum([0, 3 * n_objects, 3 * n_objects, n_objects, n_pat * (1 + words), n_pat])
-    lo_h, hi_h = (flat[at[k]:at[k + 1]].view(np.float32).reshape(n_objects, 3) for k in (0, 1))
-    pat_h = flat[at[3]:at[4]].reshape(n_pat, 1 + words)
-    set_of, sets = merge_sets(lo_h, hi_h, flat[at[2]:at[3]], pat_h[:, 0], pat_h[:, 1:], flat[at[4]:at[5]], overlap, min_neighbors)
-    boxes = np.array([np.concatenate([lo_h[s].min(0), hi_h[s].max(0)]) for s in sets], dtype=np.float32).reshape(len(sets), 6)
-    table = torch.from_numpy(np.concatenate([set_of, np.full(1, -1, np.int32)])).to(dev)                     # (the last entry serves -1)
-    return table[label.long()], table[:n_objects], torch.from_numpy(boxes).to(dev), len(sets)
+
+def _rows(call, pts, slabel, ranges, n_objects, r2):
+    """the reach rows on the grid of _label_grid -> rows int32 [n_valid, words]: the objects within reach of every point, its own left out,
+    in the grid's order"""
+    rows = torch.zeros(pts.shape[0], (n_objects + 31) // 32, dtype=torch.int32, device=pts.device)
+    call.launch("pointops2_reach_rows_launcher", pts.shape[0], n_objects, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(rows))
+    return rows
 
 
 def _reach_rows(coord, label, member, n, n_valid, n_objects, origin, cell, dims, r2, dev):
-    """the grid over the labelled points and the reach rows on it -> (sorted_label int32 [n_valid], rows int32 [n_valid, words]: the objects
-    within reach of every point, its own left out), both in the grid's order"""
-    call = functools.partial(_launch, LAST_MERGE, dev)
-    group = member.to(torch.int32) - 1                       # one group: 0 for a point in an object, -1 for the others
-    pts, order, _, ranges = _grid(call, coord, group, 1, n_valid, origin, cell, dims)
-    slabel = label[order[:n_valid]].contiguous()
-    rows = torch.zeros(n_valid, (n_objects + 31) // 32, dtype=torch.int32, device=dev)
-    call("pointops2_reach_rows_launcher", n_valid, n_objects, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(r2), ptr(rows))
-    return slabel, rows
+    """merge_objects' two device steps, _member_grid and _rows, in a call of their own and on cells that the caller has laid out - the
+    entry of tests/test_merge_hip.py, which checks the rows on its own cells -> (sorted_label int32 [n_valid], rows int32 [n_valid, words])"""
+    call = _Call("merge_objects", LAST_MERGE, coord, label)
+    pts, slabel, ranges = _member_grid(call, coord, label, member, n_valid, origin, cell, dims)
+    return slabel, _rows(call, pts, slabel, ranges, n_objects, r2)
 
 
 def _patterns(slabel, rows):
@@ -704,6 +732,12 @@ def _patterns(slabel, rows):
     if keyed.shape[0] == 0:
         return keyed, torch.zeros(0, dtype=torch.int64, device=rows.device)
     return torch.unique(keyed, dim=0, return_counts=True)
+
+
+def _merge_tables(call, lo, hi, size, pat, pat_count):
+    """the one final read-back of merge_objects: boxes, sizes and patterns as one array of 32-bit words -> merge_sets' six tables"""
+    lo_h, hi_h, size_h, pat_h, count_h = call.read(lo.view(torch.int32), hi.view(torch.int32), size, pat, pat_count.to(torch.int32))
+    return lo_h.view(np.float32), hi_h.view(np.float32), size_h, pat_h[:, 0], pat_h[:, 1:], count_h
 
 
 def box_detection(pred_box, gt_box, overlap_threshold=0.5):
@@ -722,7 +756,7 @@ def box_detection(pred_box, gt_box, overlap_threshold=0.5):
     pred, gt = pred.reshape(-1, 6) if pred.size == 0 else pred, gt.reshape(-1, 6) if gt.size == 0 else gt
     if pred.ndim != 2 or pred.shape[1] != 6 or gt.ndim != 2 or gt.shape[1] != 6:
         raise ValueError(f"box_detection: pred_box and gt_box must be [P, 6] and [G, 6], got {pred.shape} and {gt.shape}")
-    if isinstance(overlap_threshold, bool) or not isinstance(overlap_threshold, (int, float, np.integer, np.floating)) or not np.isfinite(overlap_threshold):
+    if not _is_real(overlap_threshold) or not np.isfinite(overlap_threshold):
         raise ValueError(f"box_detection: overlap_threshold must be a finite number, got {overlap_threshold!r}")
     n_pred, n_gt = pred.shape[0], gt.shape[0]
     iou = np.zeros((n_pred, n_gt))
@@ -763,11 +797,11 @@ LAST_SUPPORTS = {"launches": 0, "readbacks": 0}   # of the most recent clean_sup
 def _support_settings(who, voxel, radius, nb_points):
     """-> (voxel as a float, fp32(radius), its fp32 square, nb_points as an int), validated"""
     r, r2 = _radius(who, radius)
-    if isinstance(voxel, bool) or not isinstance(voxel, (int, float, np.integer, np.floating)):
+    if not _is_real(voxel):
         raise TypeError(f"{who}: voxel must be a number, got {type(voxel).__name__}")
     if not np.isfinite(voxel) or not voxel > 0:
         raise ValueError(f"{who}: voxel must be finite and > 0, got {voxel}")
-    if isinstance(nb_points, bool) or not isinstance(nb_points, (int, np.integer)) or nb_points < 0 or nb_points >= 2 ** 31:
+    if not _is_int(nb_points) or nb_points < 0 or nb_points >= 2 ** 31:
         raise ValueError(f"{who}: nb_points must be an int >= 0, got {nb_points!r}")
     return float(voxel), r, r2, int(nb_points)
 
@@ -786,28 +820,26 @@ def _voxel_dims(who, n_objects, origin, top, voxel):
     return dims
 
 
-def _voxel_means(call, coord, label, n_objects, n_valid, lo, voxel, dims):
+def _voxel_means(call, p, lo, voxel, dims):
     """voxel keys from every object's own minimum `lo` (device), torch's stable sort, the head flags and their scan
-    -> (sorted_keys int64 [N], order int64 [N], slot int64 [n_valid], n_voxels: a 0-d device tensor - the caller reads it back)"""
-    n = coord.shape[0]
-    keys = torch.empty(n, dtype=torch.int64, device=coord.device)
-    call("pointops2_supports_keys_launcher", n, n_objects, ptr(coord), ptr(label), ptr(lo), ctypes.c_double(voxel), dims[0], dims[1], dims[2],
-         ptr(keys))
+    -> (sorted_keys int64 [N], order int64 [N], slot int64 [n_valid], n_voxels: read back here, the second read-back of clean_supports)"""
+    keys = torch.empty(p.n, dtype=torch.int64, device=p.dev)
+    call.launch("pointops2_supports_keys_launcher", p.n, p.n_labels, ptr(p.xyz), ptr(p.label), ptr(lo), ctypes.c_double(voxel), dims[0], dims[1],
+                dims[2], ptr(keys))
     skeys, order = torch.sort(keys, stable=True)
-    head = torch.ones(n_valid, dtype=torch.int64, device=coord.device)
-    head[1:] = skeys[1:n_valid] != skeys[:n_valid - 1]
+    head = torch.ones(p.n_valid, dtype=torch.int64, device=p.dev)
+    head[1:] = skeys[1:p.n_valid] != skeys[:p.n_valid - 1]
     slot = torch.cumsum(head, 0) - 1                         # the exclusive count of heads, at a head
-    return skeys, order, slot, slot[-1] + 1
+    return skeys, order, slot, int(call.read(slot[-1] + 1)[0])
 
 
-def _means(call, coord, label, n_valid, n_voxels, skeys, order, slot):
+def _means(call, p, n_voxels, skeys, order, slot):
     """-> (mean float32 [V, 3], mean_object int32 [V], mean_size int32 [V]) in the order of the keys: object, then vz, vy, vx"""
-    dev = coord.device
-    mean = torch.empty(n_voxels, 3, dtype=torch.float32, device=dev)
-    mean_object = torch.empty(n_voxels, dtype=torch.int32, device=dev)
-    mean_size = torch.empty(n_voxels, dtype=torch.int32, device=dev)
-    call("pointops2_supports_means_launcher", coord.shape[0], n_valid, n_voxels, ptr(coord), ptr(label), ptr(skeys), ptr(order), ptr(slot),
-         ptr(mean), ptr(mean_object), ptr(mean_size))
+    mean = torch.empty(n_voxels, 3, dtype=torch.float32, device=p.dev)
+    mean_object = torch.empty(n_voxels, dtype=torch.int32, device=p.dev)
+    mean_size = torch.empty(n_voxels, dtype=torch.int32, device=p.dev)
+    call.launch("pointops2_supports_means_launcher", p.n, p.n_valid, n_voxels, ptr(p.xyz), ptr(p.label), ptr(skeys), ptr(order), ptr(slot),
+                ptr(mean), ptr(mean_object), ptr(mean_size))
     return mean, mean_object, mean_size
 
 
@@ -815,14 +847,16 @@ def _inliers(call, pts, ranges, r2, nb_points):
     """-> keep uint8 [V] by original index of the mean: more than nb_points means of its object within reach, itself included"""
     n_means = pts.shape[0]
     keep = torch.zeros(n_means, dtype=torch.uint8, device=pts.device)
-    call("pointops2_supports_count_launcher", n_means, ptr(pts), ptr(ranges), ctypes.c_float(r2), nb_points, ptr(keep))
+    call.launch("pointops2_supports_count_launcher", n_means, ptr(pts), ptr(ranges), ctypes.c_float(r2), nb_points, ptr(keep))
     return keep
 
 
-def _survivors(keep, mean_object, n_objects):
-    """-> (kept: 0-d int64 on the device, alive bool [O]: the objects with a surviving mean); the caller reads kept and alive.sum() back"""
-    per_object = torch.zeros(n_objects, dtype=torch.int64, device=keep.device).index_add_(0, mean_object.long(), keep.long())
-    return keep.sum(), per_object > 0
+def _survivors(call, keep, mean_object, n_objects):
+    """-> (alive bool [O]: the objects with a surviving mean, the number of kept means, the number of such objects: both read back here, the
+    third read-back of clean_supports)"""
+    alive = torch.zeros(n_objects, dtype=torch.int64, device=keep.device).index_add_(0, mean_object.long(), keep.long()) > 0
+    n_kept, n_alive = call.read(torch.stack([keep.sum(), alive.sum()]))[0]
+    return alive, int(n_kept), int(n_alive)
 
 
 def _compact(mean, mean_object, keep, alive, n_kept, n_alive):
@@ -864,44 +898,27 @@ def clean_supports(coord, obj, n_objects=None, voxel=SUPPORT_VOXEL, radius=SUPPO
     label outside -1 .. O-1, non-finite coordinates, voxel or radius not finite and > 0, nb_points not an int >= 0, O > MAX_LABELS;
     ValueError when O * nx * ny * nz >= 2^61 for the voxels (or the cells of the radius grid) of the scene's box, or an axis exceeds
     MAX_CELLS_PER_AXIS.  N = 0, no point in an object or no surviving mean: empty tensors, nothing launched where nothing is to do."""
-    who = "clean_supports"
-    _check_tensors(who, coord, obj, "label")
-    voxel, r, r2, nb_points = _support_settings(who, voxel, radius, nb_points)
-    n_objects = _label_count(who, n_objects, "n_objects")
-    dev, n = coord.device, coord.shape[0]
-    LAST_SUPPORTS["launches"], LAST_SUPPORTS["readbacks"] = 0, 0
+    call = _Call("clean_supports", LAST_SUPPORTS, coord, obj)
+    voxel, r, r2, nb_points = _support_settings(call.who, voxel, radius, nb_points)
+    p = _labelled(call, coord, obj, n_objects, "n_objects")
 
     def nothing():
-        return (torch.zeros(0, 3, dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
-                torch.zeros(0, dtype=torch.int32, device=dev), 0)
+        return (torch.zeros(0, 3, dtype=torch.float32, device=p.dev), torch.zeros(0, dtype=torch.int32, device=p.dev),
+                torch.zeros(0, dtype=torch.int32, device=p.dev), 0)
 
-    if n == 0:
+    if p.n_valid == 0 or p.n_labels == 0:
         return nothing()
-    coord = coord.contiguous()
-    label = obj.to(torch.int32).contiguous()
+    vdims = _voxel_dims(call.who, p.n_labels, p.origin, p.top, voxel)
+    cell, dims = _dims(call.who, p.n_labels, p.origin, p.top, r)
 
-    LAST_SUPPORTS["readbacks"] += 1
-    _, l_min, l_max, n_valid, origin, top = _scan(who, coord, label)
-    n_objects = _label_range(who, n_objects, l_min, l_max, "n_objects")
-    if n_valid == 0 or n_objects == 0:
-        return nothing()
-    vdims = _voxel_dims(who, n_objects, origin, top, voxel)
-    cell = float(r) * CELL_MARGIN
-    dims = _dims(who, n_objects, origin, top, cell)
-
-    call = functools.partial(_launch, LAST_SUPPORTS, dev)
-    lo, _, _ = _boxes(coord, label, n_objects, dev, LAST_SUPPORTS)
-    skeys, order, slot, n_voxels = _voxel_means(call, coord, label, n_objects, n_valid, lo, voxel, vdims)
-    n_voxels = int(n_voxels.item())
-    LAST_SUPPORTS["readbacks"] += 1
-    mean, mean_object, _ = _means(call, coord, label, n_valid, n_voxels, skeys, order, slot)
+    lo, _, _ = _boxes(call, p)
+    skeys, order, slot, n_voxels = _voxel_means(call, p, lo, voxel, vdims)
+    mean, mean_object, _ = _means(call, p, n_voxels, skeys, order, slot)
 
     # the means lie inside the scene's box (a mean of fp32 values, rounded to fp32, does not leave their range), so its grid serves
-    pts, _, _, ranges = _grid(call, mean, mean_object, n_objects, n_voxels, origin, cell, dims)
+    pts, _, _, ranges = _grid(call, mean, mean_object, p.n_labels, n_voxels, p.origin, cell, dims)
     keep = _inliers(call, pts, ranges, r2, nb_points)
-    kept, alive = _survivors(keep, mean_object, n_objects)
-    n_kept, n_alive = (int(v) for v in torch.stack([kept, alive.sum()]).cpu().numpy())
-    LAST_SUPPORTS["readbacks"] += 1
+    alive, n_kept, n_alive = _survivors(call, keep, mean_object, p.n_labels)
     if n_kept == 0:
         return nothing()
     return _compact(mean, mean_object, keep, alive, n_kept, n_alive) + (n_alive,)
@@ -934,7 +951,7 @@ def detect_settings(voxel=SUPPORT_VOXEL, radius=SUPPORT_RADIUS, nb_points=SUPPOR
         raise TypeError(f"detect_boxes: unexpected settings {unknown}")
     _support_settings("clean_supports", voxel, radius, nb_points)
     _radius("merge_objects", merge_radius)
-    merge_sets(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0), np.zeros(0), np.zeros((0, 0), np.int32), np.zeros(0), overlap, min_neighbors)
+    _merge_settings(overlap, min_neighbors)
 
 
 def detect_boxes(coord, shift, pred, eps=None, min_samples=None, min_points=None, contact_radius=CONTACT_RADIUS, share=CONTACT_SHARE,

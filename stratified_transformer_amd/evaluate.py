@@ -305,7 +305,7 @@ def dense_points(coord, eps=0.1, min_samples=5, min_points=50):
         raise ValueError(f"dense_points: min_points must be an int >= 0, got {min_points!r}")
     none = torch.empty(0, dtype=torch.int64, device=coord.device)
     if coord.shape[0] == 0:
-        cluster._settings(eps, min_samples, 1)
+        cluster.dbscan_settings(eps, min_samples, 1)
         return coord[:0], none
     labels, _, n_clusters = cluster.dbscan(coord.float(), eps, min_samples)
     if int(n_clusters.sum().item()) == 0:

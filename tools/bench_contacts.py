@@ -5,7 +5,7 @@ missing GPU is an error).
     python tools/bench_contacts.py [--points 100000] [--reps 30] [--warmup 3] [--no-host] [--out profiles/contacts_bench.json]
 
 The instances come from cluster.instances on the same scene with a zero shift (not timed).  `objects_ms`, `contacts_ms` (count and the
-quadratic min_d2 sweep) and `count_ms` (the grid walk alone, what objects runs): medians over `reps` calls after `warmup` calls, device
+quadratic min_d2 sweep) and `count_ms` (the grid and its walk alone, the step objects runs behind its read-back up front): medians over `reps` calls after `warmup` calls, device
 events around the call; objects() ends in a read-back, so `objects_host_ms` gives the host clock around the same calls as well.
 `host_loop_ms`: the pairing loop of `instantiation_eval` (util/train_utils.py:601-647) as tests/contacts_oracle.pair_list restates it,
 with one scipy.spatial.distance.cdist per (edge instance, face instance) as the reference computes it, on the same instances and the
@@ -124,7 +124,10 @@ def main():
     objects_calls = dict(cluster.LAST_CONTACTS)
     contacts_ms, contacts_host_ms, (count, min_d2) = device_ms(lambda: cluster.contacts(coord, instance, 0.08, n_inst), a.reps, a.warmup)
     contacts_calls = dict(cluster.LAST_CONTACTS)
-    count_ms, count_host_ms, _ = device_ms(lambda: cluster._contacts(coord, instance, 0.08, n_inst, False, "contacts"), a.reps, a.warmup)
+    call = cluster._Call("objects", cluster.LAST_CONTACTS, coord, instance)         # objects' count step, on its prologue's result
+    r, r2 = cluster._radius(call.who, 0.08)
+    p = cluster._labelled(call, coord, instance, n_inst)
+    count_ms, count_host_ms, _ = device_ms(lambda: cluster._contact_tables(call, p, r, r2, False), a.reps, a.warmup)
 
     result = {"tool": "bench_contacts", "device": torch.cuda.get_device_name(0), "points": len(coord_h), "boxes": n_boxes,
               "edge_point_share": round(float((pred_h >= 6).mean()), 4), "instances": n_inst, "face_instances": int((cls < 6).sum()),

@@ -7,16 +7,14 @@ JSON line (GPU box only; a missing GPU is an error).
 
 The objects come from cluster.instances and cluster.objects on the same scene with a zero shift (not timed).  `merge_ms`: median over
 `reps` calls of merge_objects after `warmup` calls, device events around the call; it ends in a read-back, so `merge_host_ms` gives the
-host clock around the same calls.  The parts, each timed the same way on its own: `boxes_ms` (label_boxes' launch), `grid_ms` (keys,
-torch.sort, prepare), `rows_ms` (the fixed-radius walk), `unique_ms` (border selection and torch.unique) and `host_loop_ms` (merge_sets on
-the read-back tables, host clock).  `--spacing`: distance between the boxes' corners; at the default 1.3 of bench_contacts the boxes stand
-0.5 apart and nothing is within reach of anything, at 0.85 neighbours are 0.05 / 0.15 apart and most points are border points.
+host clock around the same calls.  The parts are merge_objects' own step functions on its prologue's result, each timed the same way on
+its own: `grid_ms` (keys, torch.sort, prepare), `boxes_ms` (label_boxes' launch), `rows_ms` (the fixed-radius walk), `unique_ms` (border
+selection and torch.unique) and `host_loop_ms` (merge_sets on the read-back tables, host clock).
+`--spacing`: distance between the boxes' corners; at the default 1.3 of bench_contacts the boxes stand 0.5 apart and nothing is within reach of anything, at 0.85 neighbours are 0.05 / 0.15 apart and most points are border points.
 The host reference is the literal loop of tests/merge_oracle.py (per pair of sets one brute-force pass over all pairs of their points,
 what the reference's cdist does) on the same machine, on a scene of `--host-points` points, where one pair's matrix still fits;
 `small_*` are the device's times on that same scene and `small_agrees` says whether both give the same sets and boxes."""
 import argparse
-import ctypes
-import functools
 import json
 import os
 import statistics
@@ -31,7 +29,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_contacts import box, device_ms  # noqa: E402
 from stratified_transformer_amd import cluster  # noqa: E402
-from stratified_transformer_amd._lib import ptr  # noqa: E402
 
 
 def make_scene(points, spacing, seed=0):
@@ -56,34 +53,16 @@ def objects_of(coord_h, pred_h):
 
 
 def parts_ms(coord, obj, n_objects, reps, warmup):
-    """the steps of merge_objects one by one, on the inputs it would hand them"""
-    dev, n = coord.device, coord.shape[0]
-    label = obj.to(torch.int32).contiguous()
-    member = label >= 0
-    n_valid = int(member.sum().item())
-    r = np.float32(cluster.MERGE_RADIUS)
-    cell = float(r) * cluster.CELL_MARGIN
-    origin = coord[member].amin(0).double().cpu().numpy()
-    top = coord[member].amax(0).double().cpu().numpy()
-    dims = cluster._dims("bench_merge", 1, origin, top, cell)
-    call = functools.partial(cluster._launch, cluster.LAST_MERGE, dev)
-    words = (n_objects + 31) // 32
-
-    def grid():
-        pts, order, _, ranges = cluster._grid(call, coord, member.to(torch.int32) - 1, 1, n_valid, origin, cell, dims)
-        return pts, label[order[:n_valid]].contiguous(), ranges
-
-    def reach_rows():
-        rows = torch.zeros(n_valid, words, dtype=torch.int32, device=dev)
-        call("pointops2_reach_rows_launcher", n_valid, n_objects, ptr(pts), ptr(slabel), ptr(ranges), ctypes.c_float(np.float32(r * r)), ptr(rows))
-        return rows
-
+    """the steps of merge_objects one by one: its own step functions, in its order, on the prologue's result"""
+    call = cluster._Call("merge_objects", cluster.LAST_MERGE, coord, obj)
+    r, r2 = cluster._radius(call.who, cluster.MERGE_RADIUS)
+    p = cluster._labelled(call, coord, obj, n_objects, "n_objects")
     out = {}
-    out["boxes_ms"], _, (lo, hi, size) = device_ms(lambda: cluster._boxes(coord, label, n_objects, dev), reps, warmup)
-    out["grid_ms"], _, (pts, slabel, ranges) = device_ms(grid, reps, warmup)
-    out["rows_ms"], _, rows = device_ms(reach_rows, reps, warmup)
+    out["grid_ms"], _, (pts, slabel, ranges) = device_ms(lambda: cluster._label_grid(call, p, r), reps, warmup)
+    out["boxes_ms"], _, (lo, hi, size) = device_ms(lambda: cluster._boxes(call, p), reps, warmup)
+    out["rows_ms"], _, rows = device_ms(lambda: cluster._rows(call, pts, slabel, ranges, p.n_labels, r2), reps, warmup)
     out["unique_ms"], _, (pat, count) = device_ms(lambda: cluster._patterns(slabel, rows), reps, warmup)
-    tables = (lo.cpu().numpy(), hi.cpu().numpy(), size.cpu().numpy(), pat[:, 0].cpu().numpy(), pat[:, 1:].cpu().numpy(), count.cpu().numpy())
+    tables = cluster._merge_tables(call, lo, hi, size, pat, count)
     times = []
     for _ in range(reps):
         t0 = time.perf_counter()
@@ -91,7 +70,7 @@ def parts_ms(coord, obj, n_objects, reps, warmup):
         times.append((time.perf_counter() - t0) * 1e3)
     out["host_loop_ms"] = statistics.median(times)
     out = {k: round(v, 4) for k, v in out.items()}
-    out.update(cells=dims, labelled_points=n_valid, border_points=int((rows != 0).any(1).sum().item()), patterns=int(pat.shape[0]))
+    out.update(cells=cluster._dims(call.who, 1, p.origin, p.top, r)[1], labelled_points=p.n_valid, border_points=int((rows != 0).any(1).sum().item()), patterns=int(pat.shape[0]))
     return out
 
 

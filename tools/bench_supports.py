@@ -8,16 +8,16 @@ line (GPU box only; a missing GPU is an error).
 The objects come from cluster.instances and cluster.objects on the same scene with a zero shift (not timed).  Every object then gets
 `--strays` seeded stray points under its number, 0.15 to 0.5 outside its box, so that the outlier pass removes something.
 `supports_ms`: median over `reps` calls of clean_supports after `warmup` calls, device events around the call; it ends in a read-back, so
-`supports_host_ms` gives the host clock around the same calls.  The parts, each timed the same way on its own: `boxes_ms` (label_boxes'
-launch), `keys_sort_ms` (voxel keys, torch.sort, head flags and their scan), `means_ms`, `grid_ms` (keys, torch.sort, prepare on the
-means), `count_ms` (the fixed-radius walk) and `compact_ms` (survivors per object, compaction and renumbering with torch).
+`supports_host_ms` gives the host clock around the same calls.  The parts are clean_supports' own step functions on its prologue's result,
+each timed the same way on its own: `boxes_ms` (label_boxes' launch), `keys_sort_ms` (voxel keys, torch.sort, head flags, their scan and
+the read-back of the number of voxels), `means_ms`, `grid_ms` (keys, torch.sort, prepare on the means), `count_ms` (the fixed-radius walk)
+and `compact_ms` (survivors per object with their read-back, compaction and renumbering with torch).
 The host restatement is the per-object loop of tests/supports_oracle.py (a dict of float64 sums per voxel, in Python - Open3D itself is on
 no machine here) on the same machine in the same run (median of 3), with scipy's cKDTree for the counts where scipy imports
 (`host_counts: "ckdtree"`, float64 distances: a pair within about 1e-6 of the radius may fall on the other side, `host_kept` is reported
 beside `kept`); otherwise with the oracle's dense fp32 matrix on a scene of `--host-points` points, where it fits (`host_counts: "dense"`,
 `host_points` says the size, `small_*` are the device's times on that same scene)."""
 import argparse
-import functools
 import json
 import os
 import statistics
@@ -58,35 +58,28 @@ def scene_with_strays(points, strays, seed=0):
 
 
 def parts_ms(coord, obj, n_objects, reps, warmup):
-    """the steps of clean_supports one by one, on the inputs it would hand them"""
-    dev = coord.device
-    label = obj.to(torch.int32).contiguous()
-    _, _, _, n_valid, origin, top = cluster._scan("bench_supports", coord, label)
-    voxel, r, r2, nb_points = cluster._support_settings("bench_supports", cluster.SUPPORT_VOXEL, cluster.SUPPORT_RADIUS, cluster.SUPPORT_NB_POINTS)
-    vdims = cluster._voxel_dims("bench_supports", n_objects, origin, top, voxel)
-    cell = float(r) * cluster.CELL_MARGIN
-    dims = cluster._dims("bench_supports", n_objects, origin, top, cell)
-    call = functools.partial(cluster._launch, cluster.LAST_SUPPORTS, dev)
+    """the steps of clean_supports one by one: its own step functions, in its order, on the prologue's result"""
+    call = cluster._Call("clean_supports", cluster.LAST_SUPPORTS, coord, obj)
+    voxel, r, r2, nb_points = cluster._support_settings(call.who, cluster.SUPPORT_VOXEL, cluster.SUPPORT_RADIUS, cluster.SUPPORT_NB_POINTS)
+    p = cluster._labelled(call, coord, obj, n_objects, "n_objects")
+    vdims = cluster._voxel_dims(call.who, p.n_labels, p.origin, p.top, voxel)
+    cell, dims = cluster._dims(call.who, p.n_labels, p.origin, p.top, r)
 
     def compact():
-        kept, alive = cluster._survivors(keep, mean_object, n_objects)
-        n_kept, n_alive = (int(v) for v in torch.stack([kept, alive.sum()]).cpu().numpy())
+        alive, n_kept, n_alive = cluster._survivors(call, keep, mean_object, p.n_labels)
         return cluster._compact(mean, mean_object, keep, alive, n_kept, n_alive)
 
     out = {}
-    out["boxes_ms"], _, (lo, _, _) = device_ms(lambda: cluster._boxes(coord, label, n_objects, dev, cluster.LAST_SUPPORTS), reps, warmup)
-    out["keys_sort_ms"], _, (skeys, order, slot, n_voxels) = device_ms(
-        lambda: cluster._voxel_means(call, coord, label, n_objects, n_valid, lo, voxel, vdims), reps, warmup)
-    n_voxels = int(n_voxels.item())
-    out["means_ms"], _, (mean, mean_object, mean_size) = device_ms(
-        lambda: cluster._means(call, coord, label, n_valid, n_voxels, skeys, order, slot), reps, warmup)
+    out["boxes_ms"], _, (lo, _, _) = device_ms(lambda: cluster._boxes(call, p), reps, warmup)
+    out["keys_sort_ms"], _, (skeys, order, slot, n_voxels) = device_ms(lambda: cluster._voxel_means(call, p, lo, voxel, vdims), reps, warmup)
+    out["means_ms"], _, (mean, mean_object, mean_size) = device_ms(lambda: cluster._means(call, p, n_voxels, skeys, order, slot), reps, warmup)
     out["grid_ms"], _, (pts, _, _, ranges) = device_ms(
-        lambda: cluster._grid(call, mean, mean_object, n_objects, n_voxels, origin, cell, dims), reps, warmup)
+        lambda: cluster._grid(call, mean, mean_object, p.n_labels, n_voxels, p.origin, cell, dims), reps, warmup)
     out["count_ms"], _, keep = device_ms(lambda: cluster._inliers(call, pts, ranges, r2, nb_points), reps, warmup)
     out["compact_ms"], _, _ = device_ms(compact, reps, warmup)
     out = {k: round(v, 4) for k, v in out.items()}
-    out.update(voxel_dims=vdims, cells=dims, labelled_points=n_valid, voxels=n_voxels, longest_run=int(mean_size.max().item()),
-               mean_run=round(n_valid / n_voxels, 3))
+    out.update(voxel_dims=vdims, cells=dims, labelled_points=p.n_valid, voxels=n_voxels, longest_run=int(mean_size.max().item()),
+               mean_run=round(p.n_valid / n_voxels, 3))
     return out
 
 
