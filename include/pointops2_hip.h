@@ -450,6 +450,28 @@ void grouped_max_forward_launcher(int m, int n_s, int k, int c, int row_type, co
 void grouped_max_backward_launcher(int m, int n_s, int k, int c, int row_type, const void *grad_out, const unsigned char *arg,
                                    const int *src_offsets, const int *src_pair, void *grad_feat);
 
+/* ---- residual add + DropPath row scale + LayerNorm in one pass over the rows: the glue of a pre-norm block
+ * (model/stratified_transformer.py:245-246 and the next block's :241; model/swin3d_transformer.py:206-210) ----
+ *   forward:  z[n,ch] = x[n,ch] + s[n] * y[n,ch] (s NULL: x + y; y NULL: x), s * y rounded before the add;
+ *             o[n,ch] = ((z - mean_n) * rstd_n) * gamma[ch] + beta[ch], mean_n and the biased var_n by two passes over the row,
+ *             rstd_n = 1 / sqrt(var_n + eps); stat[n] = (mean_n, rstd_n).  z may be NULL (not wanted: with y NULL it is x).
+ *   backward: xhat = (z - mean) * rstd, g = grad_o * gamma, dz = rstd * ((g - mean_ch(g)) - xhat * mean_ch(g * xhat)) + grad_z;
+ *             grad_x = dz, grad_y = s[n] * dz (NULL: not wanted), grad_gamma[ch] = sum_n grad_o * xhat, grad_beta[ch] = sum_n grad_o.
+ *             grad_o or grad_z may be NULL (a zero gradient).  grad_x [n,c] and grad_y [n,c] are FULLY WRITTEN.  The two parameter
+ *             gradients take no float atomics: workgroup b writes its rows' sums to partials[b] (partials: fp32 [partial_rows, 2, c],
+ *             a workspace, no zero-fill; the grid is at most partial_rows workgroups) and a second kernel adds them in a fixed order:
+ *             bitwise reproducible on one device.  partials NULL: grad_gamma / grad_beta are not computed.
+ * x, z, grad_x, grad_z [n,c], gamma, beta [c], s [n], stat [n,2]: fp32.  y / grad_y have y_type and o / grad_o have o_type, each
+ * POINTOPS2_ROWS_F32, _F16 or _BF16, widened exactly, arithmetic in fp32 without fused operations, one rounding to the row type.
+ * 1 <= c <= 1024 and the row types are checked: otherwise an error is recorded and nothing is launched; n = 0 is a no-op; offsets
+ * are 64-bit, so n * c is bounded by n alone.  c % 4 == 0 with operands aligned for 16-byte (fp32) / 8-byte (half) accesses takes
+ * four channels per lane, anything else one channel per lane: same results.  A NaN or Inf stays in its row. */
+void residual_norm_forward_launcher(int n, int c, int y_type, int o_type, const float *x, const void *y, const float *s, const float *gamma,
+                                    const float *beta, float eps, float *z, void *o, float *stat);
+void residual_norm_backward_launcher(int n, int c, int y_type, int o_type, const void *grad_o, const float *grad_z, const float *z,
+                                     const float *stat, const float *s, const float *gamma, float *grad_x, void *grad_y, float *partials,
+                                     int partial_rows, float *grad_gamma, float *grad_beta);
+
 /* ---- DBSCAN: the clustering behind the model (util/train_utils.py:549-566 runs sklearn.cluster.DBSCAN per predicted class) ----
  * Neighbours: same group and d2 <= eps2[group], in fp32 with d2 = ((dx*dx) + (dy*dy)) + (dz*dz), dx = xi - xj, no fused operation; a
  * point is its own neighbour.  Core: at least min_samples[group] neighbours.  Clusters: the connected components of the core points,

@@ -20,7 +20,7 @@ model/stratified_transformer.py imports and runs unmodified under PyTorch-ROCm.
 import sys
 
 __all__ = ["install", "build", "dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "scene_eval",
-           "clean_supports", "box_supports", "scene_predict", "dense_points", "detect_boxes", "detect_scene"]
+           "clean_supports", "box_supports", "scene_predict", "dense_points", "detect_boxes", "detect_scene", "install_fused_blocks"]
 
 
 def __getattr__(name):
@@ -33,6 +33,9 @@ def __getattr__(name):
     if name in ("scene_eval", "scene_predict", "dense_points", "detect_scene"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name == "install_fused_blocks":  # layers.install_fused_blocks: the blocks' residual / DropPath / LayerNorm glue on csrc/rownorm.hip
+        from . import layers
+        return layers.install_fused_blocks
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -99,6 +99,8 @@ SIGNATURES = {
     "kpconv_aggregate_backward_launcher": [I, I, I, I, I, P, P, P, P, F, P, P],
     "grouped_max_forward_launcher": [I, I, I, I, I, P, P, P, P],
     "grouped_max_backward_launcher": [I, I, I, I, I, P, P, P, P, P],
+    "residual_norm_forward_launcher": [I, I, I, I, P, P, P, P, P, F, P, P, P],
+    "residual_norm_backward_launcher": [I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, P],
     "pointops2_dbscan_keys_launcher": [I, I, P, P, D, D, D, D, I, I, I, P],
     "pointops2_dbscan_prepare_launcher": [I, I, I, I, I, P, P, P, P, P, P],
     "pointops2_dbscan_core_launcher": [I, I, P, P, P, P, P, P, P, P],

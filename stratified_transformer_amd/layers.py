@@ -36,6 +36,10 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
     swin_window_attention_forward - one `index_build.swin_stage_index_hip` per stage with both patterns' cell plans (every cell a dense
     small window: no flagged tile entries), the same `fused.cell_attention*` per block.  No sampler, no side streams.
 
+  * The blocks' glue (off by default): `install_fused_blocks()` / `patch_block_classes()` rebind SwinTransformerBlock.forward of either
+    model file to fused_block_forward / swin_fused_block_forward - DropPath, residual add, LayerNorm and the cast in front of the next
+    Linear as one pass of pointops.residual_norm (csrc/rownorm.hip) at both residual sites; the four GEMMs and GELU stay with torch.
+
 Numbers: the same sums in another order (tests/test_hip_parity.py::test_installed_fast_layers_against_the_reference_layer:
 output and every parameter gradient of a depth-2 BasicLayer with TransitionDown against the reference's own run, <= 1e-3).
 """
@@ -208,14 +212,118 @@ def _blocks(self, feats, xyz, xyz_c, offset_i, downsample_idx, attn0, h, d, N):
     even, odd, _ = index_build.stage_index_hip(xyz_c, offset_i, float(self.window_size), float(attn0.quant_size), downsample_idx,
                                                cell_table_rows=L if want_cells else None,
                                                cell_max_queries=index_build.cell_query_cap(N, h) if want_cells else 0)
-    for i, blk in enumerate(self.blocks):                                                 # :302-319
-        bi = even if i % 2 == 0 else odd
-        blk.attn._sta_block = bi
-        try:
-            feats = blk(feats, xyz, bi.index_0, bi.index_1, bi.offsets, bi.n_max)
-        finally:
-            blk.attn._sta_block = None
+    with chained_blocks(self.blocks):
+        for i, blk in enumerate(self.blocks):                                             # :302-319
+            bi = even if i % 2 == 0 else odd
+            blk.attn._sta_block = bi
+            try:
+                feats = blk(feats, xyz, bi.index_0, bi.index_1, bi.offsets, bi.n_max)
+            finally:
+                blk.attn._sta_block = None
     return feats
+
+
+# ---- the block's glue on csrc/rownorm.hip (install_fused_blocks / patch_block_classes; off by default) ----
+# A pre-norm block (:235-248) follows each of its two residual adds by a LayerNorm: `short_cut + drop_path(attn)` by norm2, and
+# `feats + drop_path(mlp)` by the NEXT block's norm1.  pointops.residual_norm does add, DropPath scale, LayerNorm and the cast for the
+# following Linear in one pass.  The second site spans two blocks: the loop that calls the blocks names each block's successor
+# (`_sta_next`, through chained_blocks) and the block leaves the successor's norm1 result with it (`_sta_norm1`), valid for exactly the
+# tensor object it returned.  Both attributes live in the modules' __dict__ (no submodule is registered) and are cleared in a `finally`.
+class chained_blocks:
+    """`with chained_blocks(blocks): for blk in blocks: feats = blk(feats, ...)` - tells every block with the fused forward which block
+    runs next, so that it computes that block's norm1 with its own second residual add.  Without fused blocks it does nothing."""
+
+    def __init__(self, blocks):
+        self.blocks = list(blocks)
+
+    def __enter__(self):
+        for blk, nxt in zip(self.blocks[:-1], self.blocks[1:]):
+            if _is_fused(blk) and _is_fused(nxt):
+                blk.__dict__["_sta_next"] = nxt
+        return self
+
+    def __exit__(self, *exc):
+        for blk in self.blocks:
+            blk.__dict__.pop("_sta_next", None)
+            blk.__dict__.pop("_sta_norm1", None)
+        return False
+
+
+def _is_fused(blk):
+    return getattr(type(blk), "forward", None) in (fused_block_forward, swin_fused_block_forward)
+
+
+def _norm_ok(norm, c):
+    return (type(norm) is torch.nn.LayerNorm and tuple(norm.normalized_shape) == (c,) and norm.weight is not None and norm.bias is not None
+            and norm.weight.dtype == torch.float32 and norm.bias.dtype == torch.float32 and norm.weight.is_cuda and norm.bias.is_cuda)
+
+
+def _known_drop_path(dp):
+    """nn.Identity, or a module with timm 0.4.9's DropPath semantics (compat.DropPath): x / keep_prob * floor(keep_prob + rand)"""
+    return isinstance(dp, torch.nn.Identity) or (hasattr(dp, "drop_prob") and getattr(dp, "scale_by_keep", True))
+
+
+def drop_path_row_scale(drop_path, like):
+    """mask / keep_prob [n] f32 of the DropPath call `drop_path(like)`, or None where that call returns its argument (nn.Identity, eval
+    mode, drop_prob 0).  The mask is drawn with the module's own torch.rand call - shape [n, 1, ...], like's dtype and device - so a
+    seeded run drops the rows the module would drop."""
+    if isinstance(drop_path, torch.nn.Identity) or not drop_path.drop_prob or not drop_path.training:
+        return None
+    keep = 1 - drop_path.drop_prob
+    shape = (like.shape[0],) + (1,) * (like.ndim - 1)
+    mask = (keep + torch.rand(shape, dtype=like.dtype, device=like.device)).floor_()
+    return mask.reshape(-1).float().div_(keep)
+
+
+def _glue_dtype(dev):
+    """dtype of the rows handed to the next Linear: autocast's when it is on (the Linear then has nothing to cast), else f32"""
+    if hasattr(torch, "get_autocast_dtype"):
+        on, dt = torch.is_autocast_enabled("cuda"), torch.get_autocast_dtype("cuda")
+    else:
+        on, dt = torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype()
+    if dev.type == "cuda" and on:
+        return dt if dt in (torch.float16, torch.bfloat16) else None
+    return torch.float32
+
+
+def _fused_block(self, feats, attend):
+    """the block's forward around attend(norm1 rows) = self.attn(...); None: the conditions of the fused path do not hold"""
+    if not (torch.is_tensor(feats) and feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and 1 <= feats.shape[1] <= 1024):
+        return None
+    c = feats.shape[1]
+    odt = _glue_dtype(feats.device)
+    if odt is None or not (_norm_ok(self.norm1, c) and _norm_ok(self.norm2, c) and _known_drop_path(self.drop_path)):
+        return None
+    handed = self.__dict__.pop("_sta_norm1", None)
+    if handed is not None and handed[0] is feats and handed[1].dtype == odt:
+        n1 = handed[1]
+    else:
+        _, n1 = P.residual_norm(feats.contiguous(), None, None, self.norm1.weight, self.norm1.bias, self.norm1.eps, odt)          # :241
+    a = attend(n1)                                                                                                                 # :243
+    s1 = drop_path_row_scale(self.drop_path, a)
+    z, n2 = P.residual_norm(feats.contiguous(), a.contiguous(), s1, self.norm2.weight, self.norm2.bias, self.norm2.eps, odt)      # :245, norm2 of :246
+    m = self.mlp(n2)
+    s2 = drop_path_row_scale(self.drop_path, m)
+    nxt = self.__dict__.get("_sta_next")
+    if nxt is not None and _norm_ok(nxt.norm1, c):
+        out, n1_next = P.residual_norm(z, m.contiguous(), s2, nxt.norm1.weight, nxt.norm1.bias, nxt.norm1.eps, odt)              # :246, the next :241
+        nxt.__dict__["_sta_norm1"] = (out, n1_next)
+        return out
+    return z + m if s2 is None else z + m * s2.unsqueeze(1)                                                                       # :246
+
+
+def fused_block_forward(self, feats, xyz, index_0, index_1, index_0_offsets, n_max):
+    """Replacement of SwinTransformerBlock.forward (model/stratified_transformer.py:235-248), same arguments, same result: both residual
+    sites on pointops.residual_norm.  The original forward runs for CPU tensors, feats that are not [N, C <= 1024] f32, norms that are
+    not nn.LayerNorm with f32 affine parameters over C, and a drop_path that is neither nn.Identity nor a DropPath with `drop_prob`."""
+    out = _fused_block(self, feats, lambda rows: self.attn(rows, xyz, index_0, index_1, index_0_offsets, n_max))
+    return out if out is not None else _original(self)(self, feats, xyz, index_0, index_1, index_0_offsets, n_max)
+
+
+def swin_fused_block_forward(self, feats, xyz, index_0, index_0_offsets, n_max, index_1, shift_size):
+    """fused_block_forward for the Swin3D block (model/swin3d_transformer.py:197-212)"""
+    out = _fused_block(self, feats, lambda rows: self.attn(rows, xyz, index_0, index_0_offsets, n_max, index_1, shift_size))
+    return out if out is not None else _original(self)(self, feats, xyz, index_0, index_0_offsets, n_max, index_1, shift_size)
 
 
 def basic_layer_forward(self, feats, xyz, offset):
@@ -405,13 +513,14 @@ def swin_basic_layer_forward(self, feats, xyz, offset):
                                                     cell_table_rows=L if d == 16 and L <= 80 else None,
                                                     cell_max_queries=index_build.cell_query_cap(N, h))
     shift_size = 1 / 2 * torch.tensor([self.window_size] * 3).type_as(xyz).to(xyz.device)   # :234,261
-    for i, blk in enumerate(self.blocks):                                                 # :282-289
-        bi = even if i % 2 == 0 else odd
-        blk.attn._sta_block = bi
-        try:
-            feats = blk(feats, xyz, bi.index_0, bi.offsets, bi.n_max, bi.index_1, 0.0 if i % 2 == 0 else shift_size)
-        finally:
-            blk.attn._sta_block = None
+    with chained_blocks(self.blocks):
+        for i, blk in enumerate(self.blocks):                                             # :282-289
+            bi = even if i % 2 == 0 else odd
+            blk.attn._sta_block = bi
+            try:
+                feats = blk(feats, xyz, bi.index_0, bi.offsets, bi.n_max, bi.index_1, 0.0 if i % 2 == 0 else shift_size)
+            finally:
+                blk.attn._sta_block = None
     if self.downsample:                                                                   # :291-294
         feats_down, xyz_down, offset_down = self.downsample(feats, xyz, offset)
     else:
@@ -472,6 +581,31 @@ def install_fast_layers(module=None):
     done = []
     for m in mods:
         done += patch_classes(getattr(m, "BasicLayer", None), getattr(m, "WindowAttention", None), getattr(m, "TransitionDown", None))
+    return done
+
+
+def patch_block_classes(block_cls=None, swin_block_cls=None):
+    """Rebinds `forward` of a SwinTransformerBlock class with the Stratified call convention (block_cls) and / or the Swin3D one
+    (swin_block_cls) to the fused forms on pointops.residual_norm; returns what was patched.  uninstall_fast_layers() restores them."""
+    return _patch(((block_cls, fused_block_forward), (swin_block_cls, swin_fused_block_forward)))
+
+
+def install_fused_blocks(module=None):
+    """Patches SwinTransformerBlock of the reference's model module(s): the imported module (or a list), taken as Swin3D's when its name
+    ends in `swin3d_transformer`.  Default: `model.stratified_transformer` (which must be importable, see install_fast_layers; and
+    `model.stratified_transformer_backup` when it is already imported) and `model.swin3d_transformer` when it is already imported.
+    Independent of install_fast_layers / install_swin_layers: with those the next block's norm1 is fused too (the hand-off)."""
+    import importlib
+    if module is None:
+        mods = [importlib.import_module("model.stratified_transformer")]
+        mods += [sys.modules[m] for m in ("model.stratified_transformer_backup", "model.swin3d_transformer") if m in sys.modules]
+    else:
+        mods = list(module) if isinstance(module, (list, tuple)) else [module]
+    done = []
+    for m in mods:
+        blk = getattr(m, "SwinTransformerBlock", None)
+        swin = getattr(m, "__name__", "").endswith("swin3d_transformer")
+        done += patch_block_classes(None if swin else blk, blk if swin else None)
     return done
 
 

@@ -125,6 +125,71 @@ def grouped_max_backward(m, n_s, k, c, grad_out, arg, src_offsets, src_pair, gra
           opts=opts)
 
 
+# csrc/rownorm.hip (no counterpart in the reference's launcher set: residual add, DropPath row scale and LayerNorm of a pre-norm block)
+RESIDUAL_NORM_MAX_C = 1024
+RESIDUAL_NORM_PARTIAL_ROWS = 1024  # most workgroups of the backward: one row of `partials` each
+
+
+def _opt(t, dtype, shape, name):
+    if t is not None:
+        _chk((t, dtype, name))
+        _shaped(t, shape, name)
+
+
+def _residual_norm_sizes(n, c):
+    n, c = int(n), int(c)
+    if n < 0:
+        raise ValueError(f"n: expected a row count >= 0, got {n}")
+    if not 1 <= c <= RESIDUAL_NORM_MAX_C:
+        raise ValueError(f"c: expected 1 <= c <= {RESIDUAL_NORM_MAX_C}, got {c}")
+    return n, c
+
+
+def residual_norm_forward(n, c, x, y, row_scale, weight, bias, eps, z, o, stat, *, opts=None):
+    """z [n,c] f32 (or None: not wanted), o [n,c] f32 / f16 / bf16, stat [n,2] f32 <- x [n,c] f32, y [n,c] f32 / f16 / bf16 or None,
+    row_scale [n] f32 or None, weight / bias [c] f32: z = x + row_scale[:, None] * y, o = LayerNorm(z), stat = (mean, rstd) per row"""
+    n, c = _residual_norm_sizes(n, c)
+    _chk((x, F32, "x"), (weight, F32, "weight"), (bias, F32, "bias"), (stat, F32, "stat"))
+    _shaped(x, (n, c), "x"), _shaped(weight, (c,), "weight"), _shaped(bias, (c,), "bias"), _shaped(stat, (n, 2), "stat")
+    ot = _row_type(o, "o")
+    _opt(o, o.dtype, (n, c), "o")
+    yt = _row_type(y, "y") if y is not None else _lib.ROW_TYPES[F32]
+    _opt(y, None if y is None else y.dtype, (n, c), "y")
+    _opt(row_scale, F32, (n,), "row_scale")
+    _opt(z, F32, (n, c), "z")
+    if row_scale is not None and y is None:
+        raise ValueError("row_scale: given without y")
+    _call("residual_norm_forward_launcher", x, n, c, yt, ot, ptr(x), ptr(y), ptr(row_scale), ptr(weight), ptr(bias), float(eps), ptr(z), ptr(o),
+          ptr(stat), opts=opts)
+
+
+def residual_norm_backward(n, c, grad_o, grad_z, z, stat, row_scale, weight, grad_x, grad_y, partials, grad_weight, grad_bias, *, opts=None):
+    """grad_x [n,c] f32, grad_y [n,c] (y's dtype; None: not wanted), grad_weight / grad_bias [c] f32 (with partials, a
+    [rows <= 1024, 2, c] f32 workspace; all three None: not wanted) <- grad_o [n,c] (o's dtype) or None, grad_z [n,c] f32 or None,
+    z, stat, row_scale, weight of the forward.  Every output is fully written."""
+    n, c = _residual_norm_sizes(n, c)
+    _chk((z, F32, "z"), (stat, F32, "stat"), (weight, F32, "weight"), (grad_x, F32, "grad_x"))
+    _shaped(z, (n, c), "z"), _shaped(stat, (n, 2), "stat"), _shaped(weight, (c,), "weight"), _shaped(grad_x, (n, c), "grad_x")
+    ot = _row_type(grad_o, "grad_o") if grad_o is not None else _lib.ROW_TYPES[F32]
+    _opt(grad_o, None if grad_o is None else grad_o.dtype, (n, c), "grad_o")
+    yt = _row_type(grad_y, "grad_y") if grad_y is not None else _lib.ROW_TYPES[F32]
+    _opt(grad_y, None if grad_y is None else grad_y.dtype, (n, c), "grad_y")
+    _opt(grad_z, F32, (n, c), "grad_z")
+    _opt(row_scale, F32, (n,), "row_scale")
+    rows = 0
+    if partials is not None or grad_weight is not None or grad_bias is not None:
+        for t, name in ((partials, "partials"), (grad_weight, "grad_weight"), (grad_bias, "grad_bias")):
+            if t is None:
+                raise ValueError(f"{name}: partials, grad_weight and grad_bias are given together or not at all")
+        _chk((partials, F32, "partials"), (grad_weight, F32, "grad_weight"), (grad_bias, F32, "grad_bias"))
+        _shaped(grad_weight, (c,), "grad_weight"), _shaped(grad_bias, (c,), "grad_bias")
+        rows = int(partials.shape[0]) if partials.dim() == 3 else 0
+        if not 1 <= rows <= RESIDUAL_NORM_PARTIAL_ROWS or tuple(partials.shape[1:]) != (2, c):
+            raise ValueError(f"partials: expected shape [1 <= rows <= {RESIDUAL_NORM_PARTIAL_ROWS}, 2, {c}], got {list(partials.shape)}")
+    _call("residual_norm_backward_launcher", z, n, c, yt, ot, ptr(grad_o), ptr(grad_z), ptr(z), ptr(stat), ptr(row_scale), ptr(weight),
+          ptr(grad_x), ptr(grad_y), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), opts=opts)
+
+
 # attention/attention_cuda.cpp
 def attention_step1_forward_cuda(N, M, h, C, q, k, index0, index1, attn, *, opts=None):
     _chk((q, F32, "q"), (k, F32, "k"), (index0, I32, "index0"), (index1, I32, "index1"), (attn, F32, "attn"))

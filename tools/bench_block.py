@@ -1,0 +1,214 @@
+"""The glue of a pre-norm transformer block - DropPath, residual add, LayerNorm and the cast in front of the next Linear - as torch runs it
+(the composite) beside pointops.residual_norm (csrc/rownorm.hip), on the same GPU and inputs, the two sides alternating.  Prints ONE JSON
+line (GPU box only; a missing GPU is an error).
+
+    python tools/bench_block.py [--points 100000] [--reps 20] [--warmup 5] [--inner 10] [--out FILE]
+
+(a) "operator": one residual site at the four S3DIS stage shapes (N = points, points / 4 + 1, ...; C = 48, 96, 192, 384), fp32 and
+    autocast(f16) (y and o in half), training mode, drop_prob 0.3.  Composite: compat.DropPath(0.3)(y), x + ., nn.LayerNorm, and under
+    autocast the `.half()` the next Linear would apply.  Fused: layers.drop_path_row_scale + pointops.residual_norm.  Forward, and
+    forward + backward (gradients arrive at both z and o; x, y, weight, bias receive theirs).
+(b) "blocks": four stand-in BasicLayers of depth 2 (standin.SwinTransformerBlock with DropPath(0.3), the installed BasicLayer /
+    WindowAttention / TransitionDown: the real attention) strung as the model strings them on the room scene, forward + backward, with
+    layers.patch_block_classes applied or not.  Under autocast only stage 0 is fused: TransitionDown's Linear hands the later stages
+    half features, and a half residual stream takes the original forward.
+
+Every figure: median over `reps` windows of `inner` iterations between two device events (the second synchronised), in ms per
+iteration; `spread` = max - min of the composite / unpatched side over its windows.  `bytes` = what the fused forward and backward must
+move, from the shapes (fused_bytes below); `achieved_bytes_per_s` = those bytes over the fused time - launch gaps and DropPath's rand
+included, so it is a call's rate, not a kernel's.  `faster_beyond_spread`: composite - fused > the composite's spread.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stratified_transformer_amd import compat, layers, pipeline, pointops as P, scene, standin  # noqa: E402
+
+DROP = 0.3
+
+
+def fused_bytes(n, c, half):
+    """bytes one site must move: forward reads x, y, s and writes z, o, stat; backward reads dO, dZ, z, stat, s and writes dx, dy
+    (gamma, beta and the parameter-gradient partials: at most 1024 * 2 * c floats, left out)"""
+    b = 2 if half else 4
+    fwd = n * (4 * c + b * c + 4 + 4 * c + b * c + 8)
+    bwd = n * (b * c + 4 * c + 4 * c + 8 + 4 + 4 * c + b * c)
+    return fwd, bwd
+
+
+def windows(sides, reps, warmup, inner):
+    """sides: name -> fn(); -> name -> list of ms per iteration, the sides alternating window by window"""
+    times = {s: [] for s in sides}
+    for it in range(warmup + reps):
+        for s, fn in sides.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            if it >= warmup:
+                times[s].append(e0.elapsed_time(e1) / inner)
+    return times
+
+
+def summary(times, base, new):
+    r = {base + "_ms": round(statistics.median(times[base]), 5), new + "_ms": round(statistics.median(times[new]), 5),
+         base + "_spread_ms": round(max(times[base]) - min(times[base]), 5), new + "_spread_ms": round(max(times[new]) - min(times[new]), 5)}
+    r["ratio"] = round(r[base + "_ms"] / r[new + "_ms"], 3)
+    r["faster_beyond_spread"] = bool(r[base + "_ms"] - r[new + "_ms"] > r[base + "_spread_ms"])
+    return r
+
+
+def operator_case(n, c, amp, a):
+    g = torch.Generator(device="cuda").manual_seed(c)
+    half = torch.float16 if amp else torch.float32
+    x = torch.randn(n, c, device="cuda", generator=g).requires_grad_(True)
+    y = torch.randn(n, c, device="cuda", generator=g).to(half).requires_grad_(True)
+    gz, go = torch.randn(n, c, device="cuda", generator=g), torch.randn(n, c, device="cuda", generator=g).to(half)
+    norm, dp = torch.nn.LayerNorm(c).cuda(), compat.DropPath(DROP).train()
+
+    def composite():
+        z = x + dp(y)
+        o = norm(z)
+        return z, (o.half() if amp else o)
+
+    def fused():
+        return P.residual_norm(x, y, layers.drop_path_row_scale(dp, y), norm.weight, norm.bias, norm.eps, half)
+
+    def with_backward(fn):
+        def run():
+            x.grad = y.grad = None
+            norm.zero_grad(set_to_none=True)
+            z, o = fn()
+            torch.autograd.backward([z, o], [gz, go])
+        return run
+
+    torch.manual_seed(1)
+    zc, oc = composite()
+    torch.manual_seed(1)
+    zf, of = fused()
+    row = {"n": n, "c": c, "max_abs_diff_z": float((zc - zf).abs().max()), "max_abs_diff_o": float((oc.float() - of.float()).abs().max())}
+    fwd_b, bwd_b = fused_bytes(n, c, amp)
+    with torch.no_grad():
+        row["fwd"] = summary(windows({"composite": composite, "fused": fused}, a.reps, a.warmup, a.inner), "composite", "fused")
+    row["fwd_bwd"] = summary(windows({"composite": with_backward(composite), "fused": with_backward(fused)}, a.reps, a.warmup, a.inner), "composite", "fused")
+    row["fwd"]["bytes"], row["fwd_bwd"]["bytes"] = fwd_b, fwd_b + bwd_b
+    for k in ("fwd", "fwd_bwd"):
+        row[k]["achieved_bytes_per_s"] = round(row[k]["bytes"] / (row[k]["fused_ms"] * 1e-3), 1)
+    return row
+
+
+def blocks_leg(a, amp):
+    cfg = pipeline.s3dis_config()
+    st = cfg.stages
+    xyz = torch.from_numpy(scene.make_room(a.points, 0)).cuda()
+    offset = torch.tensor([a.points], dtype=torch.int32, device="cuda")
+    torch.manual_seed(0)
+    net = torch.nn.ModuleList([standin.BasicLayer(cfg.downsample_scale, 2, s.channels, s.num_heads, s.window_size, s.quant_size, ratio=cfg.ratio, k=cfg.k,
+                                                  out_channels=st[i + 1].channels if i + 1 < len(st) else None) for i, s in enumerate(st)]).cuda().train()
+    with torch.no_grad():
+        for name, p in net.named_parameters():
+            if "relative_pos" in name:
+                p.normal_(0.0, 0.02)
+    for layer in net:
+        for blk in layer.blocks:
+            blk.drop_path = compat.DropPath(DROP)
+    net.train()
+    feats0 = torch.randn(a.points, st[0].channels, device="cuda")
+    sites = [(int(n), s.channels) for n, s in zip(_stage_rows(a.points, cfg), st)]
+
+    def step():
+        P.clear_caches()
+        layers.forget_clouds()
+        net.zero_grad(set_to_none=True)
+        f, x, o = feats0.clone().requires_grad_(True), xyz, offset
+        loss = None
+        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+            for layer in net:
+                f_out, _, _, f, x, o = layer(f, x, o)
+                term = f_out.float().square().mean()
+                loss = term if loss is None else loss + term
+        loss.backward()
+
+    def patched():
+        layers.patch_block_classes(standin.SwinTransformerBlock)
+        step()
+
+    def unpatched():
+        if (standin.SwinTransformerBlock, "forward") in layers._ORIGINAL:
+            standin.SwinTransformerBlock.forward = layers._ORIGINAL.pop((standin.SwinTransformerBlock, "forward"))
+        step()
+
+    try:
+        layers.patch_classes(standin.BasicLayer, standin.WindowAttention, standin.TransitionDown)
+        r = summary(windows({"unpatched": unpatched, "patched": patched}, a.reps, a.warmup, 1), "unpatched", "patched")
+    finally:
+        layers.uninstall_fast_layers()
+    # Under autocast TransitionDown's Linear hands the later stages HALF features: their residual stream is half, which the fused
+    # forward leaves to the original one - only stage 0 is fused then.
+    fused_sites = sites[:1] if amp else sites
+    # per block two sites (attention branch, MLP branch) and, for the first block of a layer, its norm1 alone (x read, o written; twice: backward)
+    r["bytes"] = sum(2 * 2 * sum(fused_bytes(n, c, amp)) + n * c * (4 + (2 if amp else 4)) * 2 for n, c in fused_sites)
+    r["achieved_bytes_per_s_whole_step"] = round(r["bytes"] / (r["patched_ms"] * 1e-3), 1)
+    r["stage_rows"], r["fused_stages"] = [n for n, _ in sites], len(fused_sites)
+    return r
+
+
+def _stage_rows(points, cfg):
+    from stratified_transformer_amd import index_build
+    rows, off = [], [points]
+    for _ in cfg.stages:
+        rows.append(off[-1])
+        off = index_build.transition_down_offset(off, cfg.ratio)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=100000)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--skip-blocks", action="store_true")
+    ap.add_argument("--trace-loop", type=int, default=0, help="only loop the fused site this many times per stage shape (for a kernel trace)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.reps < 5:
+        raise SystemExit("bench_block: at least five repeats a side")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_block: needs the GPU (no CPU timing is meaningful)")
+    if a.trace_loop:
+        # for a run of its own under `rocprofv3 --kernel-trace --stats -- python tools/bench_block.py --trace-loop 160`: the fused site only
+        for n, c in zip(_stage_rows(a.points, pipeline.s3dis_config()), (48, 96, 192, 384)):
+            x, y = (torch.randn(n, c, device="cuda", requires_grad=True) for _ in range(2))
+            gz, go = torch.randn(n, c, device="cuda"), torch.randn(n, c, device="cuda")
+            norm, dp = torch.nn.LayerNorm(c).cuda(), compat.DropPath(DROP).train()
+            for _ in range(a.trace_loop):
+                z, o = P.residual_norm(x, y, layers.drop_path_row_scale(dp, y), norm.weight, norm.bias, norm.eps)
+                torch.autograd.backward([z, o], [gz, go])
+            torch.cuda.synchronize()
+        return
+    result = {"tool": "bench_block", "device": torch.cuda.get_device_name(0), "points": a.points, "drop_prob": DROP, "reps": a.reps, "warmup": a.warmup,
+              "inner": a.inner, "operator": {}, "blocks": {}}
+    rows = _stage_rows(a.points, pipeline.s3dis_config())
+    for mode, amp in (("fp32", False), ("autocast_f16", True)):
+        result["operator"][mode] = [operator_case(n, c, amp, a) for n, c in zip(rows, (48, 96, 192, 384))]
+        if not a.skip_blocks:
+            result["blocks"][mode] = blocks_leg(a, amp)
+    stage0 = [result["operator"][m][0]["fwd_bwd"]["faster_beyond_spread"] for m in ("fp32", "autocast_f16")]
+    result["stage0_fwd_bwd_faster_beyond_spread"] = bool(all(stage0))
+    line = json.dumps(result)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
