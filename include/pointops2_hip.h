@@ -472,6 +472,39 @@ void residual_norm_backward_launcher(int n, int c, int y_type, int o_type, const
                                      const float *stat, const float *s, const float *gamma, float *grad_x, void *grad_y, float *partials,
                                      int partial_rows, float *grad_gamma, float *grad_beta);
 
+/* ---- the loss tail of a segmentation training step in one pass: cross-entropy on the class logits, L1 on the shift head, their
+ * weighted sum and the per-class IoU counts (tool/train.py:336-362, train_backup.py:403, util/common_util.py:180-185) ----
+ * Row n is VALID when 0 <= target[n] < c and target[n] != ignore_index; any other label is never used as an index.
+ *   forward:  m_n = max_ch x[n,ch], ls_n = log(sum_ch exp(x[n,ch] - m_n)), stat[n] = (m_n, ls_n) (the row's log-sum-exp is m_n + ls_n:
+ *             kept apart, a softmax rebuilt from their fp32 sum would lose digits on rows of large logits);
+ *             logp[n,ch] = (x[n,ch] - m_n) - ls_n; loss_n = -logp[n,t] with t = target[n], or for smooth_eps > 0
+ *             -((1 - eps) * logp[n,t] + eps / (c - 1) * sum_{ch != t} logp[n,ch]); ce = sum over the valid rows of loss_n / their number
+ *             (none: NaN, as torch); l1 = sum |shift_pred - shift| / (3 n) over ALL rows (shift_pred and shift both NULL: 0);
+ *             total = ce + offset_weight * l1 (no shift pair: ce); losses = (ce, l1, total), fully written (n = 0: ce and total NaN).
+ *             With pred_n = the smallest ch at which x[n,:] is largest (the first NaN if there is one), over the valid rows:
+ *             counts[0,k] += #(pred == t == k), counts[1,k] += #(pred == k) + #(t == k) - #(pred == t == k), counts[2,k] += #(t == k);
+ *             rows[0] += valid rows, rows[1] += rows whose label is neither valid nor ignore_index.  counts [3,c] and rows [2] ACCUMULATE
+ *             by integer atomics (exact, order-free): zero-fill them.
+ *   backward: a = g[0] + g[2], b = g[1] + offset_weight * g[2] with g = grad_losses [3] and n_valid = rows[0], both read on the device;
+ *             grad_logits[n,ch] = (a / n_valid) * (exp((x[n,ch] - m_n) - ls_n) - w[n,ch]) on valid rows (w: 1 at t; smoothed: 1 - eps at
+ *             t, eps / (c - 1) elsewhere) and 0 on every other row; grad_shift_pred[n,j] = (b / (3 n)) * sign(shift_pred - shift),
+ *             sign(0) = 0.  Both are FULLY WRITTEN; either may be NULL (not wanted).
+ * logits / grad_logits [n,c] have logits_type and shift_pred / grad_shift_pred [n,3] have shift_type, each POINTOPS2_ROWS_F32, _F16 or
+ * _BF16, widened exactly, arithmetic in fp32 without fused operations, one rounding to the row type (a loss scale in grad_losses is
+ * applied before it).  target [n] int64, shift [n,3] and stat [n,2] fp32.  The two float sums take no float atomics: workgroup b
+ * writes its sums as doubles to partials[b] (partials: double [partial_rows, 2], a workspace, no zero-fill; the forward's grid is at
+ * most partial_rows workgroups of 256 rows - 128 for c > 32) and a second kernel adds them in a fixed order: bitwise reproducible on
+ * one device.  1 <= c <= 64, 0 <= smooth_eps < 1 (> 0 needs c >= 2), the row types, and shift_pred and shift given together are
+ * checked: otherwise an error is recorded and nothing is launched.  n = 0 launches no row kernel; offsets are 64-bit.  A 16-byte aligned
+ * logits (and grad_logits) is read 16 bytes a lane, anything else one element a lane: same results.  A NaN or Inf in a row stays in
+ * that row's stat and gradient and reaches only the scalar sums. */
+void seg_loss_forward_launcher(int n, int c, int logits_type, int shift_type, const void *logits, const long long *target, const void *shift_pred,
+                               const float *shift, long long ignore_index, float smooth_eps, float offset_weight, float *stat, double *partials,
+                               int partial_rows, long long *counts, long long *rows, float *losses);
+void seg_loss_backward_launcher(int n, int c, int logits_type, int shift_type, const void *logits, const long long *target, const float *stat,
+                                const void *shift_pred, const float *shift, const float *grad_losses, const long long *rows,
+                                long long ignore_index, float smooth_eps, float offset_weight, void *grad_logits, void *grad_shift_pred);
+
 /* ---- DBSCAN: the clustering behind the model (util/train_utils.py:549-566 runs sklearn.cluster.DBSCAN per predicted class) ----
  * Neighbours: same group and d2 <= eps2[group], in fp32 with d2 = ((dx*dx) + (dy*dy)) + (dz*dz), dx = xi - xj, no fused operation; a
  * point is its own neighbour.  Core: at least min_samples[group] neighbours.  Clusters: the connected components of the core points,

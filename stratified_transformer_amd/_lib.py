@@ -15,6 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 _lib = None
 
 I, U, P, Z, F, D = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
+Q = ctypes.c_longlong
 
 
 class LaunchOpts(ctypes.Structure):
@@ -101,6 +102,8 @@ SIGNATURES = {
     "grouped_max_backward_launcher": [I, I, I, I, I, P, P, P, P, P],
     "residual_norm_forward_launcher": [I, I, I, I, P, P, P, P, P, F, P, P, P],
     "residual_norm_backward_launcher": [I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, P],
+    "seg_loss_forward_launcher": [I, I, I, I, P, P, P, P, Q, F, F, P, P, I, P, P, P],
+    "seg_loss_backward_launcher": [I, I, I, I, P, P, P, P, P, P, P, Q, F, F, P, P],
     "pointops2_dbscan_keys_launcher": [I, I, P, P, D, D, D, D, I, I, I, P],
     "pointops2_dbscan_prepare_launcher": [I, I, I, I, I, P, P, P, P, P, P],
     "pointops2_dbscan_core_launcher": [I, I, P, P, P, P, P, P, P, P],

@@ -1102,6 +1102,113 @@ def residual_norm(x, y, row_scale, weight, bias, eps=1e-5, out_dtype=None):
     return (x, out) if y is None else out
 
 
+# ---------------------------------------------------------------------------------------------
+# the loss tail of a training step: cross-entropy, L1 shift, weighted sum, IoU counts (csrc/seg_loss.hip)
+# ---------------------------------------------------------------------------------------------
+class SegmentationLoss(Function):
+    """(losses [3] = (ce, l1, total), counts [3, C], rows [2]) in one pass over the logits plus the small kernel that adds the
+    per-workgroup sums (no float atomics: bitwise reproducible); both gradients in one pass, the incoming gradient and the valid-row
+    count read on the device.  counts and rows are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, target, shift_pred, shift, ignore_index, offset_weight, smooth_eps):
+        n, c = logits.shape
+        ints = _zeros((3 * c + 2,), logits, torch.int64)      # counts and rows accumulate by integer atomics: one fill for both
+        counts, rows = ints.split((3 * c, 2))
+        counts = counts.view(3, c)
+        losses = torch.empty((3,), dtype=torch.float32, device=logits.device)
+        stat = torch.empty((n, 2), dtype=torch.float32, device=logits.device)
+        partials = torch.empty((pointops_cuda.SEG_LOSS_PARTIAL_ROWS, 2), dtype=torch.float64, device=logits.device)  # 16 KB, no fill
+        pointops_cuda.seg_loss_forward(n, c, logits, target, shift_pred, shift, ignore_index, smooth_eps, offset_weight, stat, partials, counts,
+                                       rows, losses)
+        if n == 0 and shift_pred is not None:
+            losses[1] = float("nan")  # the mean of nothing, as F.l1_loss: an empty tensor has no address by which the launcher could see the pair
+        ctx.save_for_backward(logits, target, shift_pred, shift, stat, rows)
+        ctx.args = (ignore_index, smooth_eps, offset_weight)
+        ctx.mark_non_differentiable(counts, rows)
+        ctx.set_materialize_grads(False)
+        return losses, counts, rows
+
+    @staticmethod
+    def backward(ctx, grad_losses, _grad_counts, _grad_rows):
+        logits, target, shift_pred, shift, stat, rows = ctx.saved_tensors
+        if grad_losses is None:
+            return (None,) * 7
+        n, c = logits.shape
+        ignore_index, smooth_eps, offset_weight = ctx.args
+        grad_logits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        grad_shift = torch.empty_like(shift_pred) if shift_pred is not None and ctx.needs_input_grad[2] else None
+        if n > 0 and (grad_logits is not None or grad_shift is not None):
+            pointops_cuda.seg_loss_backward(n, c, logits, target, stat, shift_pred, shift, grad_losses.float().contiguous(), rows, ignore_index,
+                                            smooth_eps, offset_weight, grad_logits, grad_shift)
+        return (grad_logits, None, grad_shift, None, None, None, None)
+
+
+class SegLossResult:
+    """What segmentation_loss returns.  losses [3] f32 = (ce, shift, total); ce, shift and total are its 0-dim views, made when asked for
+    (a step that takes only `total` pays for one); counts [3, C] int64 = (intersection, union, target) per class over the valid rows;
+    rows [2] int64 = (valid rows, rows with an out-of-range label)."""
+    __slots__ = ("losses", "counts", "rows")
+
+    def __init__(self, losses, counts, rows):
+        self.losses, self.counts, self.rows = losses, counts, rows
+
+    ce = property(lambda self: self.losses[0])
+    shift = property(lambda self: self.losses[1])
+    total = property(lambda self: self.losses[2])
+
+    def __repr__(self):
+        return f"SegLossResult(losses={self.losses!r}, counts={self.counts!r}, rows={self.rows!r})"
+
+
+def segmentation_loss(logits, target, shift_pred=None, shift=None, *, ignore_index=-100, offset_weight=1.0, smooth_eps=0.0):
+    """The loss tail of a training step (tool/train.py:336-362) in one HIP pass over the logits and one backward pass (csrc/seg_loss.hip):
+    ce = F.cross_entropy(logits, target, ignore_index=ignore_index) - or, with smooth_eps > 0, util/common_util.py's smooth_loss over the
+    valid rows -, shift = F.l1_loss(shift_pred, shift), total = ce + offset_weight * shift, and intersectionAndUnionGPU's counts of the
+    argmax -> SegLossResult.  logits [n, C] f32, f16 or bf16 (under autocast hand over what the head yields: the kernel widens);
+    target [n] int64; shift_pred [n, 3] f32, f16 or bf16 with shift [n, 3] f32, or neither (shift = 0, total = ce).  A row counts
+    when 0 <= target < C and target != ignore_index; another label that is not ignore_index is skipped as well and counted in
+    rows[1] (torch traps it).  `result.total.backward()` and `scaler.scale(result.total).backward()` give logits and shift_pred
+    their gradients; `result.losses.tolist()` is the one read-back of a step.  1 <= C <= 64; 0 <= smooth_eps < 1."""
+    tensors = [("logits", logits), ("target", target), ("shift_pred", shift_pred), ("shift", shift)]
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"segmentation_loss: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+    for name, t in tensors[1:]:
+        if t is not None and t.device != logits.device:
+            raise RuntimeError(f"segmentation_loss: {name}: is on {t.device}, logits on {logits.device}")
+    if logits.dim() != 2:
+        raise ValueError(f"segmentation_loss: logits: must be [n, C], got {tuple(logits.shape)}")
+    if logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"segmentation_loss: logits: must be f32, f16 or bf16, got {logits.dtype}")
+    n, c = logits.shape
+    if not 1 <= c <= pointops_cuda.SEG_LOSS_MAX_C:
+        raise ValueError(f"segmentation_loss: logits: C must be in [1, {pointops_cuda.SEG_LOSS_MAX_C}], got {tuple(logits.shape)}")
+    if target.dtype != torch.int64:
+        raise TypeError(f"segmentation_loss: target: must be int64, got {target.dtype}")
+    if tuple(target.shape) != (n,):
+        raise ValueError(f"segmentation_loss: target: must be [{n}], got {tuple(target.shape)}")
+    if (shift_pred is None) != (shift is None):
+        raise ValueError(f"segmentation_loss: {'shift_pred' if shift is None else 'shift'}: given without {'shift' if shift is None else 'shift_pred'}")
+    if shift_pred is not None:
+        if shift_pred.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"segmentation_loss: shift_pred: must be f32, f16 or bf16, got {shift_pred.dtype}")
+        if shift.dtype != torch.float32:
+            raise TypeError(f"segmentation_loss: shift: must be f32, got {shift.dtype}")
+        for name, t in tensors[2:]:
+            if tuple(t.shape) != (n, 3):
+                raise ValueError(f"segmentation_loss: {name}: must be [{n}, 3], got {tuple(t.shape)}")
+    for name, t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"segmentation_loss: {name}: must be contiguous")
+    smooth_eps = float(smooth_eps)
+    if not 0.0 <= smooth_eps < 1.0:
+        raise ValueError(f"segmentation_loss: smooth_eps: must be in [0, 1), got {smooth_eps}")
+    if smooth_eps > 0.0 and c < 2:
+        raise ValueError(f"segmentation_loss: smooth_eps: {smooth_eps} > 0 needs C >= 2, got C = {c}")
+    return SegLossResult(*SegmentationLoss.apply(logits, target, shift_pred, shift, int(ignore_index), float(offset_weight), smooth_eps))
+
+
 class Subtraction(Function):
     @staticmethod
     def forward(ctx, input1, input2, idx):

@@ -190,6 +190,66 @@ def residual_norm_backward(n, c, grad_o, grad_z, z, stat, row_scale, weight, gra
           ptr(grad_x), ptr(grad_y), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), opts=opts)
 
 
+# csrc/seg_loss.hip (no counterpart in the reference's launcher set: the loss tail of tool/train.py - cross-entropy, L1 shift, IoU counts)
+SEG_LOSS_MAX_C = 64
+SEG_LOSS_PARTIAL_ROWS = 1024  # most workgroups of the forward: one row of `partials` each
+
+
+def _seg_loss_sizes(n, c, smooth_eps, shift_pred, shift):
+    n, c, smooth_eps = int(n), int(c), float(smooth_eps)
+    if n < 0:
+        raise ValueError(f"n: expected a row count >= 0, got {n}")
+    if not 1 <= c <= SEG_LOSS_MAX_C:
+        raise ValueError(f"c: expected 1 <= c <= {SEG_LOSS_MAX_C}, got {c}")
+    if not 0.0 <= smooth_eps < 1.0 or (smooth_eps > 0.0 and c < 2):
+        raise ValueError(f"smooth_eps: expected 0 <= smooth_eps < 1 (and c >= 2 when > 0), got {smooth_eps} with c = {c}")
+    if (shift_pred is None) != (shift is None):
+        raise ValueError(f"{'shift' if shift is None else 'shift_pred'}: shift_pred and shift are given together or not at all")
+    return n, c, smooth_eps
+
+
+def _seg_loss_inputs(n, c, logits, target, shift_pred, shift):
+    lt = _row_type(logits, "logits")
+    _chk((logits, logits.dtype, "logits"), (target, torch.int64, "target"))
+    _shaped(logits, (n, c), "logits"), _shaped(target, (n,), "target")
+    st = _row_type(shift_pred, "shift_pred") if shift_pred is not None else _lib.ROW_TYPES[F32]
+    _opt(shift_pred, None if shift_pred is None else shift_pred.dtype, (n, 3), "shift_pred")
+    _opt(shift, F32, (n, 3), "shift")
+    return lt, st
+
+
+def seg_loss_forward(n, c, logits, target, shift_pred, shift, ignore_index, smooth_eps, offset_weight, stat, partials, counts, rows, losses, *,
+                     opts=None):
+    """losses [3] f32 = (ce, l1, total), stat [n,2] f32 = (row maximum, log of the row's sum of exponentials), counts [3,c] and rows [2]
+    int64 (ACCUMULATED: zero-fill them) <- logits [n,c] f32 / f16 / bf16, target [n] int64, shift_pred [n,3] f32 / f16 / bf16 with
+    shift [n,3] f32, or both None; partials: a [1 <= rows <= 1024, 2] float64 workspace"""
+    n, c, smooth_eps = _seg_loss_sizes(n, c, smooth_eps, shift_pred, shift)
+    lt, st = _seg_loss_inputs(n, c, logits, target, shift_pred, shift)
+    _chk((stat, F32, "stat"), (partials, torch.float64, "partials"), (counts, torch.int64, "counts"), (rows, torch.int64, "rows"), (losses, F32, "losses"))
+    _shaped(stat, (n, 2), "stat"), _shaped(counts, (3, c), "counts"), _shaped(rows, (2,), "rows"), _shaped(losses, (3,), "losses")
+    prows = int(partials.shape[0]) if partials.dim() == 2 else 0
+    if not 1 <= prows <= SEG_LOSS_PARTIAL_ROWS or tuple(partials.shape[1:]) != (2,):
+        raise ValueError(f"partials: expected shape [1 <= rows <= {SEG_LOSS_PARTIAL_ROWS}, 2], got {list(partials.shape)}")
+    _call("seg_loss_forward_launcher", logits, n, c, lt, st, ptr(logits), ptr(target), ptr(shift_pred), ptr(shift), int(ignore_index), smooth_eps,
+          float(offset_weight), ptr(stat), ptr(partials), prows, ptr(counts), ptr(rows), ptr(losses), opts=opts)
+
+
+def seg_loss_backward(n, c, logits, target, stat, shift_pred, shift, grad_losses, rows, ignore_index, smooth_eps, offset_weight, grad_logits,
+                      grad_shift_pred, *, opts=None):
+    """grad_logits [n,c] (logits' dtype) and grad_shift_pred [n,3] (shift_pred's dtype), each fully written or None (not wanted) <-
+    grad_losses [3] f32 and the forward's rows [2] int64, both read on the device, and logits, target, stat, shift_pred, shift"""
+    n, c, smooth_eps = _seg_loss_sizes(n, c, smooth_eps, shift_pred, shift)
+    lt, st = _seg_loss_inputs(n, c, logits, target, shift_pred, shift)
+    _chk((stat, F32, "stat"), (grad_losses, F32, "grad_losses"), (rows, torch.int64, "rows"))
+    _shaped(stat, (n, 2), "stat"), _shaped(grad_losses, (3,), "grad_losses"), _shaped(rows, (2,), "rows")
+    _opt(grad_logits, logits.dtype, (n, c), "grad_logits")
+    if grad_shift_pred is not None and shift_pred is None:
+        raise ValueError("grad_shift_pred: given without shift_pred")
+    _opt(grad_shift_pred, None if shift_pred is None else shift_pred.dtype, (n, 3), "grad_shift_pred")
+    _call("seg_loss_backward_launcher", logits, n, c, lt, st, ptr(logits), ptr(target), ptr(stat), ptr(shift_pred), ptr(shift), ptr(grad_losses),
+          ptr(rows), int(ignore_index), smooth_eps, float(offset_weight), ptr(grad_logits), ptr(grad_shift_pred), opts=opts)
+
+
 # attention/attention_cuda.cpp
 def attention_step1_forward_cuda(N, M, h, C, q, k, index0, index1, attn, *, opts=None):
     _chk((q, F32, "q"), (k, F32, "k"), (index0, I32, "index0"), (index1, I32, "index1"), (attn, F32, "attn"))
