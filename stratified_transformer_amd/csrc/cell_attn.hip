@@ -163,6 +163,27 @@ __device__ __forceinline__ LaneCtx<TT, PK> make_lane_ctx(const TT *lds, int h, i
 // Query ids: 64 at a time, one per lane; a query's id is then a v_readlane away (a scalar: the q row address is uniform).
 // A slot past the chunk's end reads key 0 from the bounds-checked list: its row is replaced by zeros, not left to a weight of 0 to
 // cancel (0 * inf = NaN: a non-finite row 0 would reach every cell with a partial last pass).
+//
+// Store order of the query loops: loads, stores and atomics share one counter (vmcnt) that retires in issue order, and
+// the number of stores a wave issues depends on its lanes' paths (c == 0 / p == 0, nvalid), so a wait for a prefetched operand also
+// covers every store issued before that wait.  A query's results are therefore held for one iteration and stored at the top of the
+// next one, BEHIND the requests for the query after it: the one drain per iteration then covers loads and a store that were issued a
+// whole iteration earlier.  The last query's results leave after the loop.  That drain is written out at the top of the body
+// (wait_vmem: the wait this query's operands need anyway), so that no path into the loop's head - the prologue, a peeled first
+// iteration - leaves a pending load that the compiler would have to wait for inside the body, by a count that includes this
+// iteration's own requests.
+// (the empty asm keeps the requests issued before the wait before it: the builtin alone does not order loads, and the compiler sinks them)
+__device__ __forceinline__ void wait_vmem() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // s_waitcnt vmcnt(0)
+}
+// the next 64 query ids, waited for where they are requested (once per 64 queries) and not at the loop's head
+__device__ __forceinline__ int next_query_ids(rsrc_t qid, int off) {
+    const int ids = (int)bload_u32(qid, off);
+    wait_vmem();
+    return ids;
+}
+
 template <int NPA, typename RT, typename T, bool PK>
 __device__ __forceinline__ void load_key_rows(const LaneCtx<T, PK> &x, const CellBufs &cb, const RT *__restrict__ rows, int j0, int nvalid,
                                               float4 (&r4)[NPA]) {
@@ -189,17 +210,23 @@ __device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T, PK> &x, const 
     float4 q4_nx = x.q_row4(q, i_nx);
     unsigned w_nx[NPA];
     bload_words<NPA>(cb.rel, (j0 + p * NPA) * 4, w_nx);
+    float lg_pv[NPA];  // single: the weights of query il-1
+#pragma unroll
+    for (int t = 0; t < NPA; t++) lg_pv[t] = 0.f;
+#pragma unroll 1  // (and no peeling of query 0)
     for (int il = 0; il < ct.nq; il++) {
+        wait_vmem();  // this query's operands
         const int i = i_nx;
         const float4 q4 = q4_nx;
         unsigned w[NPA];
 #pragma unroll
         for (int t = 0; t < NPA; t++) w[t] = w_nx[t];
         const int roff = (il * ct.nk + j0 + p * NPA) * 4;
-        if (((il + 1) & 63) == 0) ids = (int)bload_u32(cb.qid, (il + 1 + x.lane) * 4);
+        if (((il + 1) & 63) == 0) ids = next_query_ids(cb.qid, (il + 1 + x.lane) * 4);
         i_nx = __builtin_amdgcn_readlane(ids, (il + 1) & 63);  // (past the end: query 0, never used)
         q4_nx = x.q_row4(q, i_nx);
         bload_words<NPA>(cb.rel, roff + ct.nk * 4, w_nx);
+        if (single && il && c == 0) bstore_floats<NPA>(rs_p, roff - ct.nk * 4, lg_pv, nvalid);
         float lg[NPA];
         float mx = -INFINITY;
         RowOff ro = row_off(w[0], x.L, c);
@@ -230,8 +257,7 @@ __device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T, PK> &x, const 
             }
             const float inv = 1.0f / slots_sum16(sum);
 #pragma unroll
-            for (int t = 0; t < NPA; t++) lg[t] *= inv;
-            if (c == 0) bstore_floats<NPA>(rs_p, roff, lg, nvalid);
+            for (int t = 0; t < NPA; t++) lg_pv[t] = lg[t] * inv;
         } else {
             float *st = ml + ((size_t)i * x.h + x.head) * 2;
             const float m_old = ch ? st[0] : -INFINITY, l_old = ch ? st[1] : 0.f;
@@ -247,6 +273,7 @@ __device__ __forceinline__ void fwd_sweep_logits(const LaneCtx<T, PK> &x, const 
             }
         }
     }
+    if (single && ct.nq > 0 && c == 0) bstore_floats<NPA>(rs_p, ((ct.nq - 1) * ct.nk + j0 + p * NPA) * 4, lg_pv, nvalid);
 }
 
 template <int NPA, int TS, typename RT, typename T, bool PK>
@@ -262,8 +289,16 @@ __device__ __forceinline__ void fwd_sweep_values(const LaneCtx<T, PK> &x, const 
     bload_words<NPA>(cb.rel, (j0 + p * NPA) * 4, w_nx);
     bload_floats<NPA>(rs_p, (j0 + p * NPA) * 4, a_nx);
     int ids = (int)bload_u32(cb.qid, x.lane * 4);
+    float4 tot_pv = make_float4(0.f, 0.f, 0.f, 0.f);  // the sums of query i_pv = il-1
+    int i_pv = 0;
+    auto store_out = [&](int i, float4 tot) {
+        float *o = out + (size_t)i * x.C + x.hoff;
+        stg4(o, ch ? add4(tot, ldg4(o)) : tot);
+    };
+#pragma unroll 1  // (and no peeling of query 0)
     for (int il = 0; il < ct.nq; il++) {
-        if (il && (il & 63) == 0) ids = (int)bload_u32(cb.qid, (il + x.lane) * 4);
+        wait_vmem();  // this query's operands
+        if (il && (il & 63) == 0) ids = next_query_ids(cb.qid, (il + x.lane) * 4);
         const int i = __builtin_amdgcn_readlane(ids, il & 63);
         const int roff = (il * ct.nk + j0 + p * NPA) * 4;
         unsigned w[NPA];
@@ -275,6 +310,7 @@ __device__ __forceinline__ void fwd_sweep_values(const LaneCtx<T, PK> &x, const 
         }
         bload_words<NPA>(cb.rel, roff + ct.nk * 4, w_nx);
         bload_floats<NPA>(rs_p, roff + ct.nk * 4, a_nx);
+        if (il && p == 0) store_out(i_pv, tot_pv);
         if (!single) {
             const float *st = ml + ((size_t)i * x.h + x.head) * 2;
             const float m = st[0], inv = 1.0f / st[1];
@@ -293,12 +329,10 @@ __device__ __forceinline__ void fwd_sweep_values(const LaneCtx<T, PK> &x, const 
             rv = rv1;
             __builtin_amdgcn_sched_barrier(0);
         }
-        const float4 tot = slots_sum16_4(acc);
-        if (p == 0) {
-            float *o = out + (size_t)i * x.C + x.hoff;
-            stg4(o, ch ? add4(tot, ldg4(o)) : tot);
-        }
+        tot_pv = slots_sum16_4(acc);
+        i_pv = i;
     }
+    if (ct.nq > 0 && p == 0) store_out(i_pv, tot_pv);
 }
 
 template <int NP, int LCAP, typename RT, typename T, bool PK>
@@ -341,23 +375,31 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
 // ------------------------------------------------------------------------------------------------
 // backward, sweeps A and B
 // ------------------------------------------------------------------------------------------------
-// adds the key-side accumulators of pass t (lane (p, c): floats 4c..4c+3 of the key j0 + p * NPA + t) to grad[key, head, :]:
-// through a wave-private LDS tile, so that one atomic instruction covers four whole 64-byte head rows
+// adds the key-side accumulators of a chunk (lane (p, c): floats 4c..4c+3 of the keys j0 + p * NPA + t, t < NPA) to grad[key, head, :],
+// pass by pass through a wave-private LDS tile, so that one atomic instruction covers four whole 64-byte head rows.  The key ids of all
+// 4 * NPA atomics (slot s = (lane >> 4) + 4 kk of pass t: key j0 + s * NPA + t - the NPA keys of a slot are consecutive dwords) are
+// requested together before the first pass: an id loaded where it is used costs a memory round trip per atomic, and from the second
+// one on that wait also covers the atomic before it.
 template <int NPA, typename T, bool PK>
-__device__ __forceinline__ void flush_key_pass(float *scr, float4 acc, rsrc_t rs_key, int j0, int t, int nkc, float *__restrict__ grad,
-                                               const LaneCtx<T, PK> &x) {
-    *reinterpret_cast<float4 *>(scr + x.p * 16 + 4 * x.c) = acc;
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
+__device__ __forceinline__ void flush_key_grads(float *scr, const float4 (&acc)[NPA], rsrc_t rs_key, int j0, int nkc, float *__restrict__ grad,
+                                                const LaneCtx<T, PK> &x) {
+    unsigned keys[4][NPA];
 #pragma unroll
-    for (int kk = 0; kk < 4; kk++) {
-        const int s = (x.lane >> 4) + 4 * kk;
-        const int jl = s * NPA + t;
-        const int key = (int)bload_u32(rs_key, (j0 + jl) * 4);
-        if (jl < nkc) unsafeAtomicAdd(grad + (size_t)key * x.rs() + x.head * 16 + (x.lane & 15), scr[s * 16 + (x.lane & 15)]);
+    for (int kk = 0; kk < 4; kk++) bload_words<NPA>(rs_key, (j0 + ((x.lane >> 4) + 4 * kk) * NPA) * 4, keys[kk]);  // (past the end: key 0, unused)
+    wait_vmem();  // once, here: a wait placed by the compiler behind the first (conditional) atomic would count that atomic too
+#pragma unroll
+    for (int t = 0; t < NPA; t++) {
+        *reinterpret_cast<float4 *>(scr + x.p * 16 + 4 * x.c) = acc[t];
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) {
+            const int s = (x.lane >> 4) + 4 * kk;
+            if (s * NPA + t < nkc) unsafeAtomicAdd(grad + (size_t)keys[kk][t] * x.rs() + x.head * 16 + (x.lane & 15), scr[s * 16 + (x.lane & 15)]);
+        }
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
 }
 
 // sweep A: grad_attn = <go, v + Tv>, gs = p (grad_attn - <go, out>) stored, dV += p go
@@ -378,7 +420,12 @@ __device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T, PK> &x, const 
     int ids = (int)bload_u32(cb.qid, x.lane * 4);
     int i_nx = __builtin_amdgcn_readlane(ids, 0);
     float4 go_nx = ldg4(go + (size_t)i_nx * x.C + x.hoff), o_nx = ldg4(out + (size_t)i_nx * x.C + x.hoff);
+    float gs_pv[NPA];  // the logit gradients of query il-1
+#pragma unroll
+    for (int t = 0; t < NPA; t++) gs_pv[t] = 0.f;
+#pragma unroll 1  // (and no peeling of query 0)
     for (int il = 0; il < ct.nq; il++) {
+        wait_vmem();  // this query's operands
         const int roff = (il * ct.nk + j0 + p * NPA) * 4;
         const float4 go4 = go_nx, o4 = o_nx;
         unsigned w[NPA];
@@ -388,29 +435,28 @@ __device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T, PK> &x, const 
             w[t] = w_nx[t];
             a[t] = t < nvalid ? a_nx[t] : 0.f;
         }
-        if (((il + 1) & 63) == 0) ids = (int)bload_u32(cb.qid, (il + 1 + x.lane) * 4);
+        if (((il + 1) & 63) == 0) ids = next_query_ids(cb.qid, (il + 1 + x.lane) * 4);
         i_nx = __builtin_amdgcn_readlane(ids, (il + 1) & 63);
         go_nx = ldg4(go + (size_t)i_nx * x.C + x.hoff);
         o_nx = ldg4(out + (size_t)i_nx * x.C + x.hoff);
         bload_words<NPA>(cb.rel, roff + ct.nk * 4, w_nx);
         bload_floats<NPA>(rs_p, roff + ct.nk * 4, a_nx);
+        if (il && c == 0) bstore_floats<NPA>(rs_g, roff - ct.nk * 4, gs_pv, nvalid);
         const float delta = quad_sum(pdot4(go4, o4));  // = sum over the row of p * grad_attn
-        float gs[NPA];
         Rows3 rv = rows_at<2 * TS, T>(x.lds, row_off(w[0], x.L, c));
 #pragma unroll
         for (int t = 0; t < NPA; t++) {
             Rows3 rv1 = rv;
             if (t + 1 < NPA) rv1 = rows_at<2 * TS, T>(x.lds, row_off(w[t + 1], x.L, c));
             const float ga = quad_sum(pdot4(go4, padd4(rsum(rv), v4[t])));
-            gs[t] = a[t] * (ga - delta);
+            gs_pv[t] = a[t] * (ga - delta);
             dv4[t] = pfma4(a[t], go4, dv4[t]);
             rv = rv1;
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (c == 0) bstore_floats<NPA>(rs_g, roff, gs, nvalid);
     }
-#pragma unroll
-    for (int t = 0; t < NPA; t++) flush_key_pass<NPA, T, PK>(scr, dv4[t], cb.key, j0, t, nkc, grad_v, x);
+    if (ct.nq > 0 && c == 0) bstore_floats<NPA>(rs_g, ((ct.nq - 1) * ct.nk + j0 + p * NPA) * 4, gs_pv, nvalid);
+    flush_key_grads<NPA, T, PK>(scr, dv4, cb.key, j0, nkc, grad_v, x);
 }
 
 // sweep B: dQ = sum gs (k + Tq), dK += gs (q + Tk)
@@ -431,7 +477,15 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T, PK> &x, const Ce
     int ids = (int)bload_u32(cb.qid, x.lane * 4);
     int i_nx = __builtin_amdgcn_readlane(ids, 0);
     float4 q_nx = x.q_row4(q, i_nx);
+    float4 tot_pv = make_float4(0.f, 0.f, 0.f, 0.f);  // dQ of query i_pv = il-1
+    int i_pv = 0;
+    auto store_dq = [&](int i, float4 tot) {
+        float *o = grad_q + (size_t)i * x.rs() + x.hoff;
+        stg4(o, ch ? add4(tot, ldg4(o)) : tot);
+    };
+#pragma unroll 1  // (and no peeling of query 0)
     for (int il = 0; il < ct.nq; il++) {
+        wait_vmem();  // this query's operands
         const int i = i_nx;
         const int roff = (il * ct.nk + j0 + p * NPA) * 4;
         const float4 q4 = q_nx;
@@ -442,11 +496,12 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T, PK> &x, const Ce
             w[t] = w_nx[t];
             g[t] = t < nvalid ? g_nx[t] : 0.f;
         }
-        if (((il + 1) & 63) == 0) ids = (int)bload_u32(cb.qid, (il + 1 + x.lane) * 4);
+        if (((il + 1) & 63) == 0) ids = next_query_ids(cb.qid, (il + 1 + x.lane) * 4);
         i_nx = __builtin_amdgcn_readlane(ids, (il + 1) & 63);
         q_nx = x.q_row4(q, i_nx);
         bload_words<NPA>(cb.rel, roff + ct.nk * 4, w_nx);
         bload_floats<NPA>(rs_g, roff + ct.nk * 4, g_nx);
+        if (il && p == 0) store_dq(i_pv, tot_pv);
         float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
         RowOff ro = row_off(w[0], x.L, c);
         Rows3 rq = rows_at<0, T>(x.lds, ro), rk = rows_at<TS, T>(x.lds, ro);
@@ -466,13 +521,11 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T, PK> &x, const Ce
         }
         float4 tot = slots_sum16_4(dq);
         if constexpr (PK) tot = make_float4(tot.x * x.qscale, tot.y * x.qscale, tot.z * x.qscale, tot.w * x.qscale);  // dL/dq = scale * dL/dq'
-        if (p == 0) {
-            float *o = grad_q + (size_t)i * x.rs() + x.hoff;
-            stg4(o, ch ? add4(tot, ldg4(o)) : tot);
-        }
+        tot_pv = tot;
+        i_pv = i;
     }
-#pragma unroll
-    for (int t = 0; t < NPA; t++) flush_key_pass<NPA, T, PK>(scr, dk4[t], cb.key, j0, t, nkc, grad_k, x);
+    if (ct.nq > 0 && p == 0) store_dq(i_pv, tot_pv);
+    flush_key_grads<NPA, T, PK>(scr, dk4, cb.key, j0, nkc, grad_k, x);
 }
 
 template <int NP, int LCAP, typename RT, typename T, bool PK>

@@ -1,5 +1,6 @@
 """Load/wait token scan of the compiled kernels: for each kernel of a .hip file prints, per basic block, the
-sequence of global loads (L), stores (S), atomics (A) and `s_waitcnt vmcnt(n)` (wn).  A block that reads
+sequence of vector loads (L: global_load, buffer_load), stores (S: global_store, buffer_store), global atomics (A) and
+`s_waitcnt vmcnt(n)` (wn).  A block that reads
 `L w0 L w0` is a chain of serialized memory round trips; `L L L w2 w1 w0` is one round trip.
 
     python tools/isa_loads.py rpe.hip [kernel-substring ...]
@@ -27,8 +28,8 @@ def main():
         s = ln.strip()
         if re.match(r'^\.LBB\d+_\d+:', s): toks.append('|')
         elif s.startswith('global_load') or s.startswith('buffer_load'): toks.append('L')
-        elif s.startswith('global_store'): toks.append('S')
-        elif s.startswith('global_atomic'): toks.append('A')
+        elif s.startswith('global_store') or s.startswith('buffer_store'): toks.append('S')  # (the cell kernels store p / gs through buffer descriptors)
+        elif s.startswith('global_atomic'): toks.append('A')  # (global_atomic_add_f32: the dK / dV and table-gradient flushes)
         elif s.startswith('s_waitcnt'):
             v = re.search(r'vmcnt\((\d+)\)', s)
             if v: toks.append('w' + v.group(1))
