@@ -159,11 +159,7 @@ __global__ __launch_bounds__(256) void scatter_atomic_kernel(int N, int h, const
             for (int hh = 0; hh < h; hh++) {
                 const float g = w[(size_t)m * h + hh];
                 const float4 s4 = ldg4(src + (size_t)qi * C + hh * D + 4 * c);
-                float *d = dst + (size_t)j * C + hh * D + 4 * c;
-                atomicAdd(d + 0, g * s4.x);
-                atomicAdd(d + 1, g * s4.y);
-                atomicAdd(d + 2, g * s4.z);
-                atomicAdd(d + 3, g * s4.w);
+                atomic_add4(dst + (size_t)j * C + hh * D + 4 * c, scale4(g, s4));
             }
         }
     }
@@ -220,12 +216,13 @@ __global__ void step2_v1_bwd_kernel(int M, int h, int d, const float *go, const 
     ga[t] += sum;
 }
 
-template <typename F16, typename F32>
-static bool dispatch_d(int d, F16 f16, F32 f32) {
-    if (d == 16) { f16(); return true; }
-    if (d == 32) { f32(); return true; }
-    set_error("d != 16 and d != 32");
-    return false;
+void gather_accum_by_key(hipStream_t st, int d, int n_keys, int h, const int *csc_offsets, const int *csc_query, const int *csc_pair,
+                         const float *w, const float *src, float *out, const int *order) {
+    const dim3 grid(order ? ordered_grid(n_keys, 4) : div_up(n_keys, 4), div_up(h, 4));
+    if (d == 16)
+        hipLaunchKernelGGL((gather_accum_kernel<16, true>), grid, dim3(256), 0, st, n_keys, h, csc_offsets, csc_query, csc_pair, w, src, out, order);
+    else
+        hipLaunchKernelGGL((gather_accum_kernel<32, true>), grid, dim3(256), 0, st, n_keys, h, csc_offsets, csc_query, csc_pair, w, src, out, order);
 }
 
 }  // namespace p2
@@ -244,9 +241,11 @@ void attention_step1_forward_cuda_launcher_v2(int N, int M, int h, int C, const 
     const int *rord = ln.rows_in_order(N);
     const int blocks = rord ? ordered_grid(N, 4) : div_up(N, 4);
     const size_t lds = 4 * (size_t)C * sizeof(float);
-    dispatch_d(C / h,
-               [&] { hipLaunchKernelGGL(a1_fwd_kernel<16>, dim3(blocks, N < 20000 ? div_up(h, 4) : 1), dim3(256), lds, st, N, h, q, k, index0_offsets, index1, attn, rord); },
-               [&] { hipLaunchKernelGGL(a1_fwd_kernel<32>, dim3(blocks, N < 20000 ? div_up(h, 8) : 1), dim3(256), lds, st, N, h, q, k, index0_offsets, index1, attn, rord); });
+    dispatch_d(C / h, [&](auto dtag) {
+        constexpr int D = decltype(dtag)::value;  // (head groups of LPG = D / 4 heads over blockIdx.y on small clouds)
+        hipLaunchKernelGGL(a1_fwd_kernel<D>, dim3(blocks, N < 20000 ? div_up(h, D / 4) : 1), dim3(256), lds, st, N, h, q, k, index0_offsets, index1, attn, rord);
+        return true;
+    });
     check_launch();
 }
 
@@ -262,22 +261,20 @@ void attention_step1_backward_cuda_launcher_v2(int N, int M, int h, int C, const
     const int blocks = rord ? ordered_grid(N, 4) : div_up(N, 4);
     const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair, *cq = ln.opts.csc_query;
     ForkJoin fj(st, fork_worthwhile((int64_t)M * h));  // grad_q and grad_k are independent
-    auto run = [&](auto dtag) {
+    dispatch_d(C / h, [&](auto dtag) {
         constexpr int D = decltype(dtag)::value;
-        const int chunks = div_up(h, 4);
-        hipLaunchKernelGGL((gather_accum_kernel<D, false>), dim3(blocks, chunks), dim3(256), 0, st, N, h, index0_offsets,
+        hipLaunchKernelGGL((gather_accum_kernel<D, false>), dim3(blocks, div_up(h, 4)), dim3(256), 0, st, N, h, index0_offsets,
                            index1, (const int *)nullptr, grad_out, k, grad_q, rord);
         if (co) {
             const int NK = ln.key_rows(N);
-            const int *kord = ln.rows_in_order(NK);  // (the keys of a window are its queries: the same order serves the transposed list)
-            hipLaunchKernelGGL((gather_accum_kernel<D, true>), dim3(kord ? ordered_grid(NK, 4) : div_up(NK, 4), chunks), dim3(256), 0, fj.lane(1), NK, h, co, cq, cp,
-                               grad_out, q, grad_k, kord);
+            // (the keys of a window are its queries: the same order serves the transposed list)
+            gather_accum_by_key(fj.lane(1), D, NK, h, co, cq, cp, grad_out, q, grad_k, ln.rows_in_order(NK));
         }
         else
             hipLaunchKernelGGL(scatter_atomic_kernel<D>, dim3(blocks), dim3(256), 0, st, N, h, index0_offsets,
                                index1, grad_out, q, grad_k);
-    };
-    dispatch_d(C / h, [&] { run(std::integral_constant<int, 16>{}); }, [&] { run(std::integral_constant<int, 32>{}); });
+        return true;
+    });
     check_launch();
 }
 
@@ -285,36 +282,25 @@ void attention_step1_forward_cuda_launcher(int N, int M, int h, int C, const flo
                                            const int *index0, const int *index1, float *attn) {
     (void)N;
     const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    if ((C / h) % 4) { set_error("head dim must be a multiple of 4"); return; }
-    hipLaunchKernelGGL(step1_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, q, k, index0, index1, attn);
-    check_launch();
+    if (M > 0 && (C / h) % 4) { set_error("head dim must be a multiple of 4"); return; }
+    launch_pair_heads(st, step1_v1_fwd_kernel, M, h, C / h, q, k, index0, index1, attn);
 }
 void attention_step1_backward_cuda_launcher(int N, int M, int h, int C, const float *grad_out,
                                             const int *index0, const int *index1, const float *q,
                                             const float *k, float *grad_q, float *grad_k) {
     (void)N;
-    const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    hipLaunchKernelGGL(step1_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, grad_out, index0, index1, q, k, grad_q, grad_k);
-    check_launch();
+    launch_pair_heads(begin_launch().stream, step1_v1_bwd_kernel, M, h, C / h, grad_out, index0, index1, q, k, grad_q, grad_k);
 }
 void attention_step2_forward_cuda_launcher(int N, int M, int h, int C, const float *attn, const float *v,
                                            const int *index0, const int *index1, float *output) {
     (void)N;
-    const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    hipLaunchKernelGGL(step2_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, attn, v, index0, index1, output);
-    check_launch();
+    launch_pair_heads(begin_launch().stream, step2_v1_fwd_kernel, M, h, C / h, attn, v, index0, index1, output);
 }
 void attention_step2_backward_cuda_launcher(int N, int M, int h, int C, const float *grad_out,
                                             const int *index0, const int *index1, const float *attn,
                                             const float *v, float *grad_attn, float *grad_v) {
     (void)N;
-    const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    hipLaunchKernelGGL(step2_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, C / h, grad_out, index0, index1, attn, v, grad_attn, grad_v);
-    check_launch();
+    launch_pair_heads(begin_launch().stream, step2_v1_bwd_kernel, M, h, C / h, grad_out, index0, index1, attn, v, grad_attn, grad_v);
 }
 // attention_cuda_kernel_v2.cu:148-195 is a byte-for-byte copy of the v1 step2 kernels.  (No begin_launch() here: the v1
 // launcher takes the stream and resets the launch options, of which it reads none.)

@@ -2,6 +2,7 @@
 // forward): cross-lane helpers, buffer addressing, the task dealing of a cell plan and the persistent grid.
 #pragma once
 #include "rpe_common.h"
+#include "row_types.h"
 #include <algorithm>
 
 namespace p2 {
@@ -47,38 +48,9 @@ __device__ __forceinline__ float4 slots_sum16_4(float4 v) {
 // ---- storage types of the q / k / v rows (RT) and of the tables (TT): fp32 arithmetic on exactly widened operands ----
 // (fp32, fp32): the reference's operators (stratified_transformer.py:183,194,208 `.float()`); (bf16, bf16): BASELINE config 3's second
 // leg; (half, fp32) and (bf16, fp32): the rows as the qkv Linear leaves them under autocast, the tables fp32 parameters.
-typedef unsigned short bf16_t;  // raw bits
-struct f16_t {                  // IEEE half, raw bits (a type of its own: bf16_t is the other 16-bit pattern)
-    unsigned short bits;
-};
-typedef _Float16 f16x2c __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float4 ld_row4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 ld_row4(const bf16_t *p) {
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);  // four bf16: widening to fp32 is a shift
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-}
-__device__ __forceinline__ float4 ld_row4(const f16_t *p) {
-    const uint2 u = *reinterpret_cast<const uint2 *>(p);  // four halves, two per dword: v_cvt_f32_f16 of each half
-    const f16x2c lo = __builtin_bit_cast(f16x2c, u.x), hi = __builtin_bit_cast(f16x2c, u.y);
-    return make_float4((float)lo.x, (float)lo.y, (float)hi.x, (float)hi.y);
-}
-__device__ __forceinline__ float ld_elem(const float *p) { return *p; }
-__device__ __forceinline__ float ld_elem(const bf16_t *p) { return __uint_as_float((unsigned)*p << 16); }
-__device__ __forceinline__ float ld_elem(const f16_t *p) { return (float)__builtin_bit_cast(_Float16, p->bits); }
+// The types, their loads and round_rows<RT>: row_types.h.
 // The model multiplies q by `scale` in q's own type (`query * self.scale`, :181: the product is taken in fp32 and rounded to
 // nearest even) before it widens it: round_rows<RT>(widened q * scale) is that tensor's element, bit for bit.
-template <typename RT>
-__device__ __forceinline__ float round_rows(float f);
-template <>
-__device__ __forceinline__ float round_rows<float>(float f) { return f; }
-template <>
-__device__ __forceinline__ float round_rows<f16_t>(float f) { return (float)(_Float16)f; }
-template <>
-__device__ __forceinline__ float round_rows<bf16_t>(float f) {
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return __uint_as_float(u | 0x00400000u);  // NaN stays NaN
-    return __uint_as_float((u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u);
-}
 template <typename RT>
 __device__ __forceinline__ float4 scaled_row4(const RT *p, float scale) {
     const float4 r = ld_row4(p);
@@ -231,21 +203,6 @@ struct CellTables {
 struct CellGrads {  // of the rows (the first point's row of each, laid out as the rows they belong to) or of the tables
     float *q, *k, *v;
 };
-template <typename RT>
-struct RowTag {
-    using type = RT;
-    static constexpr int code = std::is_same<RT, float>::value ? POINTOPS2_ROWS_F32 : std::is_same<RT, f16_t>::value ? POINTOPS2_ROWS_F16 : POINTOPS2_ROWS_BF16;
-};
-// f(RowTag<RT>{}) for the storage type that `row_type` (POINTOPS2_ROWS_*) names; false: no such code, f was not called
-template <typename F>
-static bool with_row_type(int row_type, F f) {
-    if (row_type == POINTOPS2_ROWS_F32) f(RowTag<float>{});
-    else if (row_type == POINTOPS2_ROWS_F16) f(RowTag<f16_t>{});
-    else if (row_type == POINTOPS2_ROWS_BF16) f(RowTag<bf16_t>{});
-    else return false;
-    return true;
-}
-
 // cell_attn_mfma.hip: the forward on the matrix cores (fp32 tables), variant POINTOPS2_CELL_FWD_MFMA64 or _MFMA80 of
 // pointops2_cell_forward_variant (cell_attn.hip decides).  packed: rows of `row_type` (POINTOPS2_ROWS_*), q scaled as it is loaded;
 // otherwise fp32 [N, h, 16] tensors taken as they stand.

@@ -17,6 +17,7 @@ struct LaunchState {
 LaunchState &state();
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
+inline int64_t div_up64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // What one launch works with: the caller's stream and the options set for it (include/pointops2_hip.h, PART 2).
 struct Launch {
@@ -57,6 +58,11 @@ void launch_bbox(int b, const float *xyz, const int *offset, float *bbox, hipStr
 // knn_grid.hip: returns false when the grid path does not apply (no workspace / unknown n, b / tiny problem)
 bool knn_grid_launch(const Launch &ln, int m, int k, const float *xyz, const float *new_xyz, const int *offset,
                      const int *new_offset, int *idx, float *dist2);
+
+// attention.hip: out[row, hh, :] += sum over the row's slots of w[pair(slot), hh] * src[query(slot), hh, :] by key, through the
+// key-major view of the pair list (grad_k of A1, grad_v of A4); d is 16 or 32; order: Launch::rows_in_order(n_keys) or nullptr
+void gather_accum_by_key(hipStream_t st, int d, int n_keys, int h, const int *csc_offsets, const int *csc_query, const int *csc_pair,
+                         const float *w, const float *src, float *out, const int *order);
 
 inline void set_error(const char *msg) { state().error = msg; }
 
@@ -144,9 +150,25 @@ inline void allow_big_lds(K kernel, size_t bytes) {
     }
 }
 
+// f(std::integral_constant<int, D>{}) for the head dimension of the pair-list walkers; f returns whether it launched
+template <typename F>
+inline bool dispatch_d(int d, F f) {
+    if (d == 16) return f(std::integral_constant<int, 16>{});
+    if (d == 32) return f(std::integral_constant<int, 32>{});
+    set_error("d != 16 and d != 32");
+    return false;
+}
+
+// the v1 pair-indexed forms: kernel(M, h, args...) with one thread per (pair, head)
+template <typename K, typename... A>
+inline void launch_pair_heads(hipStream_t st, K kernel, int M, int h, A... args) {
+    if (M <= 0) return;
+    hipLaunchKernelGGL(kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, args...);
+    check_launch();
+}
+
 // grid.x for a one-slot-per-wave launch (rows_per_wg waves): eight equal runs
 inline int ordered_grid(int n_rows, int rows_per_wg) { return 8 * div_up(div_up(n_rows, 8), rows_per_wg); }
-inline int64_t div_up64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- device helpers ----
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
@@ -184,6 +206,9 @@ __device__ __forceinline__ float4 fma4(float s, float4 a, float4 acc) {
     return make_float4(fmaf(s, a.x, acc.x), fmaf(s, a.y, acc.y), fmaf(s, a.z, acc.z), fmaf(s, a.w, acc.w));
 }
 __device__ __forceinline__ float4 scale4(float s, float4 a) { return make_float4(s * a.x, s * a.y, s * a.z, s * a.w); }
+__device__ __forceinline__ void atomic_add4(float *d, float4 v) {  // four scalar atomics: global or LDS
+    atomicAdd(d + 0, v.x); atomicAdd(d + 1, v.y); atomicAdd(d + 2, v.z); atomicAdd(d + 3, v.w);
+}
 
 // wave-wide unsigned max with DPP row operations (6 VALU + 1 readlane; a __shfl_xor butterfly costs 6
 // dependent ds_bpermute round trips, and the 64-bit key would double that)

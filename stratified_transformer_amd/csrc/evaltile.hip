@@ -26,11 +26,10 @@
 // the stamp in one wave-wide load that precedes the reset in program order (a row never straddles a wave: LPR divides 64), and the
 // row's idx and stamp are read once for both tensors.  The shift components ride on lanes 0..2 of the row: LPR is at least 8, so
 // these lanes exist whatever `classes` is - `classes` of 1 or 2 leaves them without a logit (inactive in the softmax, -inf / 0 as any
-// lane beyond `classes`), but they are lanes of a writer row all the same.  The softmax is vote_add_kernel's, operation for
-// operation; the shift is converted to fp32 (exact from f16 / bf16) and added with one fp32 add.  The shift's storage type is a
+// lane beyond `classes`), but they are lanes of a writer row all the same.  The softmax is vote_add_kernel's (vote_row, shared); the
+// shift is converted to fp32 (exact from f16 / bf16) and added with one fp32 add.  The shift's storage type is a
 // run-time argument (a wave-uniform branch around one load), so the kernel is instantiated per lane width and logit type only.
-#include <hip/hip_fp16.h>
-#include "common.h"
+#include "row_types.h"
 
 namespace p2 {
 namespace {
@@ -160,20 +159,33 @@ __global__ __launch_bounds__(ET_BLOCK) void vote_stamp_kernel(int m, int n_point
     atomicMax(&stamp[i], r);
 }
 
-__device__ __forceinline__ float logit_value(const float *p, size_t k) { return p[k]; }
-__device__ __forceinline__ float logit_value(const __half *p, size_t k) { return __half2float(p[k]); }
-__device__ __forceinline__ float logit_value(const unsigned short *p, size_t k) { return __uint_as_float((unsigned)p[k] << 16); }  // bf16
+// f(std::integral_constant<int, LPR>{}) for the lanes a row of `classes` logits takes: the power of two >= classes, at least 8
+template <typename F>
+void with_row_lanes(int classes, F f) {
+    if (classes <= 8) f(std::integral_constant<int, 8>{});
+    else if (classes <= 16) f(std::integral_constant<int, 16>{});
+    else if (classes <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
 
-// LPR lanes per row (a power of two >= classes), ET_BLOCK / LPR rows per workgroup
+// The vote of one row: LPR lanes per row, ET_BLOCK / LPR rows per workgroup; T: the logits' storage type (row_types.h).  Every lane
+// of row r learns whether the row is the writer of its point i - before lane 0 resets the stamp, which is the kernel's last step -
+// and the active lanes (class slot c < classes) add the row's softmax.
+struct VoteLane {
+    int r, c;
+    long long i;
+    bool writer;
+};
 template <int LPR, typename T>
-__global__ __launch_bounds__(ET_BLOCK) void vote_add_kernel(int m, int classes, int n_points, const T *__restrict__ logits,
-                                                            const long long *__restrict__ idx, int *stamp, float *__restrict__ pred) {
+__device__ __forceinline__ VoteLane vote_row(int m, int classes, int n_points, const T *__restrict__ logits, const long long *__restrict__ idx,
+                                             const int *stamp, float *__restrict__ pred) {
+    static_assert(LPR >= 3 && WAVE % LPR == 0, "a row holds the three shift lanes and stays inside one wave");
     const int r = blockIdx.x * (ET_BLOCK / LPR) + threadIdx.x / LPR, c = threadIdx.x % LPR;
     long long i = -1;
     if (r < m) i = idx[r];
     const bool writer = i >= 0 && i < n_points && stamp[i] == r;
     const bool active = writer && c < classes;
-    float x = active ? logit_value(logits, (size_t)r * classes + c) : -INFINITY;
+    float x = active ? ld_elem(&logits[(size_t)r * classes + c]) : -INFINITY;
     float mx = x;
 #pragma unroll
     for (int s = 1; s < LPR; s <<= 1) mx = fmaxf(mx, __shfl_xor(mx, s, WAVE));
@@ -182,26 +194,20 @@ __global__ __launch_bounds__(ET_BLOCK) void vote_add_kernel(int m, int classes, 
 #pragma unroll
     for (int s = 1; s < LPR; s <<= 1) sum += __shfl_xor(sum, s, WAVE);
     if (active) pred[(size_t)i * classes + c] += e / sum;
-    if (writer && c == 0) stamp[i] = -1;
+    return VoteLane{r, c, i, writer};
 }
 
-template <typename T>
-void launch_vote_add(hipStream_t st, int m, int classes, int n_points, const void *logits, const long long *idx, int *stamp, float *pred) {
-    const T *lg = (const T *)logits;
-    if (classes <= 8)
-        hipLaunchKernelGGL((vote_add_kernel<8, T>), dim3(div_up(m, ET_BLOCK / 8)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
-    else if (classes <= 16)
-        hipLaunchKernelGGL((vote_add_kernel<16, T>), dim3(div_up(m, ET_BLOCK / 16)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
-    else if (classes <= 32)
-        hipLaunchKernelGGL((vote_add_kernel<32, T>), dim3(div_up(m, ET_BLOCK / 32)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
-    else
-        hipLaunchKernelGGL((vote_add_kernel<64, T>), dim3(div_up(m, ET_BLOCK / 64)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, idx, stamp, pred);
+template <int LPR, typename T>
+__global__ __launch_bounds__(ET_BLOCK) void vote_add_kernel(int m, int classes, int n_points, const T *__restrict__ logits,
+                                                            const long long *__restrict__ idx, int *stamp, float *__restrict__ pred) {
+    const VoteLane v = vote_row<LPR>(m, classes, n_points, logits, idx, stamp, pred);
+    if (v.writer && v.c == 0) stamp[v.i] = -1;
 }
 
 __device__ __forceinline__ float shift_value(const void *p, int type, size_t k) {
-    if (type == POINTOPS2_ROWS_F32) return ((const float *)p)[k];
-    if (type == POINTOPS2_ROWS_F16) return __half2float(((const __half *)p)[k]);
-    return __uint_as_float((unsigned)((const unsigned short *)p)[k] << 16);  // bf16
+    if (type == POINTOPS2_ROWS_F32) return ld_elem(&((const float *)p)[k]);
+    if (type == POINTOPS2_ROWS_F16) return ld_elem(&((const f16_t *)p)[k]);
+    return ld_elem(&((const bf16_t *)p)[k]);
 }
 
 // vote_add_kernel with the second accumulator: the writer row also adds its three shift components, on lanes 0..2 of the row
@@ -209,44 +215,10 @@ template <int LPR, typename T>
 __global__ __launch_bounds__(ET_BLOCK) void vote_shift_add_kernel(int m, int classes, int n_points, const T *__restrict__ logits, int shift_type,
                                                                   const void *__restrict__ shift, const long long *__restrict__ idx, int *stamp,
                                                                   float *__restrict__ pred, float *__restrict__ pred_shift) {
-    static_assert(LPR >= 3 && WAVE % LPR == 0, "a row holds the three shift lanes and stays inside one wave");
-    const int r = blockIdx.x * (ET_BLOCK / LPR) + threadIdx.x / LPR, c = threadIdx.x % LPR;
-    long long i = -1;
-    if (r < m) i = idx[r];
-    const bool writer = i >= 0 && i < n_points && stamp[i] == r;  // every lane of the row, before lane 0 resets the stamp below
-    const bool active = writer && c < classes;
-    float x = active ? logit_value(logits, (size_t)r * classes + c) : -INFINITY;
-    float mx = x;
-#pragma unroll
-    for (int s = 1; s < LPR; s <<= 1) mx = fmaxf(mx, __shfl_xor(mx, s, WAVE));
-    const float e = active ? expf(x - mx) : 0.0f;
-    float sum = e;
-#pragma unroll
-    for (int s = 1; s < LPR; s <<= 1) sum += __shfl_xor(sum, s, WAVE);
-    if (active) pred[(size_t)i * classes + c] += e / sum;
-    if (writer && c < 3) pred_shift[(size_t)i * 3 + c] += shift_value(shift, shift_type, (size_t)r * 3 + c);
-    if (writer && c == 0) stamp[i] = -1;
+    const VoteLane v = vote_row<LPR>(m, classes, n_points, logits, idx, stamp, pred);
+    if (v.writer && v.c < 3) pred_shift[(size_t)v.i * 3 + v.c] += shift_value(shift, shift_type, (size_t)v.r * 3 + v.c);
+    if (v.writer && v.c == 0) stamp[v.i] = -1;
 }
-
-template <typename T>
-void launch_vote_shift_add(hipStream_t st, int m, int classes, int n_points, const void *logits, int shift_type, const void *shift,
-                           const long long *idx, int *stamp, float *pred, float *pred_shift) {
-    const T *lg = (const T *)logits;
-    if (classes <= 8)
-        hipLaunchKernelGGL((vote_shift_add_kernel<8, T>), dim3(div_up(m, ET_BLOCK / 8)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
-                           shift, idx, stamp, pred, pred_shift);
-    else if (classes <= 16)
-        hipLaunchKernelGGL((vote_shift_add_kernel<16, T>), dim3(div_up(m, ET_BLOCK / 16)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
-                           shift, idx, stamp, pred, pred_shift);
-    else if (classes <= 32)
-        hipLaunchKernelGGL((vote_shift_add_kernel<32, T>), dim3(div_up(m, ET_BLOCK / 32)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
-                           shift, idx, stamp, pred, pred_shift);
-    else
-        hipLaunchKernelGGL((vote_shift_add_kernel<64, T>), dim3(div_up(m, ET_BLOCK / 64)), dim3(ET_BLOCK), 0, st, m, classes, n_points, lg, shift_type,
-                           shift, idx, stamp, pred, pred_shift);
-}
-
-inline bool known_row_type(int t) { return t == POINTOPS2_ROWS_F32 || t == POINTOPS2_ROWS_F16 || t == POINTOPS2_ROWS_BF16; }
 
 }  // namespace
 }  // namespace p2
@@ -291,16 +263,21 @@ void pointops2_evaltile_vote_launcher(int m, int classes, int n_points, int row_
                                       float *pred, int *status) {
     const hipStream_t st = begin_launch().stream;
     if (m < 0 || n_points < 1 || classes < 1 || classes > 64) { set_error("evaltile_vote: need m >= 0, n_points >= 1 and 1 <= classes <= 64"); return; }
-    if (row_type != POINTOPS2_ROWS_F32 && row_type != POINTOPS2_ROWS_F16 && row_type != POINTOPS2_ROWS_BF16) {
+    if (!known_row_type(row_type)) {
         set_error("evaltile_vote: row_type must be POINTOPS2_ROWS_F32, _F16 or _BF16");
         return;
     }
     if (m == 0) return;
     if (!logits || !idx || !stamp || !pred || !status) { set_error("evaltile_vote: a NULL array"); return; }
     hipLaunchKernelGGL(vote_stamp_kernel, dim3(div_up(m, ET_BLOCK)), dim3(ET_BLOCK), 0, st, m, n_points, idx, stamp, status);
-    if (row_type == POINTOPS2_ROWS_F32) launch_vote_add<float>(st, m, classes, n_points, logits, idx, stamp, pred);
-    else if (row_type == POINTOPS2_ROWS_F16) launch_vote_add<__half>(st, m, classes, n_points, logits, idx, stamp, pred);
-    else launch_vote_add<unsigned short>(st, m, classes, n_points, logits, idx, stamp, pred);
+    with_row_type(row_type, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        with_row_lanes(classes, [&](auto lanes) {
+            constexpr int LPR = decltype(lanes)::value;
+            hipLaunchKernelGGL((vote_add_kernel<LPR, T>), dim3(div_up(m, ET_BLOCK / LPR)), dim3(ET_BLOCK), 0, st, m, classes, n_points, (const T *)logits,
+                               idx, stamp, pred);
+        });
+    });
     check_launch();
 }
 
@@ -315,9 +292,14 @@ void pointops2_evaltile_vote_shift_launcher(int m, int classes, int n_points, in
     if (m == 0) return;
     if (!logits || !shift || !idx || !stamp || !pred || !pred_shift || !status) { set_error("evaltile_vote_shift: a NULL array"); return; }
     hipLaunchKernelGGL(vote_stamp_kernel, dim3(div_up(m, ET_BLOCK)), dim3(ET_BLOCK), 0, st, m, n_points, idx, stamp, status);
-    if (row_type == POINTOPS2_ROWS_F32) launch_vote_shift_add<float>(st, m, classes, n_points, logits, shift_row_type, shift, idx, stamp, pred, pred_shift);
-    else if (row_type == POINTOPS2_ROWS_F16) launch_vote_shift_add<__half>(st, m, classes, n_points, logits, shift_row_type, shift, idx, stamp, pred, pred_shift);
-    else launch_vote_shift_add<unsigned short>(st, m, classes, n_points, logits, shift_row_type, shift, idx, stamp, pred, pred_shift);
+    with_row_type(row_type, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        with_row_lanes(classes, [&](auto lanes) {
+            constexpr int LPR = decltype(lanes)::value;
+            hipLaunchKernelGGL((vote_shift_add_kernel<LPR, T>), dim3(div_up(m, ET_BLOCK / LPR)), dim3(ET_BLOCK), 0, st, m, classes, n_points,
+                               (const T *)logits, shift_row_type, shift, idx, stamp, pred, pred_shift);
+        });
+    });
     check_launch();
 }
 

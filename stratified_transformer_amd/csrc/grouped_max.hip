@@ -19,7 +19,7 @@
 //             does, per query and channel).  fp32 accumulation in pair order, one rounding to the row type, every row of grad_feat
 //             written: no atomics, no zero-fill, the same bits from run to run.
 // Channel counts that are no multiple of the chunk (or operands that are not 16-byte aligned) take one thread per element.
-#include "common.h"
+#include "row_types.h"
 
 namespace p2 {
 namespace {
@@ -30,46 +30,23 @@ constexpr int FWD_NB = 16;    // neighbours in flight per lane (the model's k: o
 constexpr int BWD_NB = 4;     // pairs in flight per lane (m * k / n_s = 4 at ratio 0.25, k = 16)
 constexpr int NO_ARG = 255;
 
-// ---- the three row types: RT = POINTOPS2_ROWS_*; elements are widened exactly, compared / summed in fp32 ----
-template <int RT> struct Row;
-template <> struct Row<POINTOPS2_ROWS_F32> {
-    typedef float elem;
-    static __device__ __forceinline__ float widen(elem v) { return v; }
-    static __device__ __forceinline__ elem narrow(float f) { return f; }
-};
-template <> struct Row<POINTOPS2_ROWS_F16> {
-    typedef unsigned short elem;
-    static __device__ __forceinline__ float widen(elem v) { return (float)__builtin_bit_cast(_Float16, v); }
-    static __device__ __forceinline__ elem narrow(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }  // nearest even
-};
-template <> struct Row<POINTOPS2_ROWS_BF16> {
-    typedef unsigned short elem;
-    static __device__ __forceinline__ float widen(elem v) { return __uint_as_float((unsigned)v << 16); }
-    static __device__ __forceinline__ elem narrow(float f) {
-        const unsigned u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (elem)((u >> 16) | 0x40u);  // NaN stays NaN
-        return (elem)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                    // nearest even
-    }
-};
-
-// one 16-byte chunk of a row: VEC elements
-template <int RT> struct Chunk {
-    typedef typename Row<RT>::elem elem;
-    static constexpr int VEC = 16 / (int)sizeof(elem);
+// one 16-byte chunk of a row of storage type RT (row_types.h): VEC elements, widened exactly, compared / summed in fp32
+template <typename RT> struct Chunk {
+    static constexpr int VEC = 16 / (int)sizeof(RT);
     uint4 bits;
     __device__ __forceinline__ float get(int e) const {
         const unsigned w[4] = {bits.x, bits.y, bits.z, bits.w};
-        if constexpr (sizeof(elem) == 4) return __uint_as_float(w[e]);
-        else return Row<RT>::widen((elem)((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu)));
+        if constexpr (sizeof(RT) == 4) return __uint_as_float(w[e]);
+        else return widen_bits<RT>((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu));
     }
     static __device__ __forceinline__ uint4 pack(const float *v) {
         unsigned w[4];
-        if constexpr (sizeof(elem) == 4) {
+        if constexpr (sizeof(RT) == 4) {
 #pragma unroll
             for (int e = 0; e < 4; e++) w[e] = __float_as_uint(v[e]);
         } else {
 #pragma unroll
-            for (int e = 0; e < 4; e++) w[e] = (unsigned)Row<RT>::narrow(v[2 * e]) | ((unsigned)Row<RT>::narrow(v[2 * e + 1]) << 16);
+            for (int e = 0; e < 4; e++) w[e] = narrow_bits<RT>(v[2 * e]) | (narrow_bits<RT>(v[2 * e + 1]) << 16);
         }
         return make_uint4(w[0], w[1], w[2], w[3]);
     }
@@ -95,14 +72,14 @@ struct RowLanes {
     }
 };
 
-template <int RT>
+template <typename RT>
 __global__ __launch_bounds__(GM_WAVES * WAVE) void grouped_max_fwd_kernel(int m, int n_s, int k, int c, int chunks, const void *__restrict__ feat,
                                                                           const int *__restrict__ idx, void *__restrict__ out,
                                                                           unsigned char *__restrict__ arg) {
     typedef Chunk<RT> C;
     constexpr int VEC = C::VEC;
     const RowLanes rl(chunks);
-    const size_t row_bytes = (size_t)c * sizeof(typename C::elem);
+    const size_t row_bytes = (size_t)c * sizeof(RT);
     const int wave = blockIdx.x * GM_WAVES + (threadIdx.x >> 6), waves = gridDim.x * GM_WAVES;
     for (long long first = (long long)wave * rl.per_wave; first < m; first += (long long)waves * rl.per_wave) {
         const long long i = first + rl.sub;
@@ -150,12 +127,11 @@ __global__ __launch_bounds__(GM_WAVES * WAVE) void grouped_max_fwd_kernel(int m,
 }
 
 // one thread per (query, channel): any c, any alignment
-template <int RT>
+template <typename RT>
 __global__ __launch_bounds__(256) void grouped_max_fwd_scalar_kernel(int m, int n_s, int k, int c, const void *__restrict__ feat,
                                                                      const int *__restrict__ idx, void *__restrict__ out,
                                                                      unsigned char *__restrict__ arg) {
-    typedef typename Row<RT>::elem elem;
-    const elem *f = reinterpret_cast<const elem *>(feat);
+    const RT *f = reinterpret_cast<const RT *>(feat);
     const long long total = (long long)m * c;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         const long long i = t / c;
@@ -165,10 +141,10 @@ __global__ __launch_bounds__(256) void grouped_max_fwd_scalar_kernel(int m, int 
         for (int n = 0; n < k; n++) {
             const int j = idx[(size_t)i * k + n];
             if ((unsigned)j >= (unsigned)n_s) continue;
-            const float x = Row<RT>::widen(f[(size_t)j * c + ch]);
+            const float x = ld_elem(&f[(size_t)j * c + ch]);
             if (takes(x, best, a)) best = x, a = n;
         }
-        reinterpret_cast<elem *>(out)[t] = Row<RT>::narrow(best);  // (exact: best is an element of feat, or 0)
+        st_elem(&reinterpret_cast<RT *>(out)[t], best);  // (exact: best is an element of feat, or 0)
         if (arg != nullptr) arg[t] = (unsigned char)a;
     }
 }
@@ -179,7 +155,7 @@ __device__ __forceinline__ void pair_range(const int *__restrict__ src_offsets, 
     p1 = min(max(src_offsets[j + 1], p0), n_pairs);
 }
 
-template <int RT>
+template <typename RT>
 __global__ __launch_bounds__(GM_WAVES * WAVE) void grouped_max_bwd_kernel(int m, int n_s, int k, int c, int chunks,
                                                                           const void *__restrict__ grad_out,
                                                                           const unsigned char *__restrict__ arg,
@@ -188,7 +164,7 @@ __global__ __launch_bounds__(GM_WAVES * WAVE) void grouped_max_bwd_kernel(int m,
     typedef Chunk<RT> C;
     constexpr int VEC = C::VEC;
     const RowLanes rl(chunks);
-    const size_t row_bytes = (size_t)c * sizeof(typename C::elem);
+    const size_t row_bytes = (size_t)c * sizeof(RT);
     const int n_pairs = m * k;  // (fits: the launcher checked)
     const int wave = blockIdx.x * GM_WAVES + (threadIdx.x >> 6), waves = gridDim.x * GM_WAVES;
     for (long long first = (long long)wave * rl.per_wave; first < n_s; first += (long long)waves * rl.per_wave) {
@@ -238,13 +214,12 @@ __global__ __launch_bounds__(GM_WAVES * WAVE) void grouped_max_bwd_kernel(int m,
     }
 }
 
-template <int RT>
+template <typename RT>
 __global__ __launch_bounds__(256) void grouped_max_bwd_scalar_kernel(int m, int n_s, int k, int c, const void *__restrict__ grad_out,
                                                                      const unsigned char *__restrict__ arg,
                                                                      const int *__restrict__ src_offsets, const int *__restrict__ src_pair,
                                                                      void *__restrict__ grad_feat) {
-    typedef typename Row<RT>::elem elem;
-    const elem *g = reinterpret_cast<const elem *>(grad_out);
+    const RT *g = reinterpret_cast<const RT *>(grad_out);
     const int n_pairs = m * k;
     const long long total = (long long)n_s * c;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
@@ -257,9 +232,9 @@ __global__ __launch_bounds__(256) void grouped_max_bwd_scalar_kernel(int m, int 
             const int q = src_pair[p];
             if ((unsigned)q >= (unsigned)n_pairs) continue;
             const int i = q / k, n = q - i * k;
-            if ((int)arg[(size_t)i * c + ch] == n) acc += Row<RT>::widen(g[(size_t)i * c + ch]);
+            if ((int)arg[(size_t)i * c + ch] == n) acc += ld_elem(&g[(size_t)i * c + ch]);
         }
-        reinterpret_cast<elem *>(grad_feat)[t] = Row<RT>::narrow(acc);
+        st_elem(&reinterpret_cast<RT *>(grad_feat)[t], acc);
     }
 }
 
@@ -268,15 +243,13 @@ const char *grouped_max_bad_args(int m, int n_s, int k, int c, int row_type) {
     if (m < 0 || n_s < 0) return "grouped_max: negative row count";
     if (k < 1 || k > GM_MAX_K) return "grouped_max: k must be in [1, 64]";
     if (c < 1 || c > GM_MAX_C) return "grouped_max: c must be in [1, 1024]";
-    if (row_type != POINTOPS2_ROWS_F32 && row_type != POINTOPS2_ROWS_F16 && row_type != POINTOPS2_ROWS_BF16)
-        return "grouped_max: row_type must be POINTOPS2_ROWS_F32, _F16 or _BF16";
+    if (!known_row_type(row_type)) return "grouped_max: row_type must be POINTOPS2_ROWS_F32, _F16 or _BF16";
     if ((long long)m * k > 0x7fffffffLL) return "grouped_max: m * k does not fit the int32 pair ids";
     return nullptr;
 }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // 16-byte chunks per row when the chunked kernels apply (whole chunks, aligned operands), else 0
-inline int row_chunks(int c, int row_type, const void *a, const void *b, const unsigned char *arg) {
-    const int vec = row_type == POINTOPS2_ROWS_F32 ? 4 : 8;
+inline int row_chunks(int c, int vec, const void *a, const void *b, const unsigned char *arg) {
     if (c % vec != 0 || !aligned16(a) || !aligned16(b) || (reinterpret_cast<uintptr_t>(arg) & 3u) != 0) return 0;
     return c / vec;
 }
@@ -290,9 +263,9 @@ inline int scalar_grid(long long total) {
     return (int)(want < cap ? want : cap);
 }
 
-template <int RT>
+template <typename RT>
 void launch_fwd(hipStream_t st, int m, int n_s, int k, int c, const void *feat, const int *idx, void *out, unsigned char *arg) {
-    const int chunks = row_chunks(c, RT, feat, out, arg);
+    const int chunks = row_chunks(c, Chunk<RT>::VEC, feat, out, arg);
     if (chunks > 0)
         hipLaunchKernelGGL(grouped_max_fwd_kernel<RT>, dim3(chunked_grid(m, chunks)), dim3(GM_WAVES * WAVE), 0, st, m, n_s, k, c, chunks, feat, idx,
                            out, arg);
@@ -300,10 +273,10 @@ void launch_fwd(hipStream_t st, int m, int n_s, int k, int c, const void *feat, 
         hipLaunchKernelGGL(grouped_max_fwd_scalar_kernel<RT>, dim3(scalar_grid((long long)m * c)), dim3(256), 0, st, m, n_s, k, c, feat, idx, out,
                            arg);
 }
-template <int RT>
+template <typename RT>
 void launch_bwd(hipStream_t st, int m, int n_s, int k, int c, const void *grad_out, const unsigned char *arg, const int *src_offsets,
                 const int *src_pair, void *grad_feat) {
-    const int chunks = row_chunks(c, RT, grad_out, grad_feat, arg);
+    const int chunks = row_chunks(c, Chunk<RT>::VEC, grad_out, grad_feat, arg);
     if (chunks > 0)
         hipLaunchKernelGGL(grouped_max_bwd_kernel<RT>, dim3(chunked_grid(n_s, chunks)), dim3(GM_WAVES * WAVE), 0, st, m, n_s, k, c, chunks, grad_out,
                            arg, src_offsets, src_pair, grad_feat);
@@ -324,9 +297,7 @@ void grouped_max_forward_launcher(int m, int n_s, int k, int c, int row_type, co
     const hipStream_t st = begin_launch().stream;
     if (const char *bad = grouped_max_bad_args(m, n_s, k, c, row_type)) { set_error(bad); return; }
     if (m == 0 || n_s == 0) return;
-    if (row_type == POINTOPS2_ROWS_F32) launch_fwd<POINTOPS2_ROWS_F32>(st, m, n_s, k, c, feat, idx, out, arg);
-    else if (row_type == POINTOPS2_ROWS_F16) launch_fwd<POINTOPS2_ROWS_F16>(st, m, n_s, k, c, feat, idx, out, arg);
-    else launch_fwd<POINTOPS2_ROWS_BF16>(st, m, n_s, k, c, feat, idx, out, arg);
+    with_row_type(row_type, [&](auto tag) { launch_fwd<typename decltype(tag)::type>(st, m, n_s, k, c, feat, idx, out, arg); });
     check_launch();
 }
 
@@ -336,9 +307,9 @@ void grouped_max_backward_launcher(int m, int n_s, int k, int c, int row_type, c
     if (const char *bad = grouped_max_bad_args(m, n_s, k, c, row_type)) { set_error(bad); return; }
     if (m == 0 || n_s == 0) return;
     if (arg == nullptr) { set_error("grouped_max_backward: arg is NULL (the forward was run without it)"); return; }
-    if (row_type == POINTOPS2_ROWS_F32) launch_bwd<POINTOPS2_ROWS_F32>(st, m, n_s, k, c, grad_out, arg, src_offsets, src_pair, grad_feat);
-    else if (row_type == POINTOPS2_ROWS_F16) launch_bwd<POINTOPS2_ROWS_F16>(st, m, n_s, k, c, grad_out, arg, src_offsets, src_pair, grad_feat);
-    else launch_bwd<POINTOPS2_ROWS_BF16>(st, m, n_s, k, c, grad_out, arg, src_offsets, src_pair, grad_feat);
+    with_row_type(row_type, [&](auto tag) {
+        launch_bwd<typename decltype(tag)::type>(st, m, n_s, k, c, grad_out, arg, src_offsets, src_pair, grad_feat);
+    });
     check_launch();
 }
 

@@ -12,7 +12,7 @@
 // x, z, dx, dZ, gamma, beta, s, stat are fp32 (the residual stream is fp32 with and without autocast); y / dy and o / dO each have one
 // of the three row types POINTOPS2_ROWS_* (what a Linear yields and wants under autocast), widened exactly and rounded once.
 //
-// Lanes (as grouped_max.hip): a lane owns one chunk of a row - four channels: 16 bytes of an fp32 row, 8 of a half row.  A row of
+// Lanes: a lane owns one chunk of a row - four channels: 16 bytes of an fp32 row, 8 of a half row (widened and narrowed by row_types.h).  A row of
 // `chunks` <= 64 chunks occupies a SEGMENT of seg = the next power of two lanes (12, 24, 48 chunks -> 16, 32, 64 lanes; the lanes
 // behind the row's last chunk idle and add 0), so 64 / seg rows sit side by side in a wave and the row sums are an xor butterfly
 // over the aligned segment: every lane of it ends with the same bits, and no value crosses a segment - a NaN stays in its row.
@@ -26,7 +26,7 @@
 // then the 64 groups by a fixed halving tree (q takes q + 32, q + 16, ...: a sequential sum of a thousand partials would lose three more
 // bits than torch's own reduction does).  The backward's grid is capped by the rows of `partials` the caller provides.  The order is
 // a function of the shapes alone: the same bits from run to run on one device.
-#include "common.h"
+#include "row_types.h"
 
 namespace p2 {
 namespace {
@@ -35,16 +35,6 @@ constexpr int RN_MAX_C = 1024;
 constexpr int RN_WAVES = 4;                       // per workgroup
 constexpr int RN_THREADS = RN_WAVES * WAVE;
 constexpr int RED_COLS = 16, RED_GROUPS = 64;     // rownorm_param_kernel: a workgroup sums 16 columns of `partials` in 64 groups of rows
-
-__device__ __forceinline__ float widen16(unsigned v, int rt) {
-    return rt == POINTOPS2_ROWS_F16 ? (float)__builtin_bit_cast(_Float16, (unsigned short)v) : __uint_as_float(v << 16);
-}
-__device__ __forceinline__ unsigned narrow16(float f, int rt) {
-    if (rt == POINTOPS2_ROWS_F16) return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f);  // nearest even
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // NaN stays NaN
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;                   // nearest even
-}
 
 // VEC consecutive elements of a row of type rt, from element `e` of `base`, as floats
 template <int VEC>
@@ -299,12 +289,11 @@ __global__ __launch_bounds__(RED_COLS *RED_GROUPS) void rownorm_param_kernel(int
     }
 }
 
-bool row_type_ok(int t) { return t == POINTOPS2_ROWS_F32 || t == POINTOPS2_ROWS_F16 || t == POINTOPS2_ROWS_BF16; }
 // nullptr when the arguments are in range
 const char *rownorm_bad_args(int n, int c, int y_type, int o_type) {
     if (n < 0) return "residual_norm: negative row count";
     if (c < 1 || c > RN_MAX_C) return "residual_norm: c must be in [1, 1024]";
-    if (!row_type_ok(y_type) || !row_type_ok(o_type)) return "residual_norm: row types must be POINTOPS2_ROWS_F32, _F16 or _BF16";
+    if (!known_row_type(y_type) || !known_row_type(o_type)) return "residual_norm: row types must be POINTOPS2_ROWS_F32, _F16 or _BF16";
     return nullptr;  // (n * c: the kernels index with 64-bit offsets)
 }
 inline bool aligned_to(const void *p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }

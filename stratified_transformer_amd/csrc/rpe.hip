@@ -239,8 +239,7 @@ __global__ __launch_bounds__(256) void a2_bwd_query_kernel(int N, int h, int L, 
                             float *kp = (float *)k + (size_t)j * C + (h0 + t) * D + 4 * c;
                             const float4 k4 = ldg4(kp);
                             const float4 gk = scale4(g, tsum<D>(Tk, L, t, r0, r1, r2, c));
-                            float *d = grad_k + (size_t)j * C + (h0 + t) * D + 4 * c;
-                            atomicAdd(d + 0, gk.x); atomicAdd(d + 1, gk.y); atomicAdd(d + 2, gk.z); atomicAdd(d + 3, gk.w);
+                            atomic_add4(grad_k + (size_t)j * C + (h0 + t) * D + 4 * c, gk);
                             tadd<D>(Gk, L, t, r0, r1, r2, c, scale4(g, k4));
                         }
                     }
@@ -399,10 +398,7 @@ __global__ __launch_bounds__(256) void a4_bwd_query_kernel(int N, int h, int L, 
                         const float a = attn[(size_t)m * h + h0 + t];
                         const float4 ag = scale4(a, g4[t]);
                         tadd<D>(Gv, L, t, r0, r1, r2, c, ag);
-                        if (KEYSIDE) {
-                            float *d = grad_v + (size_t)j * C + (h0 + t) * D + 4 * c;
-                            atomicAdd(d + 0, ag.x); atomicAdd(d + 1, ag.y); atomicAdd(d + 2, ag.z); atomicAdd(d + 3, ag.w);
-                        }
+                        if (KEYSIDE) atomic_add4(grad_v + (size_t)j * C + (h0 + t) * D + 4 * c, ag);
                     }
                 }
             }
@@ -411,65 +407,6 @@ __global__ __launch_bounds__(256) void a4_bwd_query_kernel(int N, int h, int L, 
     }
     __syncthreads();
     flush_table<D>(Gv, grad_table, L, h, h0, hgn);
-}
-
-// key-major accumulate used for grad_v (defined in attention.hip, instantiated here through a thin
-// duplicate to keep the translation units independent)
-template <int D>
-__global__ __launch_bounds__(256) void key_accum_kernel(int N, int h, const int *__restrict__ offs,
-                                                        const int *__restrict__ sidx, const int *__restrict__ widx,
-                                                        const float *__restrict__ w, const float *__restrict__ src,
-                                                        float *__restrict__ out, const int *__restrict__ rord) {
-    constexpr int LPG = Geo<D>::LPG, PPW = Geo<D>::PPW, HC = 4;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const RowSlots slots(rord, N, 4, wave);
-    if (!slots.more()) return;
-    const int row = slots.row();
-    const int C = h * D;
-    const int p = lane / LPG, c = lane % LPG;
-    const int s = offs[row], e = offs[row + 1];
-    for (int hb = blockIdx.y * HC; hb < h; hb += gridDim.y * HC) {  // head chunks over blockIdx.y (attention.hip)
-        float4 acc[HC];
-#pragma unroll
-        for (int t = 0; t < HC; t++) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 prev[HC];  // the row's running sum, requested now and consumed after the walk
-#pragma unroll
-        for (int t = 0; t < HC; t++) prev[t] = ldg4(out + (size_t)row * C + min(hb + t, h - 1) * D + 4 * c);
-        // the ids of the next pass are requested together with the weights and rows of this one (one round trip per
-        // pass); a slot past the row's end repeats the row's last slot and is not added
-        const int first = max(0, min(s + p, e - 1));
-        int sn = sidx[first], wn = widx[first];
-        for (int m0 = s; m0 < e; m0 += PPW) {
-            const int slot = m0 + p;
-            const int nslot = min(slot + PPW, e - 1);
-            const float *srow = src + (size_t)sn * C + 4 * c;
-            const float *wrow = w + (size_t)wn * h;
-            sn = sidx[nslot];
-            wn = widx[nslot];
-            // no per-head guards: a slot past the last head repeats it (its sum is not stored), so the HC weight and
-            // row loads of a pass are issued together instead of one dependent round trip per head
-            if (slot < e) {
-                float wv[HC];
-                float4 sv[HC];
-#pragma unroll
-                for (int t = 0; t < HC; t++) {
-                    const int hh = min(hb + t, h - 1);
-                    wv[t] = wrow[hh];
-                    sv[t] = ldg4(srow + hh * D);
-                }
-                __builtin_amdgcn_sched_barrier(0);  // every load of the pass before its first use
-#pragma unroll
-                for (int t = 0; t < HC; t++) acc[t] = fma4(wv[t], sv[t], acc[t]);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < HC; t++) {
-            if (hb + t < h) {
-                float4 tot = xor_sum4<LPG, 64>(acc[t]);
-                if (p == 0) stg4(out + (size_t)row * C + (hb + t) * D + 4 * c, add4(tot, prev[t]));
-            }
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -556,41 +493,28 @@ static int table_rows_or_error(const Launch &ln) {
     if (L <= 0) set_error("rel-pos tables: this launcher needs the tables' row count L (pointops2_launch_opts.table_rows)");
     return L;
 }
-
-// waves_per_block: rows a workgroup handles at a time; per_cu: resident workgroups per CU (LDS / register budget)
-static int persistent_blocks(int rows, int head_groups, int waves_per_block = 4, int per_cu = 2) {
-    int want = div_up(rows, waves_per_block);
-    const int cus = usable_cus();
-    int cap = cus * per_cu;
-    if (head_groups > 1) cap = max(cus * per_cu / head_groups, cus / 2);
-    return min(want, cap);
+// the table length was not given: global() enqueues the generic global-memory kernels (rpe_fallback.hip); false: it was given
+template <typename F>
+static bool without_table_rows(const Launch &ln, F global) {
+    if (ln.opts.table_rows > 0) return false;
+    global();
+    check_launch();
+    return true;
 }
 
+// f(HG tag, head groups, LDS bytes) for the heads per workgroup at which `narr` images of the [L, ., D, 3] tables fit the LDS budget;
+// false: not even one head does, f was not called
 template <int D, typename F>
-static void with_hg(int hg, F f) {
-    if (hg == 1) f(std::integral_constant<int, 1>{});
-    else if (hg == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 3>{});
+static bool with_table_slice(int h, int L, int narr, F f) {
+    const int hg = pick_hg(h, L, D, narr);
+    if (hg == 0) { set_error("rel-pos table slice does not fit in LDS"); return false; }
+    with_head_group(hg, [&](auto hgtag) { f(hgtag, div_up(h, hg), (size_t)narr * hg * 3 * L * D * sizeof(float)); });
+    return true;
 }
 
 }  // namespace p2
 
 using namespace p2;
-
-#define P2_LAUNCH_HG(D_, narr_, BODY)                                                           \
-    {                                                                                           \
-        const int hg = pick_hg(h, L, D_, narr_);                                                \
-        if (hg == 0) { set_error("rel-pos table slice does not fit in LDS"); return; }          \
-        const int ngroups = div_up(h, hg);                                                      \
-        const size_t lds_bytes = (size_t)narr_ * hg * 3 * L * D_ * sizeof(float);               \
-        with_hg<D_>(hg, [&](auto hgtag) {                                                       \
-            constexpr int HGc = decltype(hgtag)::value;                                         \
-            constexpr int Dc = D_;                                                              \
-            (void)HGc; (void)Dc;                                                                \
-            BODY                                                                                \
-        });                                                                                     \
-        (void)ngroups; (void)lds_bytes;                                                         \
-    }
 
 extern "C" {
 
@@ -602,24 +526,18 @@ void dot_prod_with_idx_forward_cuda_launcher_v3(int N, int M, int h, int hdim, i
     const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
     const hipStream_t st = ln.stream;
+    if (without_table_rows(ln, [&] { a2_fwd_global(st, N, M, h, hdim, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output); })) return;
     const int L = ln.opts.table_rows;
-    if (L <= 0) {  // table length not given: the generic global-memory kernels (rpe_fallback.hip)
-        a2_fwd_global(st, N, M, h, hdim, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output);
-        check_launch();
-        return;
-    }
-    if (hdim == 16) P2_LAUNCH_HG(16, 2, {
-        allow_big_lds(a2_fwd_kernel<Dc, HGc>, lds_bytes);
-        hipLaunchKernelGGL((a2_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
-                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output, ln.rows_in_order(N));
-    })
-    else if (hdim == 32) P2_LAUNCH_HG(32, 2, {
-        allow_big_lds(a2_fwd_kernel<Dc, HGc>, lds_bytes);
-        hipLaunchKernelGGL((a2_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
-                           N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output, ln.rows_in_order(N));
-    })
-    else { set_error("d != 16 and d != 32"); return; }
-    check_launch();
+    const bool launched = dispatch_d(hdim, [&](auto dtag) {
+        constexpr int D = decltype(dtag)::value;
+        return with_table_slice<D>(h, L, 2, [&](auto hgtag, int ngroups, size_t lds_bytes) {
+            constexpr int HG = decltype(hgtag)::value;
+            allow_big_lds(a2_fwd_kernel<D, HG>, lds_bytes);
+            hipLaunchKernelGGL((a2_fwd_kernel<D, HG>), dim3(walk_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
+                               N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, output, ln.rows_in_order(N));
+        });
+    });
+    if (launched) check_launch();
 }
 
 void window_logits_softmax_forward_launcher(int N, int M, int h, int hdim, const float *q, const int *index_q_offsets,
@@ -631,12 +549,13 @@ void window_logits_softmax_forward_launcher(int N, int M, int h, int hdim, const
     if (L <= 0) return;
     if (hdim != 16) { set_error("window_logits_softmax: d != 16"); return; }
     const hipStream_t st = ln.stream;
-    P2_LAUNCH_HG(16, 2, {
-        allow_big_lds(wlogit_softmax_kernel<HGc>, lds_bytes);
-        hipLaunchKernelGGL((wlogit_softmax_kernel<HGc>), dim3(persistent_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
+    const bool launched = with_table_slice<16>(h, L, 2, [&](auto hgtag, int ngroups, size_t lds_bytes) {
+        constexpr int HG = decltype(hgtag)::value;
+        allow_big_lds(wlogit_softmax_kernel<HG>, lds_bytes);
+        hipLaunchKernelGGL((wlogit_softmax_kernel<HG>), dim3(walk_blocks(N, ngroups, 12, 2), ngroups), dim3(768), lds_bytes, st,
                            N, h, L, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, attn, ln.rows_in_order(N));
-    })
-    check_launch();
+    });
+    if (launched) check_launch();
 }
 
 void window_attention_backward_launcher(int N, int M, int h, int hdim, const float *grad_out, const float *q, const float *k,
@@ -665,12 +584,11 @@ void dot_prod_with_idx_backward_cuda_launcher_v3(int N, int M, int h, int hdim, 
     const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
     const hipStream_t st = ln.stream;
-    const int L = ln.opts.table_rows;
-    if (L <= 0) {
-        a2_bwd_global(st, N, M, h, hdim, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q, grad_table_k);
-        check_launch();
+    if (without_table_rows(ln, [&] {
+            a2_bwd_global(st, N, M, h, hdim, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q, grad_table_k);
+        }))
         return;
-    }
+    const int L = ln.opts.table_rows;
     const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair;
     const int NK = ln.key_rows(N);
     // D=16, L<=80 with a CSC view: table gradients on the matrix cores (rpe_bwd_mfma.hip)
@@ -679,30 +597,29 @@ void dot_prod_with_idx_backward_cuda_launcher_v3(int N, int M, int h, int hdim, 
         check_launch();
         return;
     }
-#define P2_A2_BWD(D_)                                                                                                       \
-    if (co) {                                                                                                               \
-        P2_LAUNCH_HG(D_, 2, {                                                                                               \
-            allow_big_lds(a2_bwd_query_kernel<Dc, HGc, false>, lds_bytes);                                                  \
-            allow_big_lds(a2_bwd_key_kernel<Dc, HGc>, lds_bytes);                                                           \
-            hipLaunchKernelGGL((a2_bwd_query_kernel<Dc, HGc, false>), dim3(persistent_blocks(N, ngroups), ngroups), dim3(256), \
-                               lds_bytes, st, N, h, L, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx,  \
-                               grad_q, grad_k, grad_table_q, grad_table_k);                                                 \
-            hipLaunchKernelGGL((a2_bwd_key_kernel<Dc, HGc>), dim3(persistent_blocks(NK, ngroups), ngroups), dim3(256),       \
-                               lds_bytes, st, NK, h, L, grad_out, k, co, cp, table_k, rel_idx, grad_k, grad_table_k);       \
-        })                                                                                                                  \
-    } else {                                                                                                                \
-        P2_LAUNCH_HG(D_, 4, {                                                                                               \
-            allow_big_lds(a2_bwd_query_kernel<Dc, HGc, true>, lds_bytes);                                                   \
-            hipLaunchKernelGGL((a2_bwd_query_kernel<Dc, HGc, true>), dim3(persistent_blocks(N, ngroups), ngroups), dim3(256), \
-                               lds_bytes, st, N, h, L, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx,  \
-                               grad_q, grad_k, grad_table_q, grad_table_k);                                                 \
-        })                                                                                                                  \
-    }
-    if (hdim == 16) { P2_A2_BWD(16) }
-    else if (hdim == 32) { P2_A2_BWD(32) }
-    else { set_error("d != 16 and d != 32"); return; }
-#undef P2_A2_BWD
-    check_launch();
+    // with a CSC view the key side has a kernel of its own; without one the by-query kernel takes it along (four LDS images, atomics)
+    const bool launched = dispatch_d(hdim, [&](auto dtag) {
+        constexpr int D = decltype(dtag)::value;
+        return with_table_slice<D>(h, L, co ? 2 : 4, [&](auto hgtag, int ngroups, size_t lds_bytes) {
+            constexpr int HG = decltype(hgtag)::value;
+            auto by_query = [&](auto keyside) {
+                constexpr bool KEYSIDE = decltype(keyside)::value;
+                allow_big_lds(a2_bwd_query_kernel<D, HG, KEYSIDE>, lds_bytes);
+                hipLaunchKernelGGL((a2_bwd_query_kernel<D, HG, KEYSIDE>), dim3(walk_blocks(N, ngroups, 4, 2), ngroups), dim3(256), lds_bytes, st,
+                                   N, h, L, grad_out, q, index_q_offsets, k, index_k, table_q, table_k, rel_idx, grad_q, grad_k, grad_table_q,
+                                   grad_table_k);
+            };
+            if (co) {
+                allow_big_lds(a2_bwd_key_kernel<D, HG>, lds_bytes);
+                by_query(std::false_type{});
+                hipLaunchKernelGGL((a2_bwd_key_kernel<D, HG>), dim3(walk_blocks(NK, ngroups, 4, 2), ngroups), dim3(256), lds_bytes, st,
+                                   NK, h, L, grad_out, k, co, cp, table_k, rel_idx, grad_k, grad_table_k);
+            } else {
+                by_query(std::true_type{});
+            }
+        });
+    });
+    if (launched) check_launch();
 }
 
 void attention_step2_with_rel_pos_value_forward_cuda_launcher_v2(int N, int M, int h, int hdim, int n_max,
@@ -713,24 +630,18 @@ void attention_step2_with_rel_pos_value_forward_cuda_launcher_v2(int N, int M, i
     const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
     const hipStream_t st = ln.stream;
+    if (without_table_rows(ln, [&] { a4_fwd_global(st, N, M, h, hdim, attn, v, index0_offsets, index1, table, rel_idx, output); })) return;
     const int L = ln.opts.table_rows;
-    if (L <= 0) {
-        a4_fwd_global(st, N, M, h, hdim, attn, v, index0_offsets, index1, table, rel_idx, output);
-        check_launch();
-        return;
-    }
-    if (hdim == 16) P2_LAUNCH_HG(16, 1, {
-        allow_big_lds(a4_fwd_kernel<Dc, HGc>, lds_bytes);
-        hipLaunchKernelGGL((a4_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 8, 3), ngroups), dim3(512), lds_bytes, st,
-                           N, h, L, attn, v, index0_offsets, index1, table, rel_idx, output, ln.rows_in_order(N));
-    })
-    else if (hdim == 32) P2_LAUNCH_HG(32, 1, {
-        allow_big_lds(a4_fwd_kernel<Dc, HGc>, lds_bytes);
-        hipLaunchKernelGGL((a4_fwd_kernel<Dc, HGc>), dim3(persistent_blocks(N, ngroups, 8, 3), ngroups), dim3(512), lds_bytes, st,
-                           N, h, L, attn, v, index0_offsets, index1, table, rel_idx, output, ln.rows_in_order(N));
-    })
-    else { set_error("d != 16 and d != 32"); return; }
-    check_launch();
+    const bool launched = dispatch_d(hdim, [&](auto dtag) {
+        constexpr int D = decltype(dtag)::value;
+        return with_table_slice<D>(h, L, 1, [&](auto hgtag, int ngroups, size_t lds_bytes) {
+            constexpr int HG = decltype(hgtag)::value;
+            allow_big_lds(a4_fwd_kernel<D, HG>, lds_bytes);
+            hipLaunchKernelGGL((a4_fwd_kernel<D, HG>), dim3(walk_blocks(N, ngroups, 8, 3), ngroups), dim3(512), lds_bytes, st,
+                               N, h, L, attn, v, index0_offsets, index1, table, rel_idx, output, ln.rows_in_order(N));
+        });
+    });
+    if (launched) check_launch();
 }
 
 void attention_step2_with_rel_pos_value_backward_cuda_launcher_v2(int N, int M, int h, int hdim, int n_max,
@@ -742,81 +653,67 @@ void attention_step2_with_rel_pos_value_backward_cuda_launcher_v2(int N, int M, 
     const Launch ln = begin_launch();
     if (N <= 0 || M <= 0) return;
     const hipStream_t st = ln.stream;
-    const int L = ln.opts.table_rows;
-    if (L <= 0) {
-        a4_bwd_global(st, N, M, h, hdim, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
-        check_launch();
+    if (without_table_rows(ln, [&] {
+            a4_bwd_global(st, N, M, h, hdim, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
+        }))
         return;
-    }
+    const int L = ln.opts.table_rows;
     const int *co = ln.opts.csc_offsets, *cp = ln.opts.csc_pair, *cq = ln.opts.csc_query;
-    const int NK4 = ln.key_rows(N);
+    const int NK = ln.key_rows(N);
     if (co && hdim == 16 && L <= 80) {
         ForkJoin fj(st, fork_worthwhile((int64_t)M * h));  // grad_attn, grad_v and grad_table are independent
-        const int *kord = ln.rows_in_order(NK4);
-        hipLaunchKernelGGL(key_accum_kernel<16>, dim3(kord ? ordered_grid(NK4, 4) : div_up(NK4, 4), div_up(h, 4)), dim3(256), 0, fj.lane(2), NK4, h, co, cq, cp, attn, grad_out, grad_v, kord);
+        gather_accum_by_key(fj.lane(2), 16, NK, h, co, cq, cp, attn, grad_out, grad_v, ln.rows_in_order(NK));
         a4_bwd_mfma(ln, N, h, hdim, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_table, fj);
         check_launch();
         return;
     }
-#define P2_A4_BWD(D_)                                                                                                       \
-    P2_LAUNCH_HG(D_, 2, {                                                                                                   \
-        allow_big_lds(a4_bwd_query_kernel<Dc, HGc, false>, lds_bytes);                                                      \
-        allow_big_lds(a4_bwd_query_kernel<Dc, HGc, true>, lds_bytes);                                                       \
-        if (co) {                                                                                                           \
-            hipLaunchKernelGGL((a4_bwd_query_kernel<Dc, HGc, false>), dim3(persistent_blocks(N, ngroups), ngroups), dim3(256), \
-                               lds_bytes, st, N, h, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, \
-                               grad_v, grad_table);                                                                         \
-            hipLaunchKernelGGL(key_accum_kernel<Dc>, dim3(div_up(NK4, 4), div_up(h, 4)), dim3(256), 0, st, NK4, h, co, cq, cp, attn, grad_out, \
-                               grad_v, (const int *)nullptr);                                                                                     \
-        } else {                                                                                                            \
-            hipLaunchKernelGGL((a4_bwd_query_kernel<Dc, HGc, true>), dim3(persistent_blocks(N, ngroups), ngroups), dim3(256), \
-                               lds_bytes, st, N, h, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, \
-                               grad_v, grad_table);                                                                         \
-        }                                                                                                                   \
-    })
-    if (hdim == 16) { P2_A4_BWD(16) }
-    else if (hdim == 32) { P2_A4_BWD(32) }
-    else { set_error("d != 16 and d != 32"); return; }
-#undef P2_A4_BWD
-    check_launch();
+    // grad_v: by key through the CSC view (attention.hip's gather-accumulate, rows by index), or with atomics from the by-query kernel
+    const bool launched = dispatch_d(hdim, [&](auto dtag) {
+        constexpr int D = decltype(dtag)::value;
+        return with_table_slice<D>(h, L, 2, [&](auto hgtag, int ngroups, size_t lds_bytes) {
+            constexpr int HG = decltype(hgtag)::value;
+            auto by_query = [&](auto keyside) {
+                constexpr bool KEYSIDE = decltype(keyside)::value;
+                hipLaunchKernelGGL((a4_bwd_query_kernel<D, HG, KEYSIDE>), dim3(walk_blocks(N, ngroups, 4, 2), ngroups), dim3(256), lds_bytes, st,
+                                   N, h, L, grad_out, index0_offsets, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
+            };
+            allow_big_lds(a4_bwd_query_kernel<D, HG, false>, lds_bytes);
+            allow_big_lds(a4_bwd_query_kernel<D, HG, true>, lds_bytes);
+            if (co) {
+                by_query(std::false_type{});
+                gather_accum_by_key(st, D, NK, h, co, cq, cp, attn, grad_out, grad_v, nullptr);
+            } else {
+                by_query(std::true_type{});
+            }
+        });
+    });
+    if (launched) check_launch();
 }
 
 // ---- v1 forms ----
 void dot_prod_with_idx_forward_cuda_launcher(int N, int M, int h, int hdim, const float *q, const int *index,
                                              const float *table, const int *rel_idx, float *output) {
     (void)N;
-    const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    hipLaunchKernelGGL(dot_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, q, index, table, rel_idx, output);
-    check_launch();
+    launch_pair_heads(begin_launch().stream, dot_v1_fwd_kernel, M, h, hdim, q, index, table, rel_idx, output);
 }
 void dot_prod_with_idx_backward_cuda_launcher(int N, int M, int h, int hdim, const float *grad_out,
                                               const float *q, const int *index, const float *table,
                                               const int *rel_idx, float *grad_q, float *grad_table) {
     (void)N;
-    const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    hipLaunchKernelGGL(dot_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, grad_out, q, index, table, rel_idx, grad_q, grad_table);
-    check_launch();
+    launch_pair_heads(begin_launch().stream, dot_v1_bwd_kernel, M, h, hdim, grad_out, q, index, table, rel_idx, grad_q, grad_table);
 }
 void attention_step2_with_rel_pos_value_forward_cuda_launcher(int N, int M, int h, int hdim, const float *attn,
                                                               const float *v, const int *index0, const int *index1,
                                                               const float *table, const int *rel_idx, float *output) {
     (void)N;
-    const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    hipLaunchKernelGGL(av_v1_fwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, attn, v, index0, index1, table, rel_idx, output);
-    check_launch();
+    launch_pair_heads(begin_launch().stream, av_v1_fwd_kernel, M, h, hdim, attn, v, index0, index1, table, rel_idx, output);
 }
 void attention_step2_with_rel_pos_value_backward_cuda_launcher(int N, int M, int h, int hdim, const float *grad_out,
                                                                const int *index0, const int *index1, const float *attn,
                                                                const float *v, const float *table, const int *rel_idx,
                                                                float *grad_attn, float *grad_v, float *grad_table) {
     (void)N;
-    const hipStream_t st = begin_launch().stream;
-    if (M <= 0) return;
-    hipLaunchKernelGGL(av_v1_bwd_kernel, dim3(div_up64((int64_t)M * h, 256)), dim3(256), 0, st, M, h, hdim, grad_out, index0, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
-    check_launch();
+    launch_pair_heads(begin_launch().stream, av_v1_bwd_kernel, M, h, hdim, grad_out, index0, index1, attn, v, table, rel_idx, grad_attn, grad_v, grad_table);
 }
 
 // The bucketed "v2" bias (relative_pos_encoding_cuda_kernel_v2.cu:9-243) computes the same function

@@ -559,25 +559,10 @@ __global__ __launch_bounds__(512, 4) void wattn_bwd_key_kernel(int NK, int h, in
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------
-static int walk_blocks(int rows, int groups, int waves_per_block, int per_cu) {
-    int want = div_up(rows, waves_per_block);
-    const int cus = usable_cus();
-    int cap = cus * per_cu;
-    if (groups > 1) cap = max(cus * per_cu / groups, cus / 2);
-    return max(1, min(want, cap));
-}
-
-template <typename F>
-static void with_heads(int h, F f) {
-    if (h >= 3) f(std::integral_constant<int, 3>{});
-    else if (h == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 1>{});
-}
-
 template <int TA>
 static void launch_table_grad(const Launch &ln, int N, int h, int L, const float *w, const float *X, const int *offs, const int *pair_map,
                               const int *rel, float *grad_table, hipStream_t st) {
-    with_heads(h, [&](auto tag) {
+    with_head_group(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
         const int groups = div_up(h, HG);
         using G = TableGeo<HG, TA>;
@@ -594,7 +579,7 @@ bool a2_bwd_mfma(const Launch &ln, int N, int M, int h, int hdim, int L, const f
     const int NK = ln.key_rows(N);
     if (hdim != 16 || co == nullptr || L < 1 || L > 80) return false;
     ForkJoin fj(ln.stream, fork_worthwhile((int64_t)M * h));  // grad_q, grad_k and the two table gradients are independent
-    with_heads(h, [&](auto tag) {
+    with_head_group(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
         const int groups = div_up(h, HG);
         const size_t lds = (size_t)HG * 3 * L * 16 * sizeof(float);
@@ -616,7 +601,7 @@ bool a2_bwd_mfma(const Launch &ln, int N, int M, int h, int hdim, int L, const f
 bool a4_bwd_mfma(const Launch &ln, int N, int h, int hdim, int L, const float *go, const int *offs, const int *idx1, const float *attn,
                  const float *v, const float *table, const int *rel, float *grad_attn, float *grad_table, ForkJoin &fj) {
     if (hdim != 16 || L < 1 || L > 80) return false;
-    with_heads(h, [&](auto tag) {
+    with_head_group(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
         const int groups = div_up(h, HG);
         const size_t lds = (size_t)HG * 3 * L * 16 * sizeof(float);
@@ -637,7 +622,7 @@ bool wattn_bwd(const Launch &ln, int N, int M, int h, int hdim, int L, const flo
     const int NK = ln.key_rows(N);
     if (hdim != 16 || co == nullptr || L < 1 || L > 80) return false;
     const hipStream_t st = ln.stream;
-    with_heads(h, [&](auto tag) {
+    with_head_group(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
         const int groups = div_up(h, HG);
         const size_t lds2 = (size_t)2 * HG * 3 * L * 16 * sizeof(float);
@@ -647,7 +632,7 @@ bool wattn_bwd(const Launch &ln, int N, int M, int h, int hdim, int L, const flo
     });
     // everything below only reads grad_logit: the key walk and the three table gradients are independent
     ForkJoin fj(st, fork_worthwhile((int64_t)M * h));
-    with_heads(h, [&](auto tag) {
+    with_head_group(h, [&](auto tag) {
         constexpr int HG = decltype(tag)::value;
         const int groups = div_up(h, HG);
         const size_t lds1 = (size_t)HG * 3 * L * 16 * sizeof(float);

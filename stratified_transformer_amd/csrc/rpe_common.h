@@ -1,5 +1,5 @@
-// Shared device helpers of the rel-pos kernels (rpe.hip, rpe_bwd_mfma.hip): LDS table images and the
-// wave-per-row walker prologue.
+// Shared pieces of the rel-pos kernels (rpe.hip, rpe_bwd_mfma.hip): LDS table images, the wave-per-row
+// walker prologue, and on the host the head-group dispatcher and the persistent grid's size.
 #pragma once
 #include "common.h"
 
@@ -53,9 +53,9 @@ __device__ __forceinline__ void tadd(float *lds, int L, int t, int r0, int r1, i
     float *a0 = lds + (((size_t)t * 3 + 0) * L + r0) * D + 4 * c;
     float *a1 = lds + (((size_t)t * 3 + 1) * L + r1) * D + 4 * c;
     float *a2 = lds + (((size_t)t * 3 + 2) * L + r2) * D + 4 * c;
-    atomicAdd(a0 + 0, v.x); atomicAdd(a0 + 1, v.y); atomicAdd(a0 + 2, v.z); atomicAdd(a0 + 3, v.w);
-    atomicAdd(a1 + 0, v.x); atomicAdd(a1 + 1, v.y); atomicAdd(a1 + 2, v.z); atomicAdd(a1 + 3, v.w);
-    atomicAdd(a2 + 0, v.x); atomicAdd(a2 + 1, v.y); atomicAdd(a2 + 2, v.z); atomicAdd(a2 + 3, v.w);
+    atomic_add4(a0, v);
+    atomic_add4(a1, v);
+    atomic_add4(a2, v);
 }
 __device__ __forceinline__ int clampr(int r, int L) { return min(max(r, 0), L - 1); }
 
@@ -81,6 +81,23 @@ __device__ __forceinline__ PairIds load_pair_ids(const int *__restrict__ idx1, c
     r.q1 = rel[m * 3 + 1];
     r.q2 = rel[m * 3 + 2];
     return r;
+}
+
+// ---- host side ----
+// f(std::integral_constant<int, HG>{}) for the heads a workgroup takes: min(heads, 3)
+template <typename F>
+inline void with_head_group(int heads, F f) {
+    if (heads >= 3) f(std::integral_constant<int, 3>{});
+    else if (heads == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+}
+// grid.x of a persistent walker.  waves_per_block: rows a workgroup handles at a time; per_cu: resident workgroups per CU (LDS /
+// register budget); groups: head groups on grid.y, which share the CUs
+inline int walk_blocks(int rows, int groups, int waves_per_block, int per_cu) {
+    const int want = div_up(rows, waves_per_block), cus = usable_cus();
+    int cap = cus * per_cu;
+    if (groups > 1) cap = max(cus * per_cu / groups, cus / 2);
+    return max(1, min(want, cap));
 }
 
 // rpe_fallback.hip: the rel-pos operators without a table length (global-memory tables, the reference's atomics)

@@ -30,7 +30,7 @@
 // Backward layout: elementwise.  A workgroup takes the same tiles; a lane takes 16 bytes of logits (4 fp32 or 8 half elements), finds
 // the row of each element (a 32-bit division inside the tile), reads that row's target and stat (neighbouring lanes share the cache
 // lines), and stores 16 bytes of gradient; the 3 N shift elements follow in the same launch, one element a lane.
-#include "common.h"
+#include "row_types.h"
 
 namespace p2 {
 namespace {
@@ -43,16 +43,6 @@ constexpr int SL_BINS = 3 * SL_MAX_C + 2;
 
 inline __host__ __device__ int tile_rows_of(int c) { return c <= 32 ? 256 : 128; }
 
-__device__ __forceinline__ float widen16(unsigned v, int rt) {
-    return rt == POINTOPS2_ROWS_F16 ? (float)__builtin_bit_cast(_Float16, (unsigned short)v) : __uint_as_float(v << 16);
-}
-__device__ __forceinline__ unsigned narrow16(float f, int rt) {
-    if (rt == POINTOPS2_ROWS_F16) return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f);  // nearest even
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // NaN stays NaN
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;                   // nearest even
-}
-__device__ __forceinline__ int elem_bytes(int rt) { return rt == POINTOPS2_ROWS_F32 ? 4 : 2; }
 __device__ __forceinline__ float load_elem(const void *__restrict__ base, size_t e, int rt) {
     return rt == POINTOPS2_ROWS_F32 ? reinterpret_cast<const float *>(base)[e] : widen16(reinterpret_cast<const unsigned short *>(base)[e], rt);
 }
@@ -75,7 +65,7 @@ __device__ __forceinline__ uint4 pack_piece(const float *v, int rt) {
                       narrow16(v[4], rt) | (narrow16(v[5], rt) << 16), narrow16(v[6], rt) | (narrow16(v[7], rt) << 16));
 }
 __device__ __forceinline__ const uint4 *piece_ptr(const void *base, size_t first_elem, int rt) {
-    return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(base) + first_elem * elem_bytes(rt));
+    return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(base) + first_elem * row_elem_bytes(rt));
 }
 
 // the rows of a launch in tiles of tile_rows: tile t of workgroup b = b, b + gridDim.x, ...
@@ -266,12 +256,11 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_bwd_kernel(int n, int c, 
     }
 }
 
-bool row_type_ok(int t) { return t == POINTOPS2_ROWS_F32 || t == POINTOPS2_ROWS_F16 || t == POINTOPS2_ROWS_BF16; }
 // nullptr when the arguments are in range
 const char *seg_loss_bad_args(int n, int c, int logits_type, int shift_type, float eps, const void *shift_pred, const float *shift) {
     if (n < 0) return "seg_loss: negative row count";
     if (c < 1 || c > SL_MAX_C) return "seg_loss: c must be in [1, 64]";
-    if (!row_type_ok(logits_type) || !row_type_ok(shift_type)) return "seg_loss: row types must be POINTOPS2_ROWS_F32, _F16 or _BF16";
+    if (!known_row_type(logits_type) || !known_row_type(shift_type)) return "seg_loss: row types must be POINTOPS2_ROWS_F32, _F16 or _BF16";
     if (!(eps >= 0.0f && eps < 1.0f)) return "seg_loss: smooth_eps must be in [0, 1)";
     if (eps > 0.0f && c < 2) return "seg_loss: smooth_eps > 0 needs c >= 2";
     if ((shift_pred == nullptr) != (shift == nullptr)) return "seg_loss: shift_pred and shift are given together or not at all";

@@ -3,7 +3,8 @@ with layers.POOLED_TRANSITION - against the float64 oracle of tests/grouped_max_
 
 Bars.  Forward of the operator: bit-identical (the maximum is a selection).  Backward of the operator, per element:
 |got - want64| <= (terms - 1) * 2^-24 * sum|term| + ulp(want64), the last term 0 for f32 and half an ulp of the row type for f16 / bf16
-(fp32 accumulation in a fixed order, one rounding).  Layer, fp32: err_on <= 4 * err_off + 2^-24 * max|.|, both errors against float64 (the
+(fp32 accumulation in a fixed order, one rounding; the rounding itself - csrc/row_types.h, shared by every operator on f16 / bf16 rows -
+is pinned bit for bit at its ties, at the overflow to inf and on a NaN by test_backward_rounds_once_to_nearest_even).  Layer, fp32: err_on <= 4 * err_off + 2^-24 * max|.|, both errors against float64 (the
 two paths are fp32 dot products of the same length in another order); gradients after the upstream gradient is zeroed, the same way
 on every side, where the float64 top-two gap of a group is below delta = 1e-4 * max|y| (a near-tie lets the two paths route a gradient to
 different rows), at most 0.5 % of the entries.  Layer, autocast(f16): forward within one f16 ulp of the larger magnitude (both round an
@@ -176,6 +177,52 @@ def test_non_finite_rows(P, name, c):
     assert np.array_equal(arg.cpu().numpy(), want_arg)
     want_g, _, _ = O.backward(go_h.double().numpy(), idx_h, want_arg, 12)
     assert np.array_equal(feat.grad.double().cpu().numpy(), want_g)              # grid values, at most a few terms: exact
+
+
+# one rounding of an fp32 sum to the row type, nearest even: (bits of a, bits of b, bits of round(a + b)); None: a NaN
+NAN = {"bf16": 0x7fc0, "f16": 0x7e00}
+ONE = {"bf16": 0x3f80, "f16": 0x3c00}
+ROUNDING = {
+    "bf16": [(0x3f80, 0x3b80, 0x3f80),   # 1 + 2^-8: a tie, down to the even 1
+             (0x3f81, 0x3b80, 0x3f82),   # (1 + 2^-7) + 2^-8: a tie, up to the even 1 + 2^-6
+             (0x7f7f, 0x7b00, 0x7f80),   # the largest finite value + half its ulp: inf
+             (0xbf80, 0xbb80, 0xbf80),   # the first tie, negative
+             (NAN["bf16"], ONE["bf16"], None)],
+    "f16": [(0x3c00, 0x1000, 0x3c00),    # 1 + 2^-11: a tie, down to the even 1
+            (0x3c01, 0x1000, 0x3c02),    # (1 + 2^-10) + 2^-11: a tie, up to the even 1 + 2^-9
+            (0x7bff, 0x4c00, 0x7c00),    # 65504 + 16: inf
+            (0xbc00, 0x9000, 0xbc00),
+            (NAN["f16"], ONE["f16"], None)],
+}
+
+
+@pytest.mark.parametrize("name", list(ROUNDING))
+@pytest.mark.parametrize("c", [8, 5])
+def test_backward_rounds_once_to_nearest_even(P, name, c):
+    """k = 1 and both queries on source row 0: the backward is round(grad_out[0] + grad_out[1]), one rounding of an fp32 sum to the row
+    type - at its ties, at the overflow to inf and on a NaN; c = 8: the 16-byte chunk kernel, c = 5: one thread per element"""
+    dtype = DTYPES[name]
+    rows = ROUNDING[name] + ROUNDING[name][:c - 5]
+    def as_rows(col):
+        raw = np.array([[r[col] for r in rows]], np.uint16).view(np.int16)
+        return torch.from_numpy(raw).view(dtype)
+    go_h = torch.cat([as_rows(0), as_rows(1)])
+    want = [r[2] for r in rows]
+    by_torch = (go_h[0].float() + go_h[1].float()).to(dtype)                     # the table agrees with torch on the CPU: fp32 add, one rounding
+    for ch, w in enumerate(want):
+        assert bool(torch.isnan(by_torch[ch])) if w is None else int(_bits(by_torch)[ch]) & 0xffff == w, ch
+    feat = torch.ones(1, c, dtype=dtype, device="cuda").requires_grad_(True)
+    out = P.grouped_max(feat, torch.zeros((2, 1), dtype=torch.int32, device="cuda"))
+    out.backward(go_h.cuda())
+    torch.cuda.synchronize()
+    assert feat.grad.dtype == dtype and tuple(feat.grad.shape) == (1, c)
+    got = _bits(feat.grad.cpu())[0].numpy().view(np.uint16)
+    print(f"grouped_max rounding {name} c={c}: got {[hex(int(g)) for g in got]}")
+    for ch, w in enumerate(want):
+        if w is None:
+            assert bool(torch.isnan(feat.grad[0, ch])), ch
+        else:
+            assert int(got[ch]) == w, (ch, hex(int(got[ch])), hex(w))
 
 
 @pytest.mark.parametrize("idx_dtype", [torch.int32, torch.int64])
