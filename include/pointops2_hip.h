@@ -472,6 +472,41 @@ void residual_norm_backward_launcher(int n, int c, int y_type, int o_type, const
                                      const float *stat, const float *s, const float *gamma, float *grad_x, void *grad_y, float *partials,
                                      int partial_rows, float *grad_gamma, float *grad_beta);
 
+/* ---- BatchNorm1d over the rows + activation (+ residual add): the per-row glue of the stem and the heads
+ * (model/stratified_transformer.py:358, :367-368 with :391, :426-443) ----
+ *   stats:    per channel over the n rows, mean = sum x / n and M2 = sum (x - mean)^2, by shifted sums per lane and Chan's merge of
+ *             (count, mean, M2) in a fixed tree - never E[x^2] - mean^2; stat [2,c] = (mean, rstd = 1 / sqrt(M2 / n + eps)).  Workgroup b
+ *             writes its rows' moments to partials[b] (fp32 [partial_rows, 3, c], a workspace, no zero-fill; the grid is at most
+ *             partial_rows workgroups); the kernel that merges them also updates the running statistics where they are not NULL:
+ *             running_mean = (1 - momentum) * running_mean + momentum * mean, running_var likewise with M2 / (n - 1) (torch's rule).
+ *   forward:  pre = ((x - mean[ch]) * rstd[ch]) * gamma[ch] + beta[ch], o = act(pre) (+ residual, NULL: none).  mean / scale [c]: the two
+ *             rows of stat, or with scale_is_var != 0 a mean and a variance (eval mode: the running statistics; rstd = 1 / sqrt(scale +
+ *             eps) is taken per lane); stat_out [2,c] (NULL: not wanted) receives (mean, rstd) as used.  o [n,c] is FULLY WRITTEN.
+ *             act: POINTOPS2_ACT_NONE, _RELU (pre <= 0 ? 0 : pre), _LEAKY_RELU (pre > 0 ? pre : pre * slope) or _TANH.
+ *   backward: xhat = (x - mean) * rstd and pre are recomputed from x and stat; g = grad_o * act'(pre) (tanh: 1 - tanh(pre)^2);
+ *             grad_gamma[ch] = sum_n g * xhat, grad_beta[ch] = sum_n g: computed when partials is not NULL (fp32 [partial_rows, 2, c], as
+ *             above), without float atomics; grad_x (NULL: not wanted; FULLY WRITTEN) = (gamma * rstd) * ((g - grad_beta / n) - xhat *
+ *             (grad_gamma / n)) with training != 0 - it reads grad_gamma / grad_beta, which this call or an earlier one computed -
+ *             and (g * gamma) * rstd with training == 0 (the statistics did not depend on x).
+ * x, o, grad_o, grad_x [n,c] have x_type and residual [n,c] has r_type, each POINTOPS2_ROWS_F32, _F16 or _BF16, widened exactly,
+ * arithmetic in fp32 without fused operations, one rounding to the row type.  gamma, beta, mean, scale, the running statistics and the
+ * parameter gradients [c], stat [2,c]: fp32.  1 <= c <= 1024, the row types, act and partial_rows in [1, 1024] are checked: otherwise
+ * an error is recorded and nothing is launched; n = 0 is a no-op; offsets are 64-bit.  c % 4 == 0 with operands aligned for 16-byte
+ * (fp32) / 8-byte (half) accesses takes four channels per lane, anything else one channel per lane: same results.  Bitwise
+ * reproducible on one device.  A NaN or Inf stays in its channel. */
+#define POINTOPS2_ACT_NONE       0
+#define POINTOPS2_ACT_RELU       1
+#define POINTOPS2_ACT_LEAKY_RELU 2
+#define POINTOPS2_ACT_TANH       3
+void batch_norm_act_stats_launcher(int n, int c, int x_type, const void *x, float *partials, int partial_rows, float eps, float momentum,
+                                   float *running_mean, float *running_var, float *stat);
+void batch_norm_act_forward_launcher(int n, int c, int x_type, int r_type, int act, float slope, const void *x, const float *mean,
+                                     const float *scale, int scale_is_var, float eps, const float *gamma, const float *beta,
+                                     const void *residual, void *o, float *stat_out);
+void batch_norm_act_backward_launcher(int n, int c, int x_type, int act, float slope, int training, const void *x, const void *grad_o,
+                                      const float *stat, const float *gamma, const float *beta, float *partials, int partial_rows,
+                                      float *grad_gamma, float *grad_beta, void *grad_x);
+
 /* ---- the loss tail of a segmentation training step in one pass: cross-entropy on the class logits, L1 on the shift head, their
  * weighted sum and the per-class IoU counts (tool/train.py:336-362, train_backup.py:403, util/common_util.py:180-185) ----
  * Row n is VALID when 0 <= target[n] < c and target[n] != ignore_index; any other label is never used as an index.

@@ -102,6 +102,9 @@ SIGNATURES = {
     "grouped_max_backward_launcher": [I, I, I, I, I, P, P, P, P, P],
     "residual_norm_forward_launcher": [I, I, I, I, P, P, P, P, P, F, P, P, P],
     "residual_norm_backward_launcher": [I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, P],
+    "batch_norm_act_stats_launcher": [I, I, I, P, P, I, F, F, P, P, P],
+    "batch_norm_act_forward_launcher": [I, I, I, I, I, F, P, P, P, I, F, P, P, P, P, P],
+    "batch_norm_act_backward_launcher": [I, I, I, I, F, I, P, P, P, P, P, P, I, P, P, P],
     "seg_loss_forward_launcher": [I, I, I, I, P, P, P, P, Q, F, F, P, P, I, P, P, P],
     "seg_loss_backward_launcher": [I, I, I, I, P, P, P, P, P, P, P, Q, F, F, P, P],
     "pointops2_dbscan_keys_launcher": [I, I, P, P, D, D, D, D, I, I, I, P],
@@ -141,6 +144,8 @@ RESULTS = {
 CELL_FWD = {"error": -1, "none": 0, "mfma64": 1, "mfma80": 2, "valu80": 3, "valu160": 4}
 # storage type of the rows of a packed qkv (POINTOPS2_ROWS_*): cell_attention_qkv_*_launcher, grouped_max_*_launcher
 ROW_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+# activation of batch_norm_act_*_launcher (POINTOPS2_ACT_*)
+ACTIVATIONS = {"none": 0, "relu": 1, "leaky_relu": 2, "tanh": 3}
 
 
 def cell_forward_variant(plan, h, L, bf16=False, hdim=16):

@@ -40,6 +40,9 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
     model file to fused_block_forward / swin_fused_block_forward - DropPath, residual add, LayerNorm and the cast in front of the next
     Linear as one pass of pointops.residual_norm (csrc/rownorm.hip) at both residual sites; the four GEMMs and GELU stay with torch.
 
+  * The batch norms of the stem and the heads (off by default): `fuse_batch_norms(model)` binds, per instance, forwards that run every
+    BatchNorm1d + activation (+ the ResBlock's shortcut add) as one pointops.batch_norm_act call (csrc/batchnorm.hip).
+
 Numbers: the same sums in another order (tests/test_hip_parity.py::test_installed_fast_layers_against_the_reference_layer:
 output and every parameter gradient of a depth-2 BasicLayer with TransitionDown against the reference's own run, <= 1e-3).
 """
@@ -607,6 +610,165 @@ def install_fused_blocks(module=None):
         swin = getattr(m, "__name__", "").endswith("swin3d_transformer")
         done += patch_block_classes(None if swin else blk, blk if swin else None)
     return done
+
+
+# ---- the batch norms of the stem and the heads on csrc/batchnorm.hip (fuse_batch_norms; off by default) ----
+# Per INSTANCE, not per class: the sites are plain nn.Sequential containers and blocks recognised by their attributes, so a fused
+# `forward` is bound in the instance's __dict__ (no submodule, parameter or buffer is added, replaced or renamed: state_dict() keeps
+# its keys, copy.deepcopy re-binds the method to the copy) and unfuse_batch_norms deletes it again.  Whether a site runs fused is decided
+# at every call; where it does not, the site's own modules run as they are and yield torch's bits.
+def _bn_of(m):
+    """the nn.BatchNorm1d a child is or holds as `.batch_norm` (FastBatchNorm1d); nn.SyncBatchNorm is not one"""
+    if isinstance(m, torch.nn.BatchNorm1d):
+        return m
+    inner = getattr(m, "batch_norm", None)
+    return inner if isinstance(inner, torch.nn.BatchNorm1d) else None
+
+
+def _act_of(m):
+    """(act, negative_slope) of batch_norm_act for an activation module, None for a module the fused pass does not know"""
+    if type(m) is torch.nn.ReLU:
+        return "relu", 0.0
+    if type(m) is torch.nn.LeakyReLU:
+        return "leaky_relu", float(m.negative_slope)
+    if type(m) is torch.nn.Tanh:
+        return "tanh", 0.0
+    return None
+
+
+def _seq_pairs(seq):
+    """{index of a norm child: (its BatchNorm1d, act, children the pair spans)}: a norm directly followed by a known activation, or by nothing"""
+    mods, pairs = list(seq), {}
+    for i, m in enumerate(mods):
+        bn = _bn_of(m)
+        if bn is None:
+            continue
+        act = ("none", 0.0) if i + 1 == len(mods) else _act_of(mods[i + 1])
+        if act is not None:
+            pairs[i] = (bn, act, 1 if i + 1 == len(mods) else 2)
+    return pairs
+
+
+_ROW_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _bn_call(bn, x, act, residual=None):
+    """P.batch_norm_act for the module `bn` on x, with the module's own bookkeeping -> (o, whether the residual went in); None: the
+    conditions of the fused pass do not hold at this call"""
+    if not (getattr(x, "is_cuda", False) and x.dim() == 2 and x.dtype in _ROW_DTYPES and 1 <= x.shape[1] <= 1024
+            and x.shape[1] == bn.num_features):
+        return None
+    if not (bn.affine and bn.momentum is not None and bn.weight.dtype == torch.float32 and bn.bias.dtype == torch.float32
+            and bn.weight.device == x.device):
+        return None
+    if residual is not None and not (getattr(residual, "is_cuda", False) and residual.device == x.device and residual.dtype in _ROW_DTYPES
+                                     and residual.shape == x.shape and residual.is_contiguous()):
+        residual = None
+    tracked = bn.running_mean is not None and bn.running_var is not None
+    if bn.training and tracked and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    o = P.batch_norm_act(x.contiguous(), bn.weight, bn.bias, bn.running_mean if tracked else None, bn.running_var if tracked else None,
+                         bn.training or not tracked, bn.momentum, bn.eps, act[0], act[1], residual)
+    return o, residual is not None
+
+
+def _run_sequential(seq, x, make_residual=None):
+    """nn.Sequential.forward with every (norm, activation) pair as one batch_norm_act call.  make_residual() yields what the caller adds to
+    the result: it is called once, behind every child in front of the pair that ends the container - that pair then adds it - or
+    behind the last child -> (result, the residual, whether it was added)"""
+    mods, pairs = list(seq), _seq_pairs(seq)
+    i, residual, added = 0, None, False
+    while i < len(mods):
+        if i in pairs:
+            bn, act, span = pairs[i]
+            if make_residual is not None and i + span == len(mods):
+                residual = make_residual()
+                make_residual = None
+            out = _bn_call(bn, x, act, residual)
+            if out is not None:
+                x, added = out
+                i += span
+                continue
+        x = mods[i](x)
+        i += 1
+    if make_residual is not None:
+        residual = make_residual()
+    return x, residual, added
+
+
+def fused_sequential_forward(self, input):
+    return _run_sequential(self, input)[0]
+
+
+def fused_simple_block_forward(self, feats, xyz, batch, neighbor_idx):
+    """KPConvSimpleBlock.forward (model/stratified_transformer.py:351-359), same arguments, same result: `activation(bn(.))` in one call"""
+    feats = self.kpconv(xyz, xyz, neighbor_idx, feats)
+    bn, act = _bn_of(self.bn), _act_of(self.activation)
+    out = _bn_call(bn, feats, act) if bn is not None and act is not None else None
+    return out[0] if out is not None else self.activation(self.bn(feats))
+
+
+def fused_res_block_forward(self, feats, xyz, batch, neighbor_idx):
+    """KPConvResBlock.forward (:380-392), same arguments, same result: unary_1's and unary_2's norm + activation in one call each, the
+    second with the `feats += shortcut` of :391"""
+    if not (torch.is_tensor(feats) and feats.is_cuda):
+        return type(self).forward(self, feats, xyz, batch, neighbor_idx)
+    shortcut = feats
+    feats = _run_sequential(self.unary_1, feats)[0]
+    feats = self.kpconv(xyz, xyz, neighbor_idx, feats)
+    # (shortcut_op runs behind unary_2's Linear, not behind its activation as in :389-390: the norm and the activation draw nothing)
+    feats, shortcut, added = _run_sequential(self.unary_2, feats, lambda: self.shortcut_op(shortcut))
+    if not added:
+        feats += shortcut
+    return feats
+
+
+_BN_FORWARDS = (fused_sequential_forward, fused_simple_block_forward, fused_res_block_forward)
+
+
+def _bn_fused(m):
+    f = m.__dict__.get("forward")
+    return f is not None and getattr(f, "__func__", None) in _BN_FORWARDS
+
+
+def fuse_batch_norms(model):
+    """Binds fused forwards on the batch-norm sites of `model` (any nn.Module; the reference's Stratified: stem_layer, classifier,
+    regressor) and returns the names of the sites, in module order:
+      * an nn.Sequential in which a BatchNorm1d - or a module holding one as `.batch_norm` - is directly followed by ReLU, LeakyReLU
+        or Tanh, or ends the container;
+      * a module with `kpconv`, `bn`, `activation` and no `unary_1` (KPConvSimpleBlock);
+      * a module with `unary_1`, `unary_2`, `kpconv`, `shortcut_op` (KPConvResBlock; reported as its two sites `<name>.unary_1`, `<name>.unary_2`).
+    Each pair runs as one pointops.batch_norm_act call (csrc/batchnorm.hip) when, at that call, the rows are a 2-D f32 / f16 / bf16 GPU
+    tensor of C <= 1024 channels and the norm has affine f32 parameters and a momentum; otherwise the site's modules run as they are.
+    Train / eval mode, the running statistics and num_batches_tracked behave as the modules' own.  unfuse_batch_norms(model) undoes it."""
+    import types
+    sites, inner = [], set()
+    for name, m in model.named_modules():
+        if id(m) in inner:
+            continue
+        res = all(hasattr(m, a) for a in ("unary_1", "unary_2", "kpconv", "shortcut_op"))
+        if res and all(isinstance(u, torch.nn.Sequential) and _seq_pairs(u) for u in (m.unary_1, m.unary_2)):
+            fn, names = fused_res_block_forward, [f"{name}.unary_1" if name else "unary_1", f"{name}.unary_2" if name else "unary_2"]
+            inner.update((id(m.unary_1), id(m.unary_2)))
+        elif (not hasattr(m, "unary_1") and all(hasattr(m, a) for a in ("kpconv", "bn", "activation")) and _bn_of(m.bn) is not None
+              and _act_of(m.activation) is not None):
+            fn, names = fused_simple_block_forward, [name]
+        elif isinstance(m, torch.nn.Sequential) and _seq_pairs(m):
+            fn, names = fused_sequential_forward, [name]
+        else:
+            continue
+        if "forward" in m.__dict__ and not _bn_fused(m):
+            continue  # someone else's instance-level forward: left alone
+        m.__dict__["forward"] = types.MethodType(fn, m)
+        sites += names
+    return sites
+
+
+def unfuse_batch_norms(model):
+    """Removes what fuse_batch_norms bound: every module of `model` runs its class's forward again"""
+    for m in model.modules():
+        if _bn_fused(m):
+            del m.__dict__["forward"]
 
 
 def uninstall_fast_layers():

@@ -1103,6 +1103,126 @@ def residual_norm(x, y, row_scale, weight, bias, eps=1e-5, out_dtype=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# BatchNorm1d over point rows + activation + residual add: the glue of the stem and the heads (csrc/batchnorm.hip)
+# ---------------------------------------------------------------------------------------------
+def _batch_norm_partials(n, c, width, like):
+    rows = min(pointops_cuda.BATCH_NORM_PARTIAL_ROWS, max(1, (n + 3) // 4))
+    return torch.empty((rows, width, c), dtype=torch.float32, device=like.device)
+
+
+class BatchNormAct(Function):
+    """o = act(batch_norm(x)) (+ residual): the statistics in one pass over x plus a small merge kernel (which also updates the running
+    statistics), the rows in a second pass; backward: the two parameter sums (pass + merge kernel), then dx.  Saves x and the [2, C]
+    statistics only - neither the normalised rows nor o.  No float atomics: bitwise reproducible.  `need`: x, weight or bias wants a
+    gradient (needs_input_grad is set under no_grad too)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, running_mean, running_var, training, momentum, eps, act, negative_slope, need):
+        n, c = x.shape
+        o = torch.empty_like(x)
+        batch_stats = training or running_mean is None
+        stat = torch.empty((2, c), dtype=torch.float32, device=x.device) if (batch_stats or need) else None
+        if n > 0:
+            if batch_stats:
+                update = training and running_mean is not None
+                pointops_cuda.batch_norm_act_stats(n, c, x, _batch_norm_partials(n, c, 3, x), eps, momentum if update else 0.0,
+                                                   running_mean if update else None, running_var if update else None, stat)
+                pointops_cuda.batch_norm_act_forward(n, c, x, stat[0], stat[1], False, eps, weight, bias, act, negative_slope, residual, o, None)
+            else:
+                pointops_cuda.batch_norm_act_forward(n, c, x, running_mean, running_var, True, eps, weight, bias, act, negative_slope, residual, o,
+                                                     stat)
+        if need:
+            ctx.save_for_backward(x, stat, weight, bias)
+        ctx.args = (act, negative_slope, batch_stats)
+        ctx.r_dtype = residual.dtype if residual is not None else None
+        ctx.set_materialize_grads(False)
+        return o
+
+    @staticmethod
+    def backward(ctx, grad_o):
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        if grad_o is None:
+            return (None,) * 12
+        grad_r = grad_o.to(ctx.r_dtype) if need_r and ctx.r_dtype is not None else None
+        grad_x = grad_w = grad_b = None
+        if need_x or need_w or need_b:
+            x, stat, weight, bias = ctx.saved_tensors
+            act, negative_slope, batch_stats = ctx.args
+            n, c = x.shape
+            if n == 0:
+                grad_x, (grad_w, grad_b) = torch.empty_like(x), _zeros((2, c), x).unbind(0)
+            else:
+                params = need_w or need_b
+                sums = params or (need_x and batch_stats)  # with batch statistics dx reads the two sums
+                grad_w, grad_b = torch.empty((2, c), dtype=torch.float32, device=x.device).unbind(0) if sums else (None, None)
+                grad_x = torch.empty_like(x) if need_x else None
+                pointops_cuda.batch_norm_act_backward(n, c, x, grad_o.contiguous(), stat, weight, bias, act, negative_slope, batch_stats,
+                                                      _batch_norm_partials(n, c, 2, x) if sums else None, grad_w, grad_b, grad_x)
+        return (grad_x if need_x else None, grad_w if need_w else None, grad_b if need_b else None, grad_r) + (None,) * 8
+
+
+def batch_norm_act(x, weight, bias, running_mean=None, running_var=None, training=True, momentum=0.1, eps=1e-5, act="none",
+                   negative_slope=0.01, residual=None):
+    """o = act(F.batch_norm(x, running_mean, running_var, weight, bias, training, momentum, eps)) (+ residual) -> o [n, c] of x's dtype, in
+    fused HIP passes (csrc/batchnorm.hip) instead of torch's statistics, normalise, activation and add kernels and the tensors between them.
+    x [n, c] f32, f16 or bf16 (what a Linear yields under autocast), contiguous; weight, bias [c] f32; running_mean / running_var [c] f32
+    or both None (batch statistics in both modes, no update); act: "none", "relu", "leaky_relu" (negative_slope) or "tanh"; residual
+    [n, c] f32, f16 or bf16 or None, added after the activation.  training: batch statistics, and the running statistics take torch's
+    update on the device (momentum; the unbiased variance); else the running statistics normalise.  All arithmetic in fp32; the
+    variance by shifted sums and Chan's merge, never E[x^2] - mean^2.  Differentiable w.r.t. x, weight, bias and residual.  The backward
+    launches only what a wanted gradient needs: the two parameter sums when weight or bias wants one - and, with batch statistics, also
+    when only x does, because dx reads both sums (freezing the parameters spares the sums in eval mode alone) -, dx when x wants one,
+    nothing for the residual.
+    1 <= c <= 1024; training with n == 1 raises ValueError as torch does; n == 0 gives an empty o."""
+    tensors = [("x", x), ("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var), ("residual", residual)]
+    for name, t in tensors[:3]:
+        if t is None:
+            raise ValueError(f"batch_norm_act: {name} is None (a BatchNorm1d with affine parameters is expected)")
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"batch_norm_act: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+    for name, t in tensors[1:]:
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"batch_norm_act: {name} is on {t.device}, x on {x.device}")
+    rows = (torch.float32, torch.float16, torch.bfloat16)
+    if x.dim() != 2:
+        raise ValueError(f"batch_norm_act: x must be [n, c], got {tuple(x.shape)}")
+    if x.dtype not in rows:
+        raise TypeError(f"batch_norm_act: x must be f32, f16 or bf16, got {x.dtype}")
+    n, c = x.shape
+    if not 1 <= c <= pointops_cuda.BATCH_NORM_MAX_C:
+        raise ValueError(f"batch_norm_act: c must be in [1, {pointops_cuda.BATCH_NORM_MAX_C}], got x {tuple(x.shape)}")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError(f"batch_norm_act: {'running_mean' if running_mean is None else 'running_var'} is None and the other is not: "
+                         "running_mean and running_var are given together or not at all")
+    for name, t in tensors[1:5]:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"batch_norm_act: {name} must be f32, got {t.dtype}")
+        if tuple(t.shape) != (c,):
+            raise ValueError(f"batch_norm_act: {name} must be [{c}], got {tuple(t.shape)}")
+    if residual is not None:
+        if residual.dtype not in rows:
+            raise TypeError(f"batch_norm_act: residual must be f32, f16 or bf16, got {residual.dtype}")
+        if tuple(residual.shape) != (n, c):
+            raise ValueError(f"batch_norm_act: residual must be [{n}, {c}] like x, got {tuple(residual.shape)}")
+    if act not in ("none", "relu", "leaky_relu", "tanh"):
+        raise ValueError(f"batch_norm_act: act must be 'none', 'relu', 'leaky_relu' or 'tanh', got {act!r}")
+    training = bool(training)
+    if training and running_mean is not None and momentum is None:
+        raise ValueError("batch_norm_act: momentum is None (a cumulative average of the running statistics is not supported)")
+    for name, t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"batch_norm_act: {name} must be contiguous")
+    if training and n == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size((n, c))}")
+    need = torch.is_grad_enabled() and any(bool(t.requires_grad) for t in (x, weight, bias))
+    return BatchNormAct.apply(x, weight, bias, residual, running_mean, running_var, training, 0.0 if momentum is None else float(momentum),
+                              float(eps), act, float(negative_slope), need)
+
+
+# ---------------------------------------------------------------------------------------------
 # the loss tail of a training step: cross-entropy, L1 shift, weighted sum, IoU counts (csrc/seg_loss.hip)
 # ---------------------------------------------------------------------------------------------
 class SegmentationLoss(Function):

@@ -190,6 +190,94 @@ def residual_norm_backward(n, c, grad_o, grad_z, z, stat, row_scale, weight, gra
           ptr(grad_x), ptr(grad_y), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), opts=opts)
 
 
+# csrc/batchnorm.hip (no counterpart in the reference's launcher set: BatchNorm1d + activation + residual add of the stem and the heads)
+BATCH_NORM_MAX_C = 1024
+BATCH_NORM_PARTIAL_ROWS = 1024  # most workgroups of the two reductions: one row of `partials` each
+
+
+def _batch_norm_sizes(n, c):
+    n, c = int(n), int(c)
+    if n < 0:
+        raise ValueError(f"n: expected a row count >= 0, got {n}")
+    if not 1 <= c <= BATCH_NORM_MAX_C:
+        raise ValueError(f"c: expected 1 <= c <= {BATCH_NORM_MAX_C}, got {c}")
+    return n, c
+
+
+def _batch_norm_act(act):
+    if act not in _lib.ACTIVATIONS:
+        raise ValueError(f"act: expected one of {sorted(_lib.ACTIVATIONS)}, got {act!r}")
+    return _lib.ACTIVATIONS[act]
+
+
+def _batch_norm_partials(partials, width, c):
+    _chk((partials, F32, "partials"))
+    rows = int(partials.shape[0]) if partials.dim() == 3 else 0
+    if not 1 <= rows <= BATCH_NORM_PARTIAL_ROWS or tuple(partials.shape[1:]) != (width, c):
+        raise ValueError(f"partials: expected shape [1 <= rows <= {BATCH_NORM_PARTIAL_ROWS}, {width}, {c}], got {list(partials.shape)}")
+    return rows
+
+
+def batch_norm_act_stats(n, c, x, partials, eps, momentum, running_mean, running_var, stat, *, opts=None):
+    """stat [2,c] f32 = (mean, 1 / sqrt(biased variance + eps)) per channel <- x [n,c] f32 / f16 / bf16; running_mean / running_var [c] f32
+    (both or neither) take torch's momentum update on the device; partials: a [1 <= rows <= 1024, 3, c] f32 workspace"""
+    n, c = _batch_norm_sizes(n, c)
+    xt = _row_type(x, "x")
+    _chk((x, x.dtype, "x"), (stat, F32, "stat"))
+    _shaped(x, (n, c), "x"), _shaped(stat, (2, c), "stat")
+    rows = _batch_norm_partials(partials, 3, c)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError(f"{'running_mean' if running_mean is None else 'running_var'}: running_mean and running_var are given together or not at all")
+    _opt(running_mean, F32, (c,), "running_mean")
+    _opt(running_var, F32, (c,), "running_var")
+    _call("batch_norm_act_stats_launcher", x, n, c, xt, ptr(x), ptr(partials), rows, float(eps), float(momentum), ptr(running_mean),
+          ptr(running_var), ptr(stat), opts=opts)
+
+
+def batch_norm_act_forward(n, c, x, mean, scale, scale_is_var, eps, weight, bias, act, negative_slope, residual, o, stat_out, *, opts=None):
+    """o [n,c] (x's dtype) = act(((x - mean) * rstd) * weight + bias) (+ residual [n,c] f32 / f16 / bf16 or None) <- x [n,c] f32 / f16 / bf16,
+    mean / scale [c] f32 (scale: rstd, or the variance with scale_is_var), weight / bias [c] f32; stat_out [2,c] f32 or None receives
+    (mean, rstd) as used"""
+    n, c = _batch_norm_sizes(n, c)
+    code = _batch_norm_act(act)
+    xt = _row_type(x, "x")
+    _chk((x, x.dtype, "x"), (mean, F32, "mean"), (scale, F32, "scale"), (weight, F32, "weight"), (bias, F32, "bias"), (o, x.dtype, "o"))
+    _shaped(x, (n, c), "x"), _shaped(mean, (c,), "mean"), _shaped(scale, (c,), "scale"), _shaped(weight, (c,), "weight"), _shaped(bias, (c,), "bias")
+    _shaped(o, (n, c), "o")
+    rt = _row_type(residual, "residual") if residual is not None else _lib.ROW_TYPES[F32]
+    _opt(residual, None if residual is None else residual.dtype, (n, c), "residual")
+    _opt(stat_out, F32, (2, c), "stat_out")
+    _call("batch_norm_act_forward_launcher", x, n, c, xt, rt, code, float(negative_slope), ptr(x), ptr(mean), ptr(scale), int(bool(scale_is_var)),
+          float(eps), ptr(weight), ptr(bias), ptr(residual), ptr(o), ptr(stat_out), opts=opts)
+
+
+def batch_norm_act_backward(n, c, x, grad_o, stat, weight, bias, act, negative_slope, training, partials, grad_weight, grad_bias, grad_x, *,
+                            opts=None):
+    """grad_weight / grad_bias [c] f32 - computed when partials (a [1 <= rows <= 1024, 2, c] f32 workspace) is given - and grad_x [n,c]
+    (x's dtype; None: not wanted) <- x, grad_o [n,c] of one dtype, stat [2,c], weight, bias of the forward.  With `training` grad_x
+    reads grad_weight / grad_bias, so they are given even where partials is None (an earlier call computed them).  Every output is
+    fully written."""
+    n, c = _batch_norm_sizes(n, c)
+    code = _batch_norm_act(act)
+    xt = _row_type(x, "x")
+    _chk((x, x.dtype, "x"), (grad_o, x.dtype, "grad_o"), (stat, F32, "stat"), (weight, F32, "weight"), (bias, F32, "bias"))
+    _shaped(x, (n, c), "x"), _shaped(grad_o, (n, c), "grad_o"), _shaped(stat, (2, c), "stat"), _shaped(weight, (c,), "weight"), _shaped(bias, (c,), "bias")
+    _opt(grad_x, x.dtype, (n, c), "grad_x")
+    _opt(grad_weight, F32, (c,), "grad_weight")
+    _opt(grad_bias, F32, (c,), "grad_bias")
+    rows = 0
+    if partials is not None:
+        rows = _batch_norm_partials(partials, 2, c)
+    if partials is None and grad_x is None:
+        raise ValueError("partials: neither partials nor grad_x is given: nothing to compute")
+    if partials is not None or (grad_x is not None and training):
+        for t, name in ((grad_weight, "grad_weight"), (grad_bias, "grad_bias")):
+            if t is None:
+                raise ValueError(f"{name}: needed by partials (the sums' destination) and by grad_x in training mode")
+    _call("batch_norm_act_backward_launcher", x, n, c, xt, code, float(negative_slope), int(bool(training)), ptr(x), ptr(grad_o), ptr(stat),
+          ptr(weight), ptr(bias), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), ptr(grad_x), opts=opts)
+
+
 # csrc/seg_loss.hip (no counterpart in the reference's launcher set: the loss tail of tool/train.py - cross-entropy, L1 shift, IoU counts)
 SEG_LOSS_MAX_C = 64
 SEG_LOSS_PARTIAL_ROWS = 1024  # most workgroups of the forward: one row of `partials` each
