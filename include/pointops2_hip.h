@@ -42,7 +42,7 @@ const char *pointops2_last_error(void);
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
  * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points, the two
  * pointops2_contacts_*_launcher, pointops2_label_boxes_launcher / pointops2_reach_rows_launcher and the three
- * pointops2_supports_*_launcher after them - a caller that needs them looks the symbols up. */
+ * pointops2_supports_*_launcher and the two pointops2_augment_*_launcher after them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -677,6 +677,55 @@ void pointops2_evaltile_vote_launcher(int m, int classes, int n_points, int row_
                                       float *pred, int *status);
 void pointops2_evaltile_vote_shift_launcher(int m, int classes, int n_points, int row_type, const void *logits, int shift_row_type, const void *shift,
                                             const long long *idx, int *stamp, float *pred, float *pred_shift, int *status);
+
+/* ---- Train-time augmentations: the transform chain of util/transform.py on device rows (stratified_transformer_amd/augment.py compiles a
+ * Compose into op tapes, makes every random draw and owns every buffer) ----
+ * pass: one thread per point of coord [n, 3] (and feat [n, 3] with POINTOPS2_AUGMENT_HAS_FEAT) - float rows, or double rows when in_f64.
+ *       The row is widened to double, the thread finds its scene in offset [n_scenes] (cumulative ends, int) and runs the n_ops ops of the
+ *       tape - opcodes [n_ops] (int, POINTOPS2_AUGMENT_OP_*), op_ptrs [n_ops][2] (long long: device addresses an op reads, 0 = none),
+ *       params [n_scenes][n_ops][POINTOPS2_AUGMENT_PARAMS] (double; [0] = the op's gate for that scene) - in float64, in the reference's
+ *       expression order, nothing fused.  With POINTOPS2_AUGMENT_STORE the rows are stored to coord_out / feat_out, rounded once to float,
+ *       or as doubles when out_f64 (a workspace; in == out is allowed).  With POINTOPS2_AUGMENT_STATS the pass accumulates, per scene, the
+ *       minimum and the maximum of the six columns of its RESULT into stats_out [n_scenes][POINTOPS2_AUGMENT_STAT_WORDS] (long long: six
+ *       minima, six maxima, one word of "column held a NaN" bits; preset by the caller to LLONG_MAX, LLONG_MIN, 0): signed integer atomics
+ *       on an order-preserving image of the double (the bit pattern, its 63 low bits inverted for a negative value; -0.0 counts as +0.0),
+ *       one per wave and column where a wave lies in one scene.  NaNs are left out of the extrema and set the column's bit.  stats_in is
+ *       the table the pass in front of this one wrote: FLIP, AUTOCONTRAST read it on the device, a set NaN bit reads as NaN.
+ *       Parameters per op, after the gate: ROTATE [1..9] the matrix R row by row (out_j = (p0 R0j + p1 R1j) + p2 R2j), [10] / [11] rotate
+ *       coord / feat; SCALE [1]; SHIFT [1..3]; JITTER [1] sigma, [2] clip, ptr 0 = noise [n, 3] double; FEAT_MUL [1]; FLIP [1..3] one flag
+ *       per axis; AUTOCONTRAST [1] the blend factor; CHROMA_TRANSLATE [1..3]; CHROMA_JITTER [1] std * 255, ptr 0 = noise [n, 3] double;
+ *       HUE_SATURATION [1] hue_val, [2] sat_ratio; ELASTIC [1] magnitude, [2] the scene's first grid value, [3..5] nx, ny, nz, [6] the
+ *       scene's first axis value, ptr 0 = the blurred grids (float), ptr 1 = the axes (double: nx, ny, nz ascending node positions).
+ *       The three chromatic ops convert feat to 0..255 and back even when their gate is shut, as the reference does.
+ * blur: one 3-tap box filter (scipy.ndimage.convolve, mode 'constant', cval 0) along `axis` of the [nx, ny, nz, 3] float grids laid end to
+ *       end in `in`: out = float((a[i-1] * w + a[i] * w) + a[i+1] * w) in double, w = double(float(1) / float(3)); desc [n_grids][4]
+ *       (long long) = first value, nx, ny, nz of every grid, ascending; total = all values.  in != out.
+ * No float atomics: equal inputs give bitwise equal results.  n = 0 / total = 0 launches nothing.  n_scenes outside
+ * [1, POINTOPS2_AUGMENT_MAX_SCENES], n_ops above POINTOPS2_AUGMENT_MAX_OPS or a missing array record an error and launch nothing.  No kernel
+ * waits on another workgroup; scene, interval and node indices are clamped into their arrays. */
+#define POINTOPS2_AUGMENT_PARAMS 16
+#define POINTOPS2_AUGMENT_MAX_SCENES 1024
+#define POINTOPS2_AUGMENT_MAX_OPS 32
+#define POINTOPS2_AUGMENT_STAT_WORDS 13
+#define POINTOPS2_AUGMENT_HAS_FEAT 1
+#define POINTOPS2_AUGMENT_STORE 2
+#define POINTOPS2_AUGMENT_STATS 4
+#define POINTOPS2_AUGMENT_OP_NOP 0
+#define POINTOPS2_AUGMENT_OP_ROTATE 1
+#define POINTOPS2_AUGMENT_OP_SCALE 2
+#define POINTOPS2_AUGMENT_OP_SHIFT 3
+#define POINTOPS2_AUGMENT_OP_JITTER 4
+#define POINTOPS2_AUGMENT_OP_FEAT_MUL 5
+#define POINTOPS2_AUGMENT_OP_FLIP 6
+#define POINTOPS2_AUGMENT_OP_AUTOCONTRAST 7
+#define POINTOPS2_AUGMENT_OP_CHROMA_TRANSLATE 8
+#define POINTOPS2_AUGMENT_OP_CHROMA_JITTER 9
+#define POINTOPS2_AUGMENT_OP_HUE_SATURATION 10
+#define POINTOPS2_AUGMENT_OP_ELASTIC 11
+void pointops2_augment_pass_launcher(int n, int n_scenes, int n_ops, int in_f64, int out_f64, int flags, const void *coord_in,
+                                     const void *feat_in, void *coord_out, void *feat_out, const int *offset, const int *opcodes,
+                                     const long long *op_ptrs, const double *params, const long long *stats_in, long long *stats_out);
+void pointops2_augment_blur_launcher(long long total, int n_grids, int axis, const long long *desc, const float *in, float *out);
 
 #ifdef __cplusplus
 }

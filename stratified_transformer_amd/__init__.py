@@ -11,6 +11,8 @@ windowed sparse-attention hot path, behind the reference's own o
                                                (all ten also exported here)
     stratified_transformer_amd.evaluate        whole-scene evaluation on csrc/evaltile.hip: crop cover, votes with shifts, IoU; the fork's
                                                detection pass in one call (scene_eval, scene_predict, dense_points, detect_scene also exported here)
+    stratified_transformer_amd.augment         the train-time transforms of util/transform.py on device tensors (csrc/augment.hip); with
+                                               dataprep.data_prepare(transform=, shuffle=) and dataprep.collate: file -> device -> batch
     stratified_transformer_amd.layers          installable fast BasicLayer.forward / WindowAttention.forward (same signatures)
     include/pointops2_hip.h                    the C ABI underneath (libpointops2_hip.so)
 

@@ -123,6 +123,8 @@ SIGNATURES = {
     "pointops2_evaltile_update_launcher": [I, I, I, P, P, P, P, P],
     "pointops2_evaltile_vote_launcher": [I, I, I, I, P, P, P, P, P],
     "pointops2_evaltile_vote_shift_launcher": [I, I, I, I, P, I, P, P, P, P, P, P],
+    "pointops2_augment_pass_launcher": [I] * 6 + [P] * 10,
+    "pointops2_augment_blur_launcher": [Q, I, I, P, P, P],
 }
 # entry points with a non-void result
 RESULTS = {

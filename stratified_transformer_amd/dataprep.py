@@ -49,14 +49,20 @@ def crop_nearest(coord, voxel_max, seed_index):
     return torch.sort(dist, stable=True)[1][:voxel_max]
 
 
-def data_prepare(coord, feat, label, split="train", voxel_size=0.04, voxel_max=None, rand=None, seed_index=None, feat_div=255.0):
+def data_prepare(coord, feat, label, split="train", voxel_size=0.04, voxel_max=None, rand=None, seed_index=None, feat_div=255.0,
+                 transform=None, shuffle=None):
     """The loaders' per-sample preparation on the device - util/data_util.py:181-203 (`data_prepare_v101`, bound by
-    util/s3dis.py:10: feat / 255) and :206-228 (`data_prepare_scannet`, util/scannet_v2.py:10: feat_div=None) without the
-    host-side transform / shuffle: shift to the minimum, one point per occupied voxel, crop to the `voxel_max` points nearest
-    to a seed point ('train' splits: a random point, else the middle one), shift again.
+    util/s3dis.py:10: feat / 255) and :206-228 (`data_prepare_scannet`, util/scannet_v2.py:10: feat_div=None):
+    the transform, shift to the minimum, one point per occupied voxel, crop to the `voxel_max` points nearest
+    to a seed point ('train' splits: a random point, else the middle one), the shuffle, shift again.
     coord [N,3] f32 / f64, feat [N,3], label [N] on the GPU; rand / seed_index replay the loader's two np.random.randint draws
-    (omitted: drawn here).  -> (coord f32, feat f32, label i64), as the loaders return them (:199-201)."""
+    (omitted: drawn here).  transform: a callable (coord, feat) -> (coord, feat) on device tensors (augment.py), applied first
+    (:180-182); shuffle: True (a device permutation is drawn) or a permutation of the prepared points to replay, applied where the
+    loader shuffles (:192-195); both default to what the function did without them: nothing.
+    -> (coord f32, feat f32, label i64), as the loaders return them (:199-201)."""
     coord = _coord(coord)
+    if transform is not None:
+        coord, feat = transform(coord, feat)
     if voxel_size:
         coord = coord - coord.min(0)[0]
         idx = voxelize(coord, voxel_size, 0, rand)
@@ -68,11 +74,52 @@ def data_prepare(coord, feat, label, split="train", voxel_size=0.04, voxel_max=N
             init = label.shape[0] // 2
         crop = crop_nearest(coord, voxel_max, init)
         coord, feat, label = coord[crop], feat[crop], label[crop]
+    if shuffle is not None and shuffle is not False:
+        if shuffle is True:
+            perm = torch.randperm(label.shape[0], device=coord.device)
+        else:
+            perm = torch.as_tensor(shuffle, device=coord.device).long()
+            if perm.shape != (label.shape[0],):
+                raise ValueError(f"shuffle: expected a permutation of the {label.shape[0]} prepared points, got shape {tuple(perm.shape)}")
+        coord, feat, label = coord[perm], feat[perm], label[perm]
     coord = coord - coord.min(0)[0]
     feat = feat.float()
     if feat_div:  # a true division, as torch's CPU kernels evaluate `FloatTensor / 255.` (:200): on the GPU `tensor / python scalar` multiplies
         feat = torch.div(feat, torch.tensor(float(feat_div), dtype=torch.float32, device=feat.device))  # by the fp32 reciprocal instead
     return coord.float(), feat, label.long()
+
+
+def collate(samples, max_batch_points, mix3d_p=None, draw=None):
+    """util/data_util.py:61-80 (`collate_fn_limit`) and :17-56 (`collate_fn_limit_mix3d`, when mix3d_p is given) on device tensors:
+    samples = [(coord, feat, label) or (coord, feat, label, shift), ...] (:83-101, `collate_fn_dcf`).  The batch is cut in front of
+    the first sample that would take it past `max_batch_points`; with probability mix3d_p (draw: the random.random() value to
+    replay, omitted: drawn here; mixed when draw <= mix3d_p) consecutive scenes are paired into one (Mix3D), an odd last one staying
+    alone.  -> (coord, feat, label, offset[, shift]); offset is an int32 device tensor whose host values are registered with
+    pointops.hint_host_offsets, so that the sampler need not read it back.  Plain torch, no kernel."""
+    import random
+
+    from . import pointops
+    if not samples:
+        raise ValueError("collate: no samples")
+    width = len(samples[0])
+    if width not in (3, 4) or any(len(s) != width for s in samples):
+        raise ValueError("collate: every sample must be (coord, feat, label) or (coord, feat, label, shift)")
+    offset, count, k = [], 0, 0
+    for s in samples:
+        count += s[0].shape[0]
+        if count > max_batch_points:
+            break
+        k += 1
+        offset.append(count)
+    if mix3d_p is not None:
+        u = random.random() if draw is None else float(draw)
+        if u <= mix3d_p:
+            offset = [offset[i] if i == k - 1 else offset[i + 1] for i in range(0, k, 2)]
+    device = samples[0][0].device
+    columns = [torch.cat([s[c] for s in samples[:k]]) if k else samples[0][c][:0] for c in range(width)]
+    off = torch.tensor(offset, dtype=torch.int32, device=device)
+    pointops.hint_host_offsets(off, offset)
+    return (columns[0], columns[1], columns[2], off) + tuple(columns[3:])
 
 
 # ---- readers of the scene files the loaders open (nothing is executed from the file) ----
