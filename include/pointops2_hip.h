@@ -42,7 +42,7 @@ const char *pointops2_last_error(void);
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
  * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points, the two
  * pointops2_contacts_*_launcher, pointops2_label_boxes_launcher / pointops2_reach_rows_launcher and the three
- * pointops2_supports_*_launcher and the two pointops2_augment_*_launcher after them - a caller that needs them looks the symbols up. */
+ * pointops2_supports_*_launcher, the two pointops2_augment_*_launcher and optim_adamw_step_launcher after them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -726,6 +726,39 @@ void pointops2_augment_pass_launcher(int n, int n_scenes, int n_ops, int in_f64,
                                      const void *feat_in, void *coord_out, void *feat_out, const int *offset, const int *opcodes,
                                      const long long *op_ptrs, const double *params, const long long *stats_in, long long *stats_out);
 void pointops2_augment_blur_launcher(long long total, int n_grids, int axis, const long long *desc, const float *in, float *out);
+
+/* ---- The optimizer step: the loss scaler's finite check and torch.optim.AdamW's update (amsgrad = False, maximize = False) of every
+ * parameter tensor in one call (stratified_transformer_amd/optim.py; csrc/optim.hip states the arithmetic and its order) ----
+ * host_table: HOST memory, n_tensors pointops2_optim_tensor followed at once by n_groups pointops2_optim_group.  The launcher checks it,
+ *       fills every first_chunk (the prefix sum of ceil(numel / POINTOPS2_OPTIM_CHUNK)) and copies it to `workspace` on the stream.  In
+ *       page-locked memory the copy is asynchronous: the caller leaves the table alone until the stream has passed this call (from pageable
+ *       memory the runtime stages the copy before it returns, and may wait for the stream to do so).
+ * workspace: device memory, at least pointops2_optim_workspace_bytes(n_tensors, n_groups) bytes, 16-byte aligned, the caller's until the
+ *       stream has passed this call: the table's copy and one record of bias corrections per tensor.
+ * scale: device, 1 float, the loss scale the gradients carry (they are multiplied by float(1.0 / (double)*scale)), or NULL: 1.
+ * found_inf: device, 1 float.  run_check != 0: cleared on the stream, then set to 1.0f when any element of any gradient is an infinity
+ *       or a NaN.  run_check == 0: the caller's own verdict, only read.  When it is not 0 the call changes nothing else: parameters, moments
+ *       and step counts keep their bits.  Otherwise every tensor's *step (1 float, device) advances by one.
+ * All pointers inside the table are device pointers of fp32 arrays of numel elements, at any 4-byte alignment; the tensors must not overlap.
+ * At most 4 launches and one copy whatever n_tensors is; no device-to-host copy and no synchronisation.  Recorded as errors, nothing
+ * enqueued: a negative n_tensors or n_groups, a numel outside [0, 2^31), a group outside [0, n_groups), a NULL pointer, a short workspace. */
+#define POINTOPS2_OPTIM_CHUNK 4096
+typedef struct pointops2_optim_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    float *step;
+    long long numel;
+    int group;
+    int first_chunk; /* written by the launcher */
+} pointops2_optim_tensor;
+typedef struct pointops2_optim_group {
+    double lr, beta1, beta2, eps, weight_decay;
+} pointops2_optim_group;
+size_t pointops2_optim_workspace_bytes(int n_tensors, int n_groups);
+void optim_adamw_step_launcher(int n_tensors, int n_groups, void *host_table, void *workspace, size_t workspace_bytes, const float *scale,
+                               float *found_inf, int run_check);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@ windowed sparse-attention hot path, behind the reference's own o
                                                detection pass in one call (scene_eval, scene_predict, dense_points, detect_scene also exported here)
     stratified_transformer_amd.augment         the train-time transforms of util/transform.py on device tensors (csrc/augment.hip); with
                                                dataprep.data_prepare(transform=, shuffle=) and dataprep.collate: file -> device -> batch
+    stratified_transformer_amd.optim           AdamW and GradScaler: scaler.step(optimizer) as one call on csrc/optim.hip, no read-back
     stratified_transformer_amd.layers          installable fast BasicLayer.forward / WindowAttention.forward (same signatures)
     include/pointops2_hip.h                    the C ABI underneath (libpointops2_hip.so)
 
@@ -45,6 +46,9 @@ def __getattr__(name):
     if name == "segmentation_loss":  # pointops.segmentation_loss: cross-entropy, L1 shift, their sum and the IoU counts on csrc/seg_loss.hip
         from . import pointops
         return pointops.segmentation_loss
+    if name == "optim":  # optim.AdamW / optim.GradScaler: the loss scaler's check and the AdamW update in one call on csrc/optim.hip
+        import importlib
+        return importlib.import_module(".optim", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -125,6 +125,7 @@ SIGNATURES = {
     "pointops2_evaltile_vote_shift_launcher": [I, I, I, I, P, I, P, P, P, P, P, P],
     "pointops2_augment_pass_launcher": [I] * 6 + [P] * 10,
     "pointops2_augment_blur_launcher": [Q, I, I, P, P, P],
+    "optim_adamw_step_launcher": [I, I, P, P, Z, P, P, I],
 }
 # entry points with a non-void result
 RESULTS = {
@@ -140,6 +141,7 @@ RESULTS = {
     "pointops2_cell_plan_workspace_bytes": ([I], Z),
     "pointops2_cell_forward_variant": ([P, I, I, I, I], I),
     "pointops2_evaltile_max_parts": ([], I),
+    "pointops2_optim_workspace_bytes": ([I, I], Z),
 }
 
 # codes of pointops2_cell_forward_variant (POINTOPS2_CELL_FWD_* of include/pointops2_hip.h): the forward kernel a cell launch runs
