@@ -506,6 +506,26 @@ void batch_norm_act_forward_launcher(int n, int c, int x_type, int r_type, int a
 void batch_norm_act_backward_launcher(int n, int c, int x_type, int act, float slope, int training, const void *x, const void *grad_o,
                                       const float *stat, const float *gamma, const float *beta, float *partials, int partial_rows,
                                       float *grad_gamma, float *grad_beta, void *grad_x);
+/* The same norm with the statistics of SEVERAL RANKS' rows (training under SyncBatchNorm).  The caller moves two small arrays between the
+ * ranks by an exact gather; everything else stays on the device, nothing is read back.
+ *   moments:        row [3,c] = this rank's (count, mean, M2): the pass of `stats` above, its partials merged in the same order.  n = 0
+ *                   writes a row of zeros and runs no row pass (x and partials may then be NULL).
+ *   merge:          rows [world,3,c], rank r's row at r, are merged by Chan's formula strictly in rank order 0 .. world-1 (a row of count 0
+ *                   is skipped); stat [2,c] = (mean, rstd = 1 / sqrt(M2 / N + eps)), total [1] = N, the summed count; the running
+ *                   statistics (both or neither) take the update of `stats` with the merged mean and M2 / (N - 1), unless N = 0.  The same
+ *                   rows give the same bits on every rank; with world = 1 they are the bits of `stats`.
+ *   forward:        batch_norm_act_forward_launcher with the two rows of stat.
+ *   local sums:     batch_norm_act_backward_launcher with grad_x = NULL: this rank's (sum g * xhat, sum g) - its parameter gradients.
+ *   sync backward:  sums [world,2,c], rank r's (sum g * xhat, sum g) at r, are added in rank order to (S_gx, S_g);
+ *                   grad_x (FULLY WRITTEN) = (gamma * rstd) * ((g - S_g / N) - xhat * (S_gx / N)) with N = total[0] read on the device.
+ *                   n = 0 is a no-op.
+ * 1 <= world <= 1024.  Counts are fp32 values: exact while N < 2^24 rows. */
+void batch_norm_act_moments_launcher(int n, int c, int x_type, const void *x, float *partials, int partial_rows, float *row);
+void batch_norm_act_merge_launcher(int world, int c, const float *rows, float eps, float momentum, float *running_mean, float *running_var,
+                                   float *stat, float *total);
+void batch_norm_act_sync_backward_launcher(int n, int c, int x_type, int act, float slope, const void *x, const void *grad_o, const float *stat,
+                                           const float *gamma, const float *beta, int world, const float *sums, const float *total,
+                                           void *grad_x);
 
 /* ---- the loss tail of a segmentation training step in one pass: cross-entropy on the class logits, L1 on the shift head, their
  * weighted sum and the per-class IoU counts (tool/train.py:336-362, train_backup.py:403, util/common_util.py:180-185) ----

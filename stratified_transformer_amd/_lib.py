@@ -105,6 +105,9 @@ SIGNATURES = {
     "batch_norm_act_stats_launcher": [I, I, I, P, P, I, F, F, P, P, P],
     "batch_norm_act_forward_launcher": [I, I, I, I, I, F, P, P, P, I, F, P, P, P, P, P],
     "batch_norm_act_backward_launcher": [I, I, I, I, F, I, P, P, P, P, P, P, I, P, P, P],
+    "batch_norm_act_moments_launcher": [I, I, I, P, P, I, P],
+    "batch_norm_act_merge_launcher": [I, I, P, F, F, P, P, P, P],
+    "batch_norm_act_sync_backward_launcher": [I, I, I, I, F, P, P, P, P, P, I, P, P, P],
     "seg_loss_forward_launcher": [I, I, I, I, P, P, P, P, Q, F, F, P, P, I, P, P, P],
     "seg_loss_backward_launcher": [I, I, I, I, P, P, P, P, P, P, P, Q, F, F, P, P],
     "pointops2_dbscan_keys_launcher": [I, I, P, P, D, D, D, D, I, I, I, P],

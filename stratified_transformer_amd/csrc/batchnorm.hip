@@ -24,12 +24,21 @@
 // the order of column_reduce.  A constant column gives S1 = S2 = 0 and every delta 0: mean = K and M2 = 0 exactly.  The dgamma / dbeta
 // sums travel the same way with `+` as the merge.  No float atomics; every order is a function of the shapes alone: the same bits from
 // run to run on one device.  Lanes: row_lanes.h (four channels a lane, rows side by side in a wave; one channel a lane as the fallback).
+//
+// Several ranks (training under SyncBatchNorm): the statistics are those of all ranks' rows.  Each rank runs the moments pass and merges its
+// workgroups' partials into ONE row (count, mean, M2) [3][C] (bn_row_kernel, column_reduce's order); the rows are gathered by the caller
+// - a copy, no arithmetic - and bn_merge_kernel Chan-merges them strictly in rank order 0 .. world-1, one thread per channel: the same
+// rows give the same (mean, rstd), count and running statistics on every rank.  Backward: each rank's (sum g * xhat, sum g) [2][C] from the
+// SUMS pass, gathered likewise; the dx pass adds the rows in rank order in its per-lane channel set-up (world * 2 * C floats per workgroup
+// from L2 against a launch and a dependent kernel for a [2][C] buffer: the set-up is once per lane, the row loop is untouched) and
+// divides by the global count, which it reads on the device.  Counts are fp32: exact below 2^24 rows.
 #include "row_lanes.h"
 
 namespace p2 {
 namespace {
 
 constexpr int BN_PARTIAL_ROWS_MAX = 1024;
+constexpr int BN_WORLD_MAX = 1024;  // ranks whose rows one merge takes
 
 struct Moments {
     float n, mean, m2;  // of the values merged so far: their number, their mean, the sum of their squared deviations from it
@@ -163,6 +172,42 @@ __global__ __launch_bounds__(RED_COLS *RED_GROUPS) void bn_stat_kernel(int rows,
     }
 }
 
+// row = (count, mean, M2) [3][c]: the rows of partials merged as bn_stat_kernel merges them (rows == 0: a row of zeros)
+__global__ __launch_bounds__(RED_COLS *RED_GROUPS) void bn_row_kernel(int rows, int c, const float *__restrict__ partials, float *__restrict__ row) {
+    __shared__ Moments red[RED_GROUPS][RED_COLS];
+    const int col = blockIdx.x * RED_COLS + threadIdx.x % RED_COLS;
+    const Moments m = column_reduce(rows, col < c, Moments{0.0f, 0.0f, 0.0f}, red, [&](int b) {
+        const float *p = partials + (size_t)b * 3 * c + col;
+        return Moments{p[0], p[c], p[2 * (size_t)c]};
+    }, [](Moments p, Moments q) { return chan_merge(p, q); });
+    if (threadIdx.x < RED_COLS && col < c) {
+        row[col] = m.n;
+        row[c + col] = m.mean;
+        row[2 * c + col] = m.m2;
+    }
+}
+
+// stat = (mean, rstd) [2][c] and total = the summed count from the ranks' rows [world][3][c], merged in rank order (an empty rank's row is
+// skipped by chan_merge); the running statistics' update where they are given.  One thread per channel.
+__global__ __launch_bounds__(WAVE) void bn_merge_kernel(int world, int c, const float *__restrict__ rows, float eps, float momentum,
+                                                        float *__restrict__ running_mean, float *__restrict__ running_var,
+                                                        float *__restrict__ stat, float *__restrict__ total) {
+    const int col = blockIdx.x * WAVE + threadIdx.x;
+    if (col >= c) return;
+    Moments m{0.0f, 0.0f, 0.0f};
+    for (int r = 0; r < world; r++) {
+        const float *p = rows + (size_t)r * 3 * c + col;
+        m = chan_merge(m, Moments{p[0], p[c], p[2 * (size_t)c]});
+    }
+    stat[col] = m.mean;
+    stat[c + col] = 1.0f / sqrtf(m.m2 / m.n + eps);
+    if (m.n > 0.0f) {
+        if (running_mean != nullptr) running_mean[col] = (1.0f - momentum) * running_mean[col] + momentum * m.mean;
+        if (running_var != nullptr) running_var[col] = (1.0f - momentum) * running_var[col] + momentum * (m.m2 / (m.n - 1.0f));  // unbiased, as torch
+    }
+    if (col == 0) total[0] = m.n;  // (every channel holds the same count)
+}
+
 template <int VEC, int ITER>
 __global__ __launch_bounds__(RN_THREADS) void bn_fwd_kernel(int n, int c, int chunks, int seg, int x_type, int r_type, int act, float slope,
                                                             const void *__restrict__ x, const float *__restrict__ mean,
@@ -203,19 +248,22 @@ __global__ __launch_bounds__(RN_THREADS) void bn_fwd_kernel(int n, int c, int ch
     }
 }
 
-// SUMS: partials[workgroup] = (sum g * xhat, sum g) [2][c] of the workgroup's rows.  else: grad_x, from the finished sums
-template <int VEC, int ITER, bool SUMS>
+// SUMS: partials[workgroup] = (sum g * xhat, sum g) [2][c] of the workgroup's rows.  else: grad_x, from the finished sums.
+// SYNC (grad_x only): sum_gx / sum_g are rows 0 / 1 of the first of `world` gathered sum rows [world][2][c], added here in rank order,
+// and the row count is total[0], the ranks' summed count
+template <int VEC, int ITER, bool SUMS, bool SYNC = false>
 __global__ __launch_bounds__(RN_THREADS) void bn_bwd_kernel(int n, int c, int chunks, int seg, int x_type, int act, float slope, int training,
                                                             const void *__restrict__ x, const void *__restrict__ grad_o,
                                                             const float *__restrict__ stat, const float *__restrict__ gamma,
                                                             const float *__restrict__ beta, const float *__restrict__ sum_gx,
                                                             const float *__restrict__ sum_g, float *__restrict__ partials,
-                                                            void *__restrict__ grad_x) {
+                                                            void *__restrict__ grad_x, int world, const float *__restrict__ total) {
     __shared__ float red[SUMS ? 2 : 1][SUMS ? RN_THREADS * ITER * VEC : 1];
     const SegLanes sl(seg);
     const Channels<VEC, ITER> ch(sl, chunks, stat, stat + c, false, 0.0f, gamma, beta);
     float a[ITER][VEC], b[ITER][VEC];  // SUMS: the lane's sums of g * xhat and g;  else: dgamma / N and dbeta / N
-    const float fn = (float)n;
+    float fn = (float)n;
+    if constexpr (SYNC) fn = total[0];
 #pragma unroll
     for (int it = 0; it < ITER; it++) {
 #pragma unroll
@@ -224,6 +272,15 @@ __global__ __launch_bounds__(RN_THREADS) void bn_bwd_kernel(int n, int c, int ch
             const size_t at = (size_t)(sl.chunk0 + it * WAVE) * VEC;
             load_chunk<VEC>(sum_gx, at, POINTOPS2_ROWS_F32, a[it]);
             load_chunk<VEC>(sum_g, at, POINTOPS2_ROWS_F32, b[it]);
+            if constexpr (SYNC) {
+                for (int r = 1; r < world; r++) {  // rank order: the same sums on every rank
+                    float ar[VEC], br[VEC];
+                    load_chunk<VEC>(sum_gx, (size_t)r * 2 * c + at, POINTOPS2_ROWS_F32, ar);
+                    load_chunk<VEC>(sum_g, (size_t)r * 2 * c + at, POINTOPS2_ROWS_F32, br);
+#pragma unroll
+                    for (int e = 0; e < VEC; e++) a[it][e] += ar[e], b[it][e] += br[e];
+                }
+            }
 #pragma unroll
             for (int e = 0; e < VEC; e++) a[it][e] = a[it][e] / fn, b[it][e] = b[it][e] / fn;
         }
@@ -352,7 +409,7 @@ void batch_norm_act_backward_launcher(int n, int c, int x_type, int act, float s
         for_shape(sh, [&](auto tag) {
             hipLaunchKernelGGL((bn_bwd_kernel<decltype(tag)::vec, decltype(tag)::iter, true>), dim3(grid), dim3(RN_THREADS), 0, st, n, c, sh.chunks,
                                sh.seg, x_type, act, slope, training, x, grad_o, stat, gamma, beta, (const float *)nullptr, (const float *)nullptr,
-                               partials, (void *)nullptr);
+                               partials, (void *)nullptr, 0, (const float *)nullptr);
         });
         if (!check_launch()) return;
         hipLaunchKernelGGL(bn_param_kernel, dim3(div_up(2 * c, RED_COLS)), dim3(RED_COLS * RED_GROUPS), 0, st, grid, c, partials, grad_gamma,
@@ -363,10 +420,68 @@ void batch_norm_act_backward_launcher(int n, int c, int x_type, int act, float s
         for_shape(sh, [&](auto tag) {
             hipLaunchKernelGGL((bn_bwd_kernel<decltype(tag)::vec, decltype(tag)::iter, false>), dim3(sh.grid(n, num_cus() * 64)), dim3(RN_THREADS), 0,
                                st, n, c, sh.chunks, sh.seg, x_type, act, slope, training, x, grad_o, stat, gamma, beta, grad_gamma, grad_beta,
-                               (float *)nullptr, grad_x);
+                               (float *)nullptr, grad_x, 0, (const float *)nullptr);
         });
         check_launch();
     }
+}
+
+void batch_norm_act_moments_launcher(int n, int c, int x_type, const void *x, float *partials, int partial_rows, float *row) {
+    const hipStream_t st = begin_launch().stream;
+    if (const char *bad = bn_bad_args(n, c, x_type, POINTOPS2_ROWS_F32, POINTOPS2_ACT_NONE)) { set_error(bad); return; }
+    if (row == nullptr || (n > 0 && (x == nullptr || partials == nullptr || bad_partial_rows(partial_rows)))) {
+        set_error("batch_norm_act_moments: row - and with n > 0 x and partials - must not be NULL, partial_rows in [1, 1024]");
+        return;
+    }
+    int grid = 0;
+    if (n > 0) {
+        const RowShape sh(c, c % 4 == 0 && rows_aligned(x, x_type));
+        grid = sh.grid(n, partial_rows);
+        for_shape(sh, [&](auto tag) {
+            hipLaunchKernelGGL((bn_moments_kernel<decltype(tag)::vec, decltype(tag)::iter>), dim3(grid), dim3(RN_THREADS), 0, st, n, c, sh.chunks,
+                               sh.seg, x_type, x, partials);
+        });
+        if (!check_launch()) return;
+    }
+    hipLaunchKernelGGL(bn_row_kernel, dim3(div_up(c, RED_COLS)), dim3(RED_COLS * RED_GROUPS), 0, st, grid, c, partials, row);
+    check_launch();
+}
+
+void batch_norm_act_merge_launcher(int world, int c, const float *rows, float eps, float momentum, float *running_mean, float *running_var,
+                                   float *stat, float *total) {
+    const hipStream_t st = begin_launch().stream;
+    if (const char *bad = bn_bad_args(0, c, POINTOPS2_ROWS_F32, POINTOPS2_ROWS_F32, POINTOPS2_ACT_NONE)) { set_error(bad); return; }
+    if (world < 1 || world > BN_WORLD_MAX || rows == nullptr || stat == nullptr || total == nullptr ||
+        (running_mean == nullptr) != (running_var == nullptr)) {
+        set_error("batch_norm_act_merge: world in [1, 1024]; rows, stat and total must not be NULL; running_mean and running_var go together");
+        return;
+    }
+    hipLaunchKernelGGL(bn_merge_kernel, dim3(div_up(c, WAVE)), dim3(WAVE), 0, st, world, c, rows, eps, momentum, running_mean, running_var, stat,
+                       total);
+    check_launch();
+}
+
+void batch_norm_act_sync_backward_launcher(int n, int c, int x_type, int act, float slope, const void *x, const void *grad_o, const float *stat,
+                                           const float *gamma, const float *beta, int world, const float *sums, const float *total,
+                                           void *grad_x) {
+    const hipStream_t st = begin_launch().stream;
+    if (const char *bad = bn_bad_args(n, c, x_type, POINTOPS2_ROWS_F32, act)) { set_error(bad); return; }
+    if (world < 1 || world > BN_WORLD_MAX) { set_error("batch_norm_act_sync_backward: world must be in [1, 1024]"); return; }
+    if (n == 0) return;
+    if (x == nullptr || grad_o == nullptr || stat == nullptr || gamma == nullptr || beta == nullptr || sums == nullptr || total == nullptr ||
+        grad_x == nullptr) {
+        set_error("batch_norm_act_sync_backward: x, grad_o, stat, gamma, beta, sums, total and grad_x must not be NULL");
+        return;
+    }
+    const bool chunked = c % 4 == 0 && rows_aligned(x, x_type) && rows_aligned(grad_o, x_type) && rows_aligned(grad_x, x_type) && aligned_to(stat, 16) &&
+                         aligned_to(gamma, 16) && aligned_to(beta, 16) && aligned_to(sums, 16);
+    const RowShape sh(c, chunked);
+    for_shape(sh, [&](auto tag) {
+        hipLaunchKernelGGL((bn_bwd_kernel<decltype(tag)::vec, decltype(tag)::iter, false, true>), dim3(sh.grid(n, num_cus() * 64)), dim3(RN_THREADS), 0,
+                           st, n, c, sh.chunks, sh.seg, x_type, act, slope, 1, x, grad_o, stat, gamma, beta, sums, sums + c, (float *)nullptr, grad_x,
+                           world, total);
+    });
+    check_launch();
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
 
   * The batch norms of the stem and the heads (off by default): `fuse_batch_norms(model)` binds, per instance, forwards that run every
     BatchNorm1d + activation (+ the ResBlock's shortcut add) as one pointops.batch_norm_act call (csrc/batchnorm.hip).
+    `fuse_sync_batch_norms(model)` takes nn.SyncBatchNorm sites too and runs pointops.sync_batch_norm_act wherever the module synchronises.
 
 Numbers: the same sums in another order (tests/test_hip_parity.py::test_installed_fast_layers_against_the_reference_layer:
 output and every parameter gradient of a depth-2 BasicLayer with TransitionDown against the reference's own run, <= 1e-3).
@@ -617,12 +618,13 @@ def install_fused_blocks(module=None):
 # `forward` is bound in the instance's __dict__ (no submodule, parameter or buffer is added, replaced or renamed: state_dict() keeps
 # its keys, copy.deepcopy re-binds the method to the copy) and unfuse_batch_norms deletes it again.  Whether a site runs fused is decided
 # at every call; where it does not, the site's own modules run as they are and yield torch's bits.
-def _bn_of(m):
-    """the nn.BatchNorm1d a child is or holds as `.batch_norm` (FastBatchNorm1d); nn.SyncBatchNorm is not one"""
-    if isinstance(m, torch.nn.BatchNorm1d):
+def _bn_of(m, sync=False):
+    """the nn.BatchNorm1d a child is or holds as `.batch_norm` (FastBatchNorm1d); nn.SyncBatchNorm is one only with `sync`"""
+    kinds = (torch.nn.BatchNorm1d, torch.nn.SyncBatchNorm) if sync else torch.nn.BatchNorm1d
+    if isinstance(m, kinds):
         return m
     inner = getattr(m, "batch_norm", None)
-    return inner if isinstance(inner, torch.nn.BatchNorm1d) else None
+    return inner if isinstance(inner, kinds) else None
 
 
 def _act_of(m):
@@ -636,11 +638,11 @@ def _act_of(m):
     return None
 
 
-def _seq_pairs(seq):
+def _seq_pairs(seq, sync=False):
     """{index of a norm child: (its BatchNorm1d, act, children the pair spans)}: a norm directly followed by a known activation, or by nothing"""
     mods, pairs = list(seq), {}
     for i, m in enumerate(mods):
-        bn = _bn_of(m)
+        bn = _bn_of(m, sync)
         if bn is None:
             continue
         act = ("none", 0.0) if i + 1 == len(mods) else _act_of(mods[i + 1])
@@ -650,6 +652,19 @@ def _seq_pairs(seq):
 
 
 _ROW_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _sync_group(bn):
+    """the process group over which the module `bn` synchronises at this call, None where it does not: nn.SyncBatchNorm's own rule -
+    training mode, torch.distributed initialised, more than one rank in the module's group (at one rank, and in eval mode, the module
+    is a plain batch norm).  All of it is equal on every rank."""
+    if not (isinstance(bn, torch.nn.SyncBatchNorm) and bn.training):
+        return None
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    group = bn.process_group if bn.process_group is not None else dist.group.WORLD
+    return group if dist.get_world_size(group) > 1 else None
 
 
 def _bn_call(bn, x, act, residual=None):
@@ -667,16 +682,21 @@ def _bn_call(bn, x, act, residual=None):
     tracked = bn.running_mean is not None and bn.running_var is not None
     if bn.training and tracked and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
+    group = _sync_group(bn)
+    if group is not None:
+        o = P.sync_batch_norm_act(x.contiguous(), bn.weight, bn.bias, bn.running_mean if tracked else None, bn.running_var if tracked else None,
+                                  bn.momentum, bn.eps, act[0], act[1], residual, group)
+        return o, residual is not None
     o = P.batch_norm_act(x.contiguous(), bn.weight, bn.bias, bn.running_mean if tracked else None, bn.running_var if tracked else None,
                          bn.training or not tracked, bn.momentum, bn.eps, act[0], act[1], residual)
     return o, residual is not None
 
 
-def _run_sequential(seq, x, make_residual=None):
+def _run_sequential(seq, x, make_residual=None, sync=False):
     """nn.Sequential.forward with every (norm, activation) pair as one batch_norm_act call.  make_residual() yields what the caller adds to
     the result: it is called once, behind every child in front of the pair that ends the container - that pair then adds it - or
     behind the last child -> (result, the residual, whether it was added)"""
-    mods, pairs = list(seq), _seq_pairs(seq)
+    mods, pairs = list(seq), _seq_pairs(seq, sync)
     i, residual, added = 0, None, False
     while i < len(mods):
         if i in pairs:
@@ -700,35 +720,50 @@ def fused_sequential_forward(self, input):
     return _run_sequential(self, input)[0]
 
 
-def fused_simple_block_forward(self, feats, xyz, batch, neighbor_idx):
+def fused_simple_block_forward(self, feats, xyz, batch, neighbor_idx, sync=False):
     """KPConvSimpleBlock.forward (model/stratified_transformer.py:351-359), same arguments, same result: `activation(bn(.))` in one call"""
     feats = self.kpconv(xyz, xyz, neighbor_idx, feats)
-    bn, act = _bn_of(self.bn), _act_of(self.activation)
+    bn, act = _bn_of(self.bn, sync), _act_of(self.activation)
     out = _bn_call(bn, feats, act) if bn is not None and act is not None else None
     return out[0] if out is not None else self.activation(self.bn(feats))
 
 
-def fused_res_block_forward(self, feats, xyz, batch, neighbor_idx):
+def fused_res_block_forward(self, feats, xyz, batch, neighbor_idx, sync=False):
     """KPConvResBlock.forward (:380-392), same arguments, same result: unary_1's and unary_2's norm + activation in one call each, the
     second with the `feats += shortcut` of :391"""
     if not (torch.is_tensor(feats) and feats.is_cuda):
         return type(self).forward(self, feats, xyz, batch, neighbor_idx)
     shortcut = feats
-    feats = _run_sequential(self.unary_1, feats)[0]
+    feats = _run_sequential(self.unary_1, feats, sync=sync)[0]
     feats = self.kpconv(xyz, xyz, neighbor_idx, feats)
     # (shortcut_op runs behind unary_2's Linear, not behind its activation as in :389-390: the norm and the activation draw nothing)
-    feats, shortcut, added = _run_sequential(self.unary_2, feats, lambda: self.shortcut_op(shortcut))
+    feats, shortcut, added = _run_sequential(self.unary_2, feats, lambda: self.shortcut_op(shortcut), sync)
     if not added:
         feats += shortcut
     return feats
 
 
+# fuse_sync_batch_norms binds these: the same forwards with nn.SyncBatchNorm counted as a norm (the choice travels with the bound
+# function, so a deepcopy keeps it and no attribute is added to the module)
+def fused_sync_sequential_forward(self, input):
+    return _run_sequential(self, input, sync=True)[0]
+
+
+def fused_sync_simple_block_forward(self, feats, xyz, batch, neighbor_idx):
+    return fused_simple_block_forward(self, feats, xyz, batch, neighbor_idx, sync=True)
+
+
+def fused_sync_res_block_forward(self, feats, xyz, batch, neighbor_idx):
+    return fused_res_block_forward(self, feats, xyz, batch, neighbor_idx, sync=True)
+
+
 _BN_FORWARDS = (fused_sequential_forward, fused_simple_block_forward, fused_res_block_forward)
+_BN_SYNC_FORWARDS = (fused_sync_sequential_forward, fused_sync_simple_block_forward, fused_sync_res_block_forward)
 
 
 def _bn_fused(m):
     f = m.__dict__.get("forward")
-    return f is not None and getattr(f, "__func__", None) in _BN_FORWARDS
+    return f is not None and getattr(f, "__func__", None) in _BN_FORWARDS + _BN_SYNC_FORWARDS
 
 
 def fuse_batch_norms(model):
@@ -740,21 +775,37 @@ def fuse_batch_norms(model):
       * a module with `unary_1`, `unary_2`, `kpconv`, `shortcut_op` (KPConvResBlock; reported as its two sites `<name>.unary_1`, `<name>.unary_2`).
     Each pair runs as one pointops.batch_norm_act call (csrc/batchnorm.hip) when, at that call, the rows are a 2-D f32 / f16 / bf16 GPU
     tensor of C <= 1024 channels and the norm has affine f32 parameters and a momentum; otherwise the site's modules run as they are.
-    Train / eval mode, the running statistics and num_batches_tracked behave as the modules' own.  unfuse_batch_norms(model) undoes it."""
+    Train / eval mode, the running statistics and num_batches_tracked behave as the modules' own.  unfuse_batch_norms(model) undoes it.
+    nn.SyncBatchNorm sites are left alone: fuse_sync_batch_norms takes them."""
+    return _fuse_batch_norms(model, False)
+
+
+def fuse_sync_batch_norms(model):
+    """fuse_batch_norms for a model trained on several ranks: an nn.SyncBatchNorm (what SyncBatchNorm.convert_sync_batchnorm makes of
+    every norm under the reference's `sync_bn: True`) counts as a norm, beside BatchNorm1d, in all three kinds of site; the same site
+    names come back.  Where such a module synchronises at a call - training mode, torch.distributed initialised, more than one rank in
+    its process_group - the pair runs as one pointops.sync_batch_norm_act call: statistics over all ranks' rows, two small gathers per
+    call; everywhere else (one rank, eval mode) as batch_norm_act, which is what torch's module computes there.  Everything else as
+    fuse_batch_norms; unfuse_batch_norms(model) undoes either."""
+    return _fuse_batch_norms(model, True)
+
+
+def _fuse_batch_norms(model, sync):
     import types
+    seq_fn, simple_fn, res_fn = _BN_SYNC_FORWARDS if sync else _BN_FORWARDS
     sites, inner = [], set()
     for name, m in model.named_modules():
         if id(m) in inner:
             continue
         res = all(hasattr(m, a) for a in ("unary_1", "unary_2", "kpconv", "shortcut_op"))
-        if res and all(isinstance(u, torch.nn.Sequential) and _seq_pairs(u) for u in (m.unary_1, m.unary_2)):
-            fn, names = fused_res_block_forward, [f"{name}.unary_1" if name else "unary_1", f"{name}.unary_2" if name else "unary_2"]
+        if res and all(isinstance(u, torch.nn.Sequential) and _seq_pairs(u, sync) for u in (m.unary_1, m.unary_2)):
+            fn, names = res_fn, [f"{name}.unary_1" if name else "unary_1", f"{name}.unary_2" if name else "unary_2"]
             inner.update((id(m.unary_1), id(m.unary_2)))
-        elif (not hasattr(m, "unary_1") and all(hasattr(m, a) for a in ("kpconv", "bn", "activation")) and _bn_of(m.bn) is not None
+        elif (not hasattr(m, "unary_1") and all(hasattr(m, a) for a in ("kpconv", "bn", "activation")) and _bn_of(m.bn, sync) is not None
               and _act_of(m.activation) is not None):
-            fn, names = fused_simple_block_forward, [name]
-        elif isinstance(m, torch.nn.Sequential) and _seq_pairs(m):
-            fn, names = fused_sequential_forward, [name]
+            fn, names = simple_fn, [name]
+        elif isinstance(m, torch.nn.Sequential) and _seq_pairs(m, sync):
+            fn, names = seq_fn, [name]
         else:
             continue
         if "forward" in m.__dict__ and not _bn_fused(m):
@@ -765,7 +816,7 @@ def fuse_batch_norms(model):
 
 
 def unfuse_batch_norms(model):
-    """Removes what fuse_batch_norms bound: every module of `model` runs its class's forward again"""
+    """Removes what fuse_batch_norms or fuse_sync_batch_norms bound: every module of `model` runs its class's forward again"""
     for m in model.modules():
         if _bn_fused(m):
             del m.__dict__["forward"]

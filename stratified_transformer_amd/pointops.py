@@ -1161,6 +1161,50 @@ class BatchNormAct(Function):
         return (grad_x if need_x else None, grad_w if need_w else None, grad_b if need_b else None, grad_r) + (None,) * 8
 
 
+def _batch_norm_check(op, x, weight, bias, running_mean, running_var, training, momentum, act, residual):
+    """the argument checks batch_norm_act and sync_batch_norm_act share; the messages start with `op`"""
+    tensors = [("x", x), ("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var), ("residual", residual)]
+    for name, t in tensors[:3]:
+        if t is None:
+            raise ValueError(f"{op}: {name} is None (a BatchNorm1d with affine parameters is expected)")
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{op}: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+    for name, t in tensors[1:]:
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{op}: {name} is on {t.device}, x on {x.device}")
+    rows = (torch.float32, torch.float16, torch.bfloat16)
+    if x.dim() != 2:
+        raise ValueError(f"{op}: x must be [n, c], got {tuple(x.shape)}")
+    if x.dtype not in rows:
+        raise TypeError(f"{op}: x must be f32, f16 or bf16, got {x.dtype}")
+    n, c = x.shape
+    if not 1 <= c <= pointops_cuda.BATCH_NORM_MAX_C:
+        raise ValueError(f"{op}: c must be in [1, {pointops_cuda.BATCH_NORM_MAX_C}], got x {tuple(x.shape)}")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError(f"{op}: {'running_mean' if running_mean is None else 'running_var'} is None and the other is not: "
+                         "running_mean and running_var are given together or not at all")
+    for name, t in tensors[1:5]:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"{op}: {name} must be f32, got {t.dtype}")
+        if tuple(t.shape) != (c,):
+            raise ValueError(f"{op}: {name} must be [{c}], got {tuple(t.shape)}")
+    if residual is not None:
+        if residual.dtype not in rows:
+            raise TypeError(f"{op}: residual must be f32, f16 or bf16, got {residual.dtype}")
+        if tuple(residual.shape) != (n, c):
+            raise ValueError(f"{op}: residual must be [{n}, {c}] like x, got {tuple(residual.shape)}")
+    if act not in ("none", "relu", "leaky_relu", "tanh"):
+        raise ValueError(f"{op}: act must be 'none', 'relu', 'leaky_relu' or 'tanh', got {act!r}")
+    if training and running_mean is not None and momentum is None:
+        raise ValueError(f"{op}: momentum is None (a cumulative average of the running statistics is not supported)")
+    for name, t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous")
+
+
 def batch_norm_act(x, weight, bias, running_mean=None, running_var=None, training=True, momentum=0.1, eps=1e-5, act="none",
                    negative_slope=0.01, residual=None):
     """o = act(F.batch_norm(x, running_mean, running_var, weight, bias, training, momentum, eps)) (+ residual) -> o [n, c] of x's dtype, in
@@ -1174,52 +1218,95 @@ def batch_norm_act(x, weight, bias, running_mean=None, running_var=None, trainin
     when only x does, because dx reads both sums (freezing the parameters spares the sums in eval mode alone) -, dx when x wants one,
     nothing for the residual.
     1 <= c <= 1024; training with n == 1 raises ValueError as torch does; n == 0 gives an empty o."""
-    tensors = [("x", x), ("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var), ("residual", residual)]
-    for name, t in tensors[:3]:
-        if t is None:
-            raise ValueError(f"batch_norm_act: {name} is None (a BatchNorm1d with affine parameters is expected)")
-    for name, t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"batch_norm_act: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
-    for name, t in tensors[1:]:
-        if t is not None and t.device != x.device:
-            raise RuntimeError(f"batch_norm_act: {name} is on {t.device}, x on {x.device}")
-    rows = (torch.float32, torch.float16, torch.bfloat16)
-    if x.dim() != 2:
-        raise ValueError(f"batch_norm_act: x must be [n, c], got {tuple(x.shape)}")
-    if x.dtype not in rows:
-        raise TypeError(f"batch_norm_act: x must be f32, f16 or bf16, got {x.dtype}")
-    n, c = x.shape
-    if not 1 <= c <= pointops_cuda.BATCH_NORM_MAX_C:
-        raise ValueError(f"batch_norm_act: c must be in [1, {pointops_cuda.BATCH_NORM_MAX_C}], got x {tuple(x.shape)}")
-    if (running_mean is None) != (running_var is None):
-        raise ValueError(f"batch_norm_act: {'running_mean' if running_mean is None else 'running_var'} is None and the other is not: "
-                         "running_mean and running_var are given together or not at all")
-    for name, t in tensors[1:5]:
-        if t is None:
-            continue
-        if t.dtype != torch.float32:
-            raise TypeError(f"batch_norm_act: {name} must be f32, got {t.dtype}")
-        if tuple(t.shape) != (c,):
-            raise ValueError(f"batch_norm_act: {name} must be [{c}], got {tuple(t.shape)}")
-    if residual is not None:
-        if residual.dtype not in rows:
-            raise TypeError(f"batch_norm_act: residual must be f32, f16 or bf16, got {residual.dtype}")
-        if tuple(residual.shape) != (n, c):
-            raise ValueError(f"batch_norm_act: residual must be [{n}, {c}] like x, got {tuple(residual.shape)}")
-    if act not in ("none", "relu", "leaky_relu", "tanh"):
-        raise ValueError(f"batch_norm_act: act must be 'none', 'relu', 'leaky_relu' or 'tanh', got {act!r}")
     training = bool(training)
-    if training and running_mean is not None and momentum is None:
-        raise ValueError("batch_norm_act: momentum is None (a cumulative average of the running statistics is not supported)")
-    for name, t in tensors:
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"batch_norm_act: {name} must be contiguous")
+    _batch_norm_check("batch_norm_act", x, weight, bias, running_mean, running_var, training, momentum, act, residual)
+    n, c = x.shape
     if training and n == 1:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size((n, c))}")
     need = torch.is_grad_enabled() and any(bool(t.requires_grad) for t in (x, weight, bias))
     return BatchNormAct.apply(x, weight, bias, residual, running_mean, running_var, training, 0.0 if momentum is None else float(momentum),
                               float(eps), act, float(negative_slope), need)
+
+
+class SyncBatchNormAct(Function):
+    """BatchNormAct in training mode with the statistics of every rank's rows (nn.SyncBatchNorm + activation + residual).  Forward: this
+    rank's (count, mean, M2) row, an exact gather of the ranks' rows, their Chan merge in rank order on the device (which also updates
+    the running statistics), the normalise pass.  Backward: this rank's two sums - its weight / bias gradients, which stay LOCAL as in
+    torch's SyncBatchNorm (DDP averages them) -, a gather of the ranks' sums, dx from their sum in rank order and the global count,
+    read on the device.  Saves x, stat [2, C], total [1], weight, bias.  No read-back; the two collectives run whatever n and
+    needs_input_grad are on this rank."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, running_mean, running_var, momentum, eps, act, negative_slope, group, need):
+        from . import sharding
+        n, c = x.shape
+        row = torch.empty((3, c), dtype=torch.float32, device=x.device)
+        pointops_cuda.batch_norm_act_moments(n, c, x, _batch_norm_partials(n, c, 3, x) if n > 0 else None, row)
+        rows = sharding.all_gather_rows(row, group)
+        world = rows.shape[0]
+        stat = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        total = torch.empty((1,), dtype=torch.float32, device=x.device)
+        pointops_cuda.batch_norm_act_merge(world, c, rows, eps, momentum, running_mean, running_var, stat, total)
+        o = torch.empty_like(x)
+        if n > 0:
+            pointops_cuda.batch_norm_act_forward(n, c, x, stat[0], stat[1], False, eps, weight, bias, act, negative_slope, residual, o, None)
+        if need:
+            ctx.save_for_backward(x, stat, total, weight, bias)
+        ctx.args = (act, negative_slope, group)
+        ctx.r_dtype = residual.dtype if residual is not None else None
+        ctx.set_materialize_grads(False)
+        return o
+
+    @staticmethod
+    def backward(ctx, grad_o):
+        from . import sharding
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        if grad_o is None:
+            return (None,) * 12
+        grad_r = grad_o.to(ctx.r_dtype) if need_r and ctx.r_dtype is not None else None
+        if not ctx.saved_tensors:  # nothing but the residual wanted a gradient: on every rank alike, no collective
+            return (None, None, None, grad_r) + (None,) * 8
+        x, stat, total, weight, bias = ctx.saved_tensors
+        act, negative_slope, group = ctx.args
+        n, c = x.shape
+        grad_o = grad_o.contiguous()
+        if n > 0:
+            local = torch.empty((2, c), dtype=torch.float32, device=x.device)
+            pointops_cuda.batch_norm_act_backward(n, c, x, grad_o, stat, weight, bias, act, negative_slope, True, _batch_norm_partials(n, c, 2, x),
+                                                  local[0], local[1], None)
+        else:
+            local = _zeros((2, c), x)
+        sums = sharding.all_gather_rows(local, group)
+        grad_x = torch.empty_like(x)
+        pointops_cuda.batch_norm_act_sync_backward(n, c, x, grad_o, stat, weight, bias, act, negative_slope, sums.shape[0], sums, total, grad_x)
+        return (grad_x if need_x else None, local[0] if need_w else None, local[1] if need_b else None, grad_r) + (None,) * 8
+
+
+def sync_batch_norm_act(x, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, act="none", negative_slope=0.01,
+                        residual=None, group=None):
+    """batch_norm_act in training mode with the batch statistics of ALL ranks of `group` (None: the default group): what nn.SyncBatchNorm
+    followed by the activation and the add computes in training mode, in the fused HIP passes of csrc/batchnorm.hip.  Training mode only:
+    in eval mode SyncBatchNorm does not synchronise, and batch_norm_act is the operator.  Arguments and checks as batch_norm_act's, except:
+      * n == 0 is legal - an empty rank: o and dx are empty, the parameter gradients zero, and the rank takes part in both collectives;
+      * n == 1 is not diagnosed.  torch diagnoses a TOTAL of one row, which takes a read-back of the gathered counts; this operator reads
+        nothing back.  A total of one row gives rstd = 1 / sqrt(eps) and a running variance of NaN (0 / 0).
+    Per call and rank, two small collectives through sharding.all_gather_rows: the (count, mean, M2) rows [3, c] in the forward, the
+    (sum g * xhat, sum g) rows [2, c] in the backward - exact gathers, merged and added on the device strictly in rank order, so every
+    rank computes the same statistics bit for bit and a rerun repeats them.  With gloo the rows are staged through the host; with nccl
+    (RCCL) they stay on the device.  weight and bias receive this rank's sums alone, as in torch's SyncBatchNorm: DDP averages them.
+    With an explicit group of one rank the same path runs and yields batch_norm_act's bits.
+    Counts travel as fp32: a rank's own n >= 2**24 raises ValueError, and the step's total must stay below 2**24 rows as well (not checked:
+    that would be a read-back).  Whether the collectives run depends on nothing but grad mode and the requires_grad flags of x, weight
+    and bias, which must agree on all ranks; the row count and needs_input_grad of a rank never decide it.  As with torch's module, an
+    output that one rank does not use in its loss leaves the other ranks waiting in the backward's gather."""
+    _batch_norm_check("sync_batch_norm_act", x, weight, bias, running_mean, running_var, True, momentum, act, residual)
+    n, c = x.shape
+    if n >= pointops_cuda.BATCH_NORM_MAX_ROWS:
+        raise ValueError(f"sync_batch_norm_act: {n} rows on this rank; the row counts travel as fp32 and are exact below 2**24 = "
+                         f"{pointops_cuda.BATCH_NORM_MAX_ROWS} rows per step")
+    need = torch.is_grad_enabled() and any(bool(t.requires_grad) for t in (x, weight, bias))
+    return SyncBatchNormAct.apply(x, weight, bias, residual, running_mean, running_var, 0.0 if momentum is None else float(momentum), float(eps),
+                                  act, float(negative_slope), group, need)
 
 
 # ---------------------------------------------------------------------------------------------

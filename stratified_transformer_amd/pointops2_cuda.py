@@ -278,6 +278,66 @@ def batch_norm_act_backward(n, c, x, grad_o, stat, weight, bias, act, negative_s
           ptr(weight), ptr(bias), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), ptr(grad_x), opts=opts)
 
 
+# the same norm over several ranks' rows (SyncBatchNorm in training mode): per-rank moments, the merge of the gathered rows, dx from the gathered sums
+BATCH_NORM_MAX_WORLD = 1024
+BATCH_NORM_MAX_ROWS = 2 ** 24  # counts travel as fp32
+
+
+def _batch_norm_world(t, width, c, name):
+    _chk((t, F32, name))
+    world = int(t.shape[0]) if t.dim() == 3 else 0
+    if not 1 <= world <= BATCH_NORM_MAX_WORLD or tuple(t.shape[1:]) != (width, c):
+        raise ValueError(f"{name}: expected shape [1 <= world <= {BATCH_NORM_MAX_WORLD}, {width}, {c}], got {list(t.shape)}")
+    return world
+
+
+def batch_norm_act_moments(n, c, x, partials, row, *, opts=None):
+    """row [3,c] f32 = this rank's (count, mean, M2) per channel <- x [n,c] f32 / f16 / bf16; partials: a [1 <= rows <= 1024, 3, c] f32
+    workspace (None with n == 0, which writes a row of zeros)"""
+    n, c = _batch_norm_sizes(n, c)
+    xt = _row_type(x, "x")
+    _chk((x, x.dtype, "x"), (row, F32, "row"))
+    _shaped(x, (n, c), "x"), _shaped(row, (3, c), "row")
+    rows = 0
+    if partials is not None:
+        rows = _batch_norm_partials(partials, 3, c)
+    elif n > 0:
+        raise ValueError("partials: needed by the row pass (n > 0)")
+    _call("batch_norm_act_moments_launcher", x, n, c, xt, ptr(x), ptr(partials), rows, ptr(row), opts=opts)
+
+
+def batch_norm_act_merge(world, c, rows, eps, momentum, running_mean, running_var, stat, total, *, opts=None):
+    """stat [2,c] f32 = (mean, rstd) of all ranks' rows, total [1] f32 = their number <- rows [world,3,c] f32, merged in rank order;
+    running_mean / running_var [c] f32 (both or neither) take torch's momentum update with the merged moments"""
+    _, c = _batch_norm_sizes(0, c)
+    if _batch_norm_world(rows, 3, c, "rows") != int(world):
+        raise ValueError(f"rows: expected {int(world)} rows (world), got {list(rows.shape)}")
+    _chk((stat, F32, "stat"), (total, F32, "total"))
+    _shaped(stat, (2, c), "stat"), _shaped(total, (1,), "total")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError(f"{'running_mean' if running_mean is None else 'running_var'}: running_mean and running_var are given together or not at all")
+    _opt(running_mean, F32, (c,), "running_mean")
+    _opt(running_var, F32, (c,), "running_var")
+    _call("batch_norm_act_merge_launcher", rows, int(world), c, ptr(rows), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
+          ptr(stat), ptr(total), opts=opts)
+
+
+def batch_norm_act_sync_backward(n, c, x, grad_o, stat, weight, bias, act, negative_slope, world, sums, total, grad_x, *, opts=None):
+    """grad_x [n,c] (x's dtype, fully written) <- x, grad_o [n,c] of one dtype, stat [2,c], weight, bias of the forward, sums [world,2,c]
+    f32 (every rank's (sum g * xhat, sum g), added in rank order) and total [1] f32 (the ranks' summed row count)"""
+    n, c = _batch_norm_sizes(n, c)
+    code = _batch_norm_act(act)
+    xt = _row_type(x, "x")
+    _chk((x, x.dtype, "x"), (grad_o, x.dtype, "grad_o"), (stat, F32, "stat"), (weight, F32, "weight"), (bias, F32, "bias"), (total, F32, "total"),
+         (grad_x, x.dtype, "grad_x"))
+    _shaped(x, (n, c), "x"), _shaped(grad_o, (n, c), "grad_o"), _shaped(stat, (2, c), "stat"), _shaped(weight, (c,), "weight"), _shaped(bias, (c,), "bias")
+    _shaped(total, (1,), "total"), _shaped(grad_x, (n, c), "grad_x")
+    if _batch_norm_world(sums, 2, c, "sums") != int(world):
+        raise ValueError(f"sums: expected {int(world)} rows (world), got {list(sums.shape)}")
+    _call("batch_norm_act_sync_backward_launcher", x, n, c, xt, code, float(negative_slope), ptr(x), ptr(grad_o), ptr(stat), ptr(weight), ptr(bias),
+          int(world), ptr(sums), ptr(total), ptr(grad_x), opts=opts)
+
+
 # csrc/seg_loss.hip (no counterpart in the reference's launcher set: the loss tail of tool/train.py - cross-entropy, L1 shift, IoU counts)
 SEG_LOSS_MAX_C = 64
 SEG_LOSS_PARTIAL_ROWS = 1024  # most workgroups of the forward: one row of `partials` each

@@ -96,6 +96,20 @@ def _all_reduce_sum(t, group):
     return t
 
 
+def all_gather_rows(row, group=None):
+    """row [k, c] of every rank -> [world, k, c] on row's device, rank r's row at r, on every rank: a copy, no arithmetic, so whatever
+    is computed from the result in a fixed order has the same bits on every rank (pointops.sync_batch_norm_act: the per-rank
+    moments and backward sums; never an all_reduce of them, whose order of addition is the backend's).  BYTES_MOVED grows by the bytes
+    of `row`, what this rank hands in, as for the other gathers here."""
+    world = dist.get_world_size(group)
+    staged = row.is_cuda and _host_staged(group)
+    src = row.cpu() if staged else row.contiguous()
+    out = torch.empty((world * src.shape[0],) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    _count(src)
+    _comm("all_gather", dist.all_gather_into_tensor, out, src, group=group)
+    return out.view((world,) + tuple(src.shape)).to(row.device)
+
+
 class _GatherRows(torch.autograd.Function):
     """forward: all-gather row shards (padded to the longest shard, so every backend's fixed-size
     collective applies) into the full [N, ...] tensor; backward: reduce-scatter of the full gradient back
