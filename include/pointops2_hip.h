@@ -42,7 +42,7 @@ const char *pointops2_last_error(void);
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
  * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points, the two
  * pointops2_contacts_*_launcher, pointops2_label_boxes_launcher / pointops2_reach_rows_launcher and the three
- * pointops2_supports_*_launcher, the two pointops2_augment_*_launcher and optim_adamw_step_launcher after them - a caller that needs them looks the symbols up. */
+ * pointops2_supports_*_launcher, the two pointops2_augment_*_launcher optim_adamw_step_launcher and optim_step_launcher after them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -779,6 +779,24 @@ typedef struct pointops2_optim_group {
 size_t pointops2_optim_workspace_bytes(int n_tensors, int n_groups);
 void optim_adamw_step_launcher(int n_tensors, int n_groups, void *host_table, void *workspace, size_t workspace_bytes, const float *scale,
                                float *found_inf, int run_check);
+/* The general step: optim_adamw_step_launcher is optim_step_launcher(POINTOPS2_OPTIM_ADAMW, ..., 0.0, NULL).
+ * kind: POINTOPS2_OPTIM_ADAMW, or POINTOPS2_OPTIM_SGD: torch.optim.SGD's update (dampening = 0, maximize = False) over the same two structs:
+ *       exp_avg is the momentum buffer (zeros before the first step; may be NULL when the group's momentum is 0), exp_avg_sq and step are
+ *       NULL and unused; in the group beta1 is the momentum, beta2 is 1.0 for Nesterov and 0.0 otherwise, eps is unused.
+ * max_norm, grad_norm: max_norm > 0 with a grad_norm (device, 1 float) clips by the global 2-norm as torch.nn.utils.clip_grad_norm_ does:
+ *       *grad_norm = the norm of all the table's gradients after the unscale, summed in float64 in a fixed order (csrc/optim.hip) inside the
+ *       finite check's read, and every gradient enters its update multiplied by float(min(1.0, max_norm / (norm + 1e-6))).  The gradients
+ *       themselves are not written.  max_norm <= 0 or grad_norm == NULL: no clipping, *grad_norm is not touched.
+ * workspace: with clipping at least pointops2_optim_step_workspace_bytes(n_tensors, n_groups, n_chunks) bytes, n_chunks = the sum of
+ *       ceil(numel / POINTOPS2_OPTIM_CHUNK) over the table (one float64 partial per chunk); without it the size above is enough.
+ * At most 4 launches and one copy without clipping and 5 with it; no device-to-host copy and no synchronisation.  Recorded as errors,
+ * nothing enqueued: what optim_adamw_step_launcher refuses (for SGD the NULL rule above), an unknown kind, a NaN max_norm, max_norm > 0 with
+ * a workspace short of the size with n_chunks. */
+#define POINTOPS2_OPTIM_ADAMW 0
+#define POINTOPS2_OPTIM_SGD 1
+size_t pointops2_optim_step_workspace_bytes(int n_tensors, int n_groups, long long n_chunks);
+void optim_step_launcher(int kind, int n_tensors, int n_groups, void *host_table, void *workspace, size_t workspace_bytes, const float *scale,
+                         float *found_inf, int run_check, double max_norm, float *grad_norm);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,7 @@ SIGNATURES = {
     "pointops2_augment_pass_launcher": [I] * 6 + [P] * 10,
     "pointops2_augment_blur_launcher": [Q, I, I, P, P, P],
     "optim_adamw_step_launcher": [I, I, P, P, Z, P, P, I],
+    "optim_step_launcher": [I, I, I, P, P, Z, P, P, I, D, P],
 }
 # entry points with a non-void result
 RESULTS = {
@@ -145,7 +146,10 @@ RESULTS = {
     "pointops2_cell_forward_variant": ([P, I, I, I, I], I),
     "pointops2_evaltile_max_parts": ([], I),
     "pointops2_optim_workspace_bytes": ([I, I], Z),
+    "pointops2_optim_step_workspace_bytes": ([I, I, Q], Z),
 }
+# kind of optim_step_launcher (POINTOPS2_OPTIM_*)
+OPTIM_KINDS = {"adamw": 0, "sgd": 1}
 
 # codes of pointops2_cell_forward_variant (POINTOPS2_CELL_FWD_* of include/pointops2_hip.h): the forward kernel a cell launch runs
 CELL_FWD = {"error": -1, "none": 0, "mfma64": 1, "mfma80": 2, "valu80": 3, "valu160": 4}
