@@ -798,6 +798,23 @@ size_t pointops2_optim_step_workspace_bytes(int n_tensors, int n_groups, long lo
 void optim_step_launcher(int kind, int n_tensors, int n_groups, void *host_table, void *workspace, size_t workspace_bytes, const float *scale,
                          float *found_inf, int run_check, double max_norm, float *grad_norm);
 
+/* ---- residual add + DropPath row scale + LayerNorm on a residual stream of any row type: residual_norm_*_launcher above with the stream
+ * operands x, z, grad_x and grad_z of x_type (POINTOPS2_ROWS_F32, _F16 or _BF16) - under autocast every stage behind a TransitionDown
+ * carries a half stream.  residual_norm_*_launcher is this pair with x_type = POINTOPS2_ROWS_F32: the same bits.  For a 16-bit x_type:
+ *   forward:  x and y are widened exactly, p = fp32(s[n] * y) (s NULL: y), z32 = fp32(x + p), z = z32 rounded ONCE to x_type.  mean_n,
+ *             var_n, stat and o are computed from the STORED z widened back, not from z32: o is the LayerNorm of the tensor the caller
+ *             holds, which the backward reads again.  y NULL: z is x; nothing is rounded, and z (if not NULL) receives a copy of x.
+ *   backward: dz as above, in fp32, from the widened stored z, stat, grad_o and the exactly widened grad_z; grad_x = dz rounded to
+ *             x_type and grad_y = s[n] * dz rounded to y_type, both from the unrounded dz; grad_gamma and grad_beta stay fp32.
+ * Validation, NULL rules, partials, the 64-bit offsets and the n = 0 no-op are those of the fp32 pair, with x_type checked like the other
+ * two row types.  Four channels per lane need c % 4 == 0 and every [n,c] operand aligned for its own type (16 bytes fp32, 8 bytes
+ * half); anything else takes one channel per lane: same results. */
+void residual_norm_stream_forward_launcher(int n, int c, int x_type, int y_type, int o_type, const void *x, const void *y, const float *s,
+                                           const float *gamma, const float *beta, float eps, void *z, void *o, float *stat);
+void residual_norm_stream_backward_launcher(int n, int c, int x_type, int y_type, int o_type, const void *grad_o, const void *grad_z,
+                                            const void *z, const float *stat, const float *s, const float *gamma, void *grad_x, void *grad_y,
+                                            float *partials, int partial_rows, float *grad_gamma, float *grad_beta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,8 @@ SIGNATURES = {
     "pointops2_augment_blur_launcher": [Q, I, I, P, P, P],
     "optim_adamw_step_launcher": [I, I, P, P, Z, P, P, I],
     "optim_step_launcher": [I, I, I, P, P, Z, P, P, I, D, P],
+    "residual_norm_stream_forward_launcher": [I, I, I, I, I, P, P, P, P, P, F, P, P, P],
+    "residual_norm_stream_backward_launcher": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, P],
 }
 # entry points with a non-void result
 RESULTS = {

@@ -9,8 +9,11 @@
 //   backward  xhat = (z - mean) * rstd     g = dO * gamma     dz = rstd * ((g - mean_c(g)) - xhat * mean_c(g * xhat)) + dZ
 //             dx = dz     dy = s[n] * dz     dgamma[c] = sum_n dO * xhat     dbeta[c] = sum_n dO
 //
-// x, z, dx, dZ, gamma, beta, s, stat are fp32 (the residual stream is fp32 with and without autocast); y / dy and o / dO each have one
-// of the three row types POINTOPS2_ROWS_* (what a Linear yields and wants under autocast), widened exactly and rounded once.
+// gamma, beta, s, stat are fp32.  The stream x / z / dx / dZ, y / dy and o / dO each have one of the three row types POINTOPS2_ROWS_*
+// (x_type, y_type, o_type), widened exactly and rounded once.  The stream is fp32 without autocast and in the first stage; behind a
+// TransitionDown under autocast it is half.  With a half stream z is rounded ONCE to the stream type, and mean, variance, stat and o are
+// those of the STORED z widened back - the LayerNorm of the tensor the caller holds, which the backward reads again; dx = round(dz) and
+// dy = round(s * dz) both start from the unrounded fp32 dz.  x_type fp32: the rounding is the identity, the bits are those of the fp32 kernels.
 //
 // Lanes (row_lanes.h): a lane owns a chunk of four channels, a row a power-of-two segment of lanes, 64 / seg rows side by side in a wave;
 // the row sums are an xor butterfly over the aligned segment: every lane of it ends with the same bits, and no value crosses a
@@ -27,10 +30,10 @@ namespace p2 {
 namespace {
 
 template <int VEC, int ITER>
-__global__ __launch_bounds__(RN_THREADS) void rownorm_fwd_kernel(int n, int c, int chunks, int seg, int y_type, int o_type,
-                                                                 const float *__restrict__ x, const void *__restrict__ y,
+__global__ __launch_bounds__(RN_THREADS) void rownorm_fwd_kernel(int n, int c, int chunks, int seg, int x_type, int y_type, int o_type,
+                                                                 const void *__restrict__ x, const void *__restrict__ y,
                                                                  const float *__restrict__ s, const float *__restrict__ gamma,
-                                                                 const float *__restrict__ beta, float eps, float *__restrict__ z,
+                                                                 const float *__restrict__ beta, float eps, void *__restrict__ z,
                                                                  void *__restrict__ o, float *__restrict__ stat) {
     const SegLanes sl(seg);
     bool act[ITER];
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(RN_THREADS) void rownorm_fwd_kernel(int n, int c, i
             for (int e = 0; e < VEC; e++) v[it][e] = 0.0f;
             if (live && act[it]) {
                 const size_t at = (size_t)row * c + (size_t)(sl.chunk0 + it * WAVE) * VEC;
-                load_chunk<VEC>(x, at, POINTOPS2_ROWS_F32, v[it]);
+                load_chunk<VEC>(x, at, x_type, v[it]);
                 if (y != nullptr) {
                     float yv[VEC];
                     load_chunk<VEC>(y, at, y_type, yv);
@@ -69,8 +72,12 @@ __global__ __launch_bounds__(RN_THREADS) void rownorm_fwd_kernel(int n, int c, i
                         const float t = s != nullptr ? sc * yv[e] : yv[e];
                         v[it][e] = v[it][e] + t;
                     }
+                    if (x_type != POINTOPS2_ROWS_F32) {  // (wave-uniform) the row is what the stored z holds
+#pragma unroll
+                        for (int e = 0; e < VEC; e++) v[it][e] = widen16(narrow16(v[it][e], x_type), x_type);
+                    }
                 }
-                if (z != nullptr) store_chunk<VEC>(z, at, POINTOPS2_ROWS_F32, v[it]);
+                if (z != nullptr) store_chunk<VEC>(z, at, x_type, v[it]);
             }
 #pragma unroll
             for (int e = 0; e < VEC; e++) sum += v[it][e];
@@ -102,11 +109,11 @@ __global__ __launch_bounds__(RN_THREADS) void rownorm_fwd_kernel(int n, int c, i
 }
 
 template <int VEC, int ITER>
-__global__ __launch_bounds__(RN_THREADS) void rownorm_bwd_kernel(int n, int c, int chunks, int seg, int y_type, int o_type,
-                                                                 const void *__restrict__ grad_o, const float *__restrict__ grad_z,
-                                                                 const float *__restrict__ z, const float *__restrict__ stat,
+__global__ __launch_bounds__(RN_THREADS) void rownorm_bwd_kernel(int n, int c, int chunks, int seg, int x_type, int y_type, int o_type,
+                                                                 const void *__restrict__ grad_o, const void *__restrict__ grad_z,
+                                                                 const void *__restrict__ z, const float *__restrict__ stat,
                                                                  const float *__restrict__ s, const float *__restrict__ gamma,
-                                                                 float *__restrict__ grad_x, void *__restrict__ grad_y,
+                                                                 void *__restrict__ grad_x, void *__restrict__ grad_y,
                                                                  float *__restrict__ partials) {
     __shared__ float red[2][RN_THREADS * ITER * VEC];
     const SegLanes sl(seg);
@@ -139,7 +146,7 @@ __global__ __launch_bounds__(RN_THREADS) void rownorm_bwd_kernel(int n, int c, i
                 if (live && act[it]) {
                     const size_t at = (size_t)row * c + (size_t)(sl.chunk0 + it * WAVE) * VEC;
                     float zv[VEC], dov[VEC];
-                    load_chunk<VEC>(z, at, POINTOPS2_ROWS_F32, zv);
+                    load_chunk<VEC>(z, at, x_type, zv);
                     load_chunk<VEC>(grad_o, at, o_type, dov);
 #pragma unroll
                     for (int e = 0; e < VEC; e++) {
@@ -167,11 +174,11 @@ __global__ __launch_bounds__(RN_THREADS) void rownorm_bwd_kernel(int n, int c, i
             for (int e = 0; e < VEC; e++) dz[e] = grad_o != nullptr ? rstd * ((g[it][e] - m1) - xh[it][e] * m2) : 0.0f;
             if (grad_z != nullptr) {
                 float rz[VEC];
-                load_chunk<VEC>(grad_z, at, POINTOPS2_ROWS_F32, rz);
+                load_chunk<VEC>(grad_z, at, x_type, rz);
 #pragma unroll
                 for (int e = 0; e < VEC; e++) dz[e] = dz[e] + rz[e];
             }
-            store_chunk<VEC>(grad_x, at, POINTOPS2_ROWS_F32, dz);
+            store_chunk<VEC>(grad_x, at, x_type, dz);  // (grad_y below starts from the unrounded dz)
             if (grad_y != nullptr) {
                 if (s != nullptr) {
 #pragma unroll
@@ -196,10 +203,11 @@ __global__ __launch_bounds__(RED_COLS *RED_GROUPS) void rownorm_param_kernel(int
 }
 
 // nullptr when the arguments are in range
-const char *rownorm_bad_args(int n, int c, int y_type, int o_type) {
+const char *rownorm_bad_args(int n, int c, int x_type, int y_type, int o_type) {
     if (n < 0) return "residual_norm: negative row count";
     if (c < 1 || c > RN_MAX_C) return "residual_norm: c must be in [1, 1024]";
-    if (!known_row_type(y_type) || !known_row_type(o_type)) return "residual_norm: row types must be POINTOPS2_ROWS_F32, _F16 or _BF16";
+    if (!known_row_type(x_type) || !known_row_type(y_type) || !known_row_type(o_type))
+        return "residual_norm: row types must be POINTOPS2_ROWS_F32, _F16 or _BF16";
     return nullptr;  // (n * c: the kernels index with 64-bit offsets)
 }
 
@@ -210,30 +218,30 @@ using namespace p2;
 
 extern "C" {
 
-void residual_norm_forward_launcher(int n, int c, int y_type, int o_type, const float *x, const void *y, const float *s, const float *gamma,
-                                    const float *beta, float eps, float *z, void *o, float *stat) {
+void residual_norm_stream_forward_launcher(int n, int c, int x_type, int y_type, int o_type, const void *x, const void *y, const float *s,
+                                           const float *gamma, const float *beta, float eps, void *z, void *o, float *stat) {
     const hipStream_t st = begin_launch().stream;
-    if (const char *bad = rownorm_bad_args(n, c, y_type, o_type)) { set_error(bad); return; }
+    if (const char *bad = rownorm_bad_args(n, c, x_type, y_type, o_type)) { set_error(bad); return; }
     if (n == 0) return;
     if (x == nullptr || gamma == nullptr || beta == nullptr || o == nullptr || stat == nullptr) {
         set_error("residual_norm_forward: x, gamma, beta, o and stat must not be NULL");
         return;
     }
-    const bool chunked = c % 4 == 0 && aligned_to(x, 16) && aligned_to(z, 16) && aligned_to(gamma, 16) && aligned_to(beta, 16) &&
+    const bool chunked = c % 4 == 0 && rows_aligned(x, x_type) && rows_aligned(z, x_type) && aligned_to(gamma, 16) && aligned_to(beta, 16) &&
                          rows_aligned(y, y_type) && rows_aligned(o, o_type);
     const RowShape sh(c, chunked);
     for_shape(sh, [&](auto tag) {
         hipLaunchKernelGGL((rownorm_fwd_kernel<decltype(tag)::vec, decltype(tag)::iter>), dim3(sh.grid(n, num_cus() * 64)), dim3(RN_THREADS), 0, st,
-                           n, c, sh.chunks, sh.seg, y_type, o_type, x, y, s, gamma, beta, eps, z, o, stat);
+                           n, c, sh.chunks, sh.seg, x_type, y_type, o_type, x, y, s, gamma, beta, eps, z, o, stat);
     });
     check_launch();
 }
 
-void residual_norm_backward_launcher(int n, int c, int y_type, int o_type, const void *grad_o, const float *grad_z, const float *z,
-                                     const float *stat, const float *s, const float *gamma, float *grad_x, void *grad_y, float *partials,
-                                     int partial_rows, float *grad_gamma, float *grad_beta) {
+void residual_norm_stream_backward_launcher(int n, int c, int x_type, int y_type, int o_type, const void *grad_o, const void *grad_z,
+                                            const void *z, const float *stat, const float *s, const float *gamma, void *grad_x, void *grad_y,
+                                            float *partials, int partial_rows, float *grad_gamma, float *grad_beta) {
     const hipStream_t st = begin_launch().stream;
-    if (const char *bad = rownorm_bad_args(n, c, y_type, o_type)) { set_error(bad); return; }
+    if (const char *bad = rownorm_bad_args(n, c, x_type, y_type, o_type)) { set_error(bad); return; }
     if (n == 0) return;
     if (grad_x == nullptr) { set_error("residual_norm_backward: grad_x is NULL"); return; }
     if (grad_o != nullptr && (z == nullptr || stat == nullptr || gamma == nullptr)) {
@@ -245,13 +253,13 @@ void residual_norm_backward_launcher(int n, int c, int y_type, int o_type, const
         set_error("residual_norm_backward: partials needs partial_rows >= 1, grad_gamma and grad_beta");
         return;
     }
-    const bool chunked = c % 4 == 0 && aligned_to(grad_z, 16) && aligned_to(z, 16) && aligned_to(gamma, 16) && aligned_to(grad_x, 16) &&
-                         rows_aligned(grad_o, o_type) && rows_aligned(grad_y, y_type);
+    const bool chunked = c % 4 == 0 && rows_aligned(grad_z, x_type) && rows_aligned(z, x_type) && aligned_to(gamma, 16) &&
+                         rows_aligned(grad_x, x_type) && rows_aligned(grad_o, o_type) && rows_aligned(grad_y, y_type);
     const RowShape sh(c, chunked);
     const int grid = sh.grid(n, sums ? partial_rows : num_cus() * 64);
     for_shape(sh, [&](auto tag) {
         hipLaunchKernelGGL((rownorm_bwd_kernel<decltype(tag)::vec, decltype(tag)::iter>), dim3(grid), dim3(RN_THREADS), 0, st, n, c, sh.chunks,
-                           sh.seg, y_type, o_type, grad_o, grad_z, z, stat, s, gamma, grad_x, grad_y, sums ? partials : nullptr);
+                           sh.seg, x_type, y_type, o_type, grad_o, grad_z, z, stat, s, gamma, grad_x, grad_y, sums ? partials : nullptr);
     });
     if (!check_launch()) return;
     if (sums) {
@@ -259,6 +267,19 @@ void residual_norm_backward_launcher(int n, int c, int y_type, int o_type, const
                            grad_beta);
         check_launch();
     }
+}
+
+// the fp32 stream: the pair above with x_type = POINTOPS2_ROWS_F32
+void residual_norm_forward_launcher(int n, int c, int y_type, int o_type, const float *x, const void *y, const float *s, const float *gamma,
+                                    const float *beta, float eps, float *z, void *o, float *stat) {
+    residual_norm_stream_forward_launcher(n, c, POINTOPS2_ROWS_F32, y_type, o_type, x, y, s, gamma, beta, eps, z, o, stat);
+}
+
+void residual_norm_backward_launcher(int n, int c, int y_type, int o_type, const void *grad_o, const float *grad_z, const float *z,
+                                     const float *stat, const float *s, const float *gamma, float *grad_x, void *grad_y, float *partials,
+                                     int partial_rows, float *grad_gamma, float *grad_beta) {
+    residual_norm_stream_backward_launcher(n, c, POINTOPS2_ROWS_F32, y_type, o_type, grad_o, grad_z, z, stat, s, gamma, grad_x, grad_y, partials,
+                                           partial_rows, grad_gamma, grad_beta);
 }
 
 }  // extern "C"

@@ -39,6 +39,7 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
   * The blocks' glue (off by default): `install_fused_blocks()` / `patch_block_classes()` rebind SwinTransformerBlock.forward of either
     model file to fused_block_forward / swin_fused_block_forward - DropPath, residual add, LayerNorm and the cast in front of the next
     Linear as one pass of pointops.residual_norm (csrc/rownorm.hip) at both residual sites; the four GEMMs and GELU stay with torch.
+    `HALF_STREAM = True` extends it to the half residual stream of the stages behind a TransitionDown under autocast.
 
   * The batch norms of the stem and the heads (off by default): `fuse_batch_norms(model)` binds, per instance, forwards that run every
     BatchNorm1d + activation (+ the ResBlock's shortcut add) as one pointops.batch_norm_act call (csrc/batchnorm.hip).
@@ -66,6 +67,11 @@ SPECULATE = os.environ.get("P2_SPECULATE", "1") != "0"
 # TransitionDown's tail (:106-109) as norm / linear on the N source rows + pointops.grouped_max, instead of on the k gathered copies of
 # every sampled row (install(pooled_transition=True)).  Same maxima up to the fp32 rounding of the Linear's sums taken in another order.
 POOLED_TRANSITION = False
+# The fused block forward (install_fused_blocks) on a HALF residual stream: under autocast every stage behind a TransitionDown carries
+# f16 / bf16 features, which the fused forward otherwise leaves to the original one.  True: such a block runs both sites on
+# pointops.residual_norm_stream when autocast is on with the stream's own dtype.  z is then rounded once per site from the fp32 sum, where
+# the original rounds DropPath's product first: the same tensor up to one rounding of the half type.
+HALF_STREAM = False
 STATS = {"layers": 0, "speculated": 0, "reruns": 0, "transitions_prefetched": 0}
 _CLOUDS = {}  # id(xyz) -> _Cloud
 _FLAG_HOST = {}  # device index -> ring of pinned bool [1] words (speculation checks)
@@ -292,34 +298,43 @@ def _glue_dtype(dev):
 
 def _fused_block(self, feats, attend):
     """the block's forward around attend(norm1 rows) = self.attn(...); None: the conditions of the fused path do not hold"""
-    if not (torch.is_tensor(feats) and feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and 1 <= feats.shape[1] <= 1024):
+    if not (torch.is_tensor(feats) and feats.is_cuda and feats.dim() == 2 and 1 <= feats.shape[1] <= 1024):
+        return None
+    half = feats.dtype in (torch.float16, torch.bfloat16)
+    if not (feats.dtype == torch.float32 or (half and HALF_STREAM)):
         return None
     c = feats.shape[1]
     odt = _glue_dtype(feats.device)
     if odt is None or not (_norm_ok(self.norm1, c) and _norm_ok(self.norm2, c) and _known_drop_path(self.drop_path)):
         return None
+    if half and odt != feats.dtype:          # a half stream without autocast, or under autocast of the other half type
+        return None
+    residual_norm = P.residual_norm_stream if half else P.residual_norm
     handed = self.__dict__.pop("_sta_norm1", None)
     if handed is not None and handed[0] is feats and handed[1].dtype == odt:
         n1 = handed[1]
     else:
-        _, n1 = P.residual_norm(feats.contiguous(), None, None, self.norm1.weight, self.norm1.bias, self.norm1.eps, odt)          # :241
+        _, n1 = residual_norm(feats.contiguous(), None, None, self.norm1.weight, self.norm1.bias, self.norm1.eps, odt)          # :241
     a = attend(n1)                                                                                                                 # :243
     s1 = drop_path_row_scale(self.drop_path, a)
-    z, n2 = P.residual_norm(feats.contiguous(), a.contiguous(), s1, self.norm2.weight, self.norm2.bias, self.norm2.eps, odt)      # :245, norm2 of :246
+    z, n2 = residual_norm(feats.contiguous(), a.contiguous(), s1, self.norm2.weight, self.norm2.bias, self.norm2.eps, odt)      # :245, norm2 of :246
     m = self.mlp(n2)
     s2 = drop_path_row_scale(self.drop_path, m)
     nxt = self.__dict__.get("_sta_next")
     if nxt is not None and _norm_ok(nxt.norm1, c):
-        out, n1_next = P.residual_norm(z, m.contiguous(), s2, nxt.norm1.weight, nxt.norm1.bias, nxt.norm1.eps, odt)              # :246, the next :241
+        out, n1_next = residual_norm(z, m.contiguous(), s2, nxt.norm1.weight, nxt.norm1.bias, nxt.norm1.eps, odt)              # :246, the next :241
         nxt.__dict__["_sta_norm1"] = (out, n1_next)
         return out
+    if half and s2 is not None:              # (s2 is f32: the sum in fp32, one rounding back to the stream's dtype)
+        return (z.float() + m.float() * s2.unsqueeze(1)).to(z.dtype)                                                               # :246
     return z + m if s2 is None else z + m * s2.unsqueeze(1)                                                                       # :246
 
 
 def fused_block_forward(self, feats, xyz, index_0, index_1, index_0_offsets, n_max):
     """Replacement of SwinTransformerBlock.forward (model/stratified_transformer.py:235-248), same arguments, same result: both residual
     sites on pointops.residual_norm.  The original forward runs for CPU tensors, feats that are not [N, C <= 1024] f32, norms that are
-    not nn.LayerNorm with f32 affine parameters over C, and a drop_path that is neither nn.Identity nor a DropPath with `drop_prob`."""
+    not nn.LayerNorm with f32 affine parameters over C, and a drop_path that is neither nn.Identity nor a DropPath with `drop_prob`.
+    With HALF_STREAM, f16 / bf16 feats under autocast of the same dtype take the fused path too, on pointops.residual_norm_stream."""
     out = _fused_block(self, feats, lambda rows: self.attn(rows, xyz, index_0, index_1, index_0_offsets, n_max))
     return out if out is not None else _original(self)(self, feats, xyz, index_0, index_1, index_0_offsets, n_max)
 

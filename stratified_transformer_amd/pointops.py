@@ -1014,6 +1014,39 @@ def grouped_max(feat, idx):
 # ---------------------------------------------------------------------------------------------
 # residual add + DropPath row scale + LayerNorm: the glue between the GEMMs of a pre-norm block (csrc/rownorm.hip)
 # ---------------------------------------------------------------------------------------------
+def _residual_norm_forward(kernel, ctx, x, y, row_scale, weight, bias, eps, out_dtype):
+    n, c = x.shape
+    z = torch.empty_like(x) if y is not None else None
+    o = torch.empty((n, c), dtype=out_dtype, device=x.device)
+    stat = torch.empty((n, 2), dtype=torch.float32, device=x.device)
+    if n > 0:
+        kernel(n, c, x, y, row_scale, weight, bias, eps, z, o, stat)
+    ctx.save_for_backward(x if z is None else z, stat, row_scale, weight)
+    ctx.y_dtype = y.dtype if y is not None else None
+    ctx.set_materialize_grads(False)
+    return o if z is None else (z, o)
+
+
+def _residual_norm_backward(kernel, ctx, grads):
+    z, stat, row_scale, weight = ctx.saved_tensors
+    grad_z, grad_o = (None, grads[0]) if ctx.y_dtype is None else grads
+    n, c = z.shape
+    need_x, need_y, _, need_w, need_b = ctx.needs_input_grad[:5]
+    if grad_z is None and grad_o is None:
+        return (None,) * 7
+    grad_x = torch.empty_like(z)
+    grad_y = torch.empty((n, c), dtype=ctx.y_dtype, device=z.device) if ctx.y_dtype is not None and need_y else None
+    partials = grad_w = grad_b = None
+    if grad_o is not None and (need_w or need_b):
+        rows = min(pointops_cuda.RESIDUAL_NORM_PARTIAL_ROWS, max(1, (n + 3) // 4))
+        partials = torch.empty((rows, 2, c), dtype=torch.float32, device=z.device)
+        grad_w, grad_b = (_zeros((c,), z) if n == 0 else torch.empty_like(weight) for _ in range(2))
+    if n > 0:
+        kernel(n, c, None if grad_o is None else grad_o.contiguous(), None if grad_z is None else grad_z.contiguous(),
+               z, stat, row_scale, weight, grad_x, grad_y, partials, grad_w, grad_b)
+    return (grad_x if need_x else None, grad_y, None, grad_w if need_w else None, grad_b if need_b else None, None, None)
+
+
 class ResidualNorm(Function):
     """(z, o) = (x + row_scale[:, None] * y, LayerNorm(z)) in one pass over the rows, and its backward in one pass plus the small
     kernel that adds the parameter-gradient partials (no float atomics: bitwise reproducible).  With y None the only result is o
@@ -1021,36 +1054,71 @@ class ResidualNorm(Function):
 
     @staticmethod
     def forward(ctx, x, y, row_scale, weight, bias, eps, out_dtype):
-        n, c = x.shape
-        z = torch.empty_like(x) if y is not None else None
-        o = torch.empty((n, c), dtype=out_dtype, device=x.device)
-        stat = torch.empty((n, 2), dtype=torch.float32, device=x.device)
-        if n > 0:
-            pointops_cuda.residual_norm_forward(n, c, x, y, row_scale, weight, bias, eps, z, o, stat)
-        ctx.save_for_backward(x if z is None else z, stat, row_scale, weight)
-        ctx.y_dtype = y.dtype if y is not None else None
-        ctx.set_materialize_grads(False)
-        return o if z is None else (z, o)
+        return _residual_norm_forward(pointops_cuda.residual_norm_forward, ctx, x, y, row_scale, weight, bias, eps, out_dtype)
 
     @staticmethod
     def backward(ctx, *grads):
-        z, stat, row_scale, weight = ctx.saved_tensors
-        grad_z, grad_o = (None, grads[0]) if ctx.y_dtype is None else grads
-        n, c = z.shape
-        need_x, need_y, _, need_w, need_b = ctx.needs_input_grad[:5]
-        if grad_z is None and grad_o is None:
-            return (None,) * 7
-        grad_x = torch.empty_like(z)
-        grad_y = torch.empty((n, c), dtype=ctx.y_dtype, device=z.device) if ctx.y_dtype is not None and need_y else None
-        partials = grad_w = grad_b = None
-        if grad_o is not None and (need_w or need_b):
-            rows = min(pointops_cuda.RESIDUAL_NORM_PARTIAL_ROWS, max(1, (n + 3) // 4))
-            partials = torch.empty((rows, 2, c), dtype=torch.float32, device=z.device)
-            grad_w, grad_b = (_zeros((c,), z) if n == 0 else torch.empty_like(weight) for _ in range(2))
-        if n > 0:
-            pointops_cuda.residual_norm_backward(n, c, None if grad_o is None else grad_o.contiguous(), None if grad_z is None else grad_z.contiguous(),
-                                                 z, stat, row_scale, weight, grad_x, grad_y, partials, grad_w, grad_b)
-        return (grad_x if need_x else None, grad_y, None, grad_w if need_w else None, grad_b if need_b else None, None, None)
+        return _residual_norm_backward(pointops_cuda.residual_norm_backward, ctx, grads)
+
+
+class ResidualNormStream(Function):
+    """ResidualNorm on a residual stream of any row type: x, z and their gradients share one dtype of f32, f16 or bf16"""
+
+    @staticmethod
+    def forward(ctx, x, y, row_scale, weight, bias, eps, out_dtype):
+        return _residual_norm_forward(pointops_cuda.residual_norm_stream_forward, ctx, x, y, row_scale, weight, bias, eps, out_dtype)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return _residual_norm_backward(pointops_cuda.residual_norm_stream_backward, ctx, grads)
+
+
+_ROW_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _residual_norm_checked(op, stream_dtypes, x, y, row_scale, weight, bias, out_dtype):
+    """the host-side rejections of `op` (residual_norm / residual_norm_stream) -> the dtype of o"""
+    tensors = [("x", x), ("y", y), ("row_scale", row_scale), ("weight", weight), ("bias", bias)]
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{op}: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+    for name, t in tensors[1:]:
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{op}: {name} is on {t.device}, x on {x.device}")
+    if x.dim() != 2:
+        raise ValueError(f"{op}: x must be [n, c], got {tuple(x.shape)}")
+    if x.dtype not in stream_dtypes:
+        want = "f32 (the residual stream)" if len(stream_dtypes) == 1 else "f32, f16 or bf16"
+        raise TypeError(f"{op}: x must be {want}, got {x.dtype}")
+    n, c = x.shape
+    if not 1 <= c <= 1024:
+        raise ValueError(f"{op}: c must be in [1, 1024], got x {tuple(x.shape)}")
+    if y is not None:
+        if y.dtype not in _ROW_DTYPES:
+            raise TypeError(f"{op}: y must be f32, f16 or bf16, got {y.dtype}")
+        if tuple(y.shape) != (n, c):
+            raise ValueError(f"{op}: y must be [{n}, {c}] like x, got {tuple(y.shape)}")
+    if row_scale is not None:
+        if y is None:
+            raise ValueError(f"{op}: row_scale needs y")
+        if row_scale.dtype != torch.float32:
+            raise TypeError(f"{op}: row_scale must be f32, got {row_scale.dtype}")
+        if tuple(row_scale.shape) != (n,):
+            raise ValueError(f"{op}: row_scale must be [{n}], got {tuple(row_scale.shape)}")
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t is None:
+            raise ValueError(f"{op}: {name} is None (a LayerNorm with affine parameters is expected)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{op}: {name} must be f32, got {t.dtype}")
+        if tuple(t.shape) != (c,):
+            raise ValueError(f"{op}: {name} must be [{c}], got {tuple(t.shape)}")
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    if out_dtype not in _ROW_DTYPES:
+        raise TypeError(f"{op}: out_dtype must be f32, f16 or bf16, got {out_dtype}")
+    for name, t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous")
+    return out_dtype
 
 
 def residual_norm(x, y, row_scale, weight, bias, eps=1e-5, out_dtype=None):
@@ -1059,46 +1127,19 @@ def residual_norm(x, y, row_scale, weight, bias, eps=1e-5, out_dtype=None):
     x [n, c] f32 (the residual stream); y [n, c] f32, f16 or bf16, or None (z is x itself); row_scale [n] f32 or None (DropPath:
     mask / keep_prob; needs y); weight, bias [c] f32; out_dtype: the dtype of o, f32 (None), f16 or bf16.  z is f32.  All arithmetic
     in fp32, mean and variance by two passes.  Differentiable w.r.t. x, y, weight and bias.  1 <= c <= 1024."""
-    tensors = [("x", x), ("y", y), ("row_scale", row_scale), ("weight", weight), ("bias", bias)]
-    for name, t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"residual_norm: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
-    for name, t in tensors[1:]:
-        if t is not None and t.device != x.device:
-            raise RuntimeError(f"residual_norm: {name} is on {t.device}, x on {x.device}")
-    if x.dim() != 2:
-        raise ValueError(f"residual_norm: x must be [n, c], got {tuple(x.shape)}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"residual_norm: x must be f32 (the residual stream), got {x.dtype}")
-    n, c = x.shape
-    if not 1 <= c <= 1024:
-        raise ValueError(f"residual_norm: c must be in [1, 1024], got x {tuple(x.shape)}")
-    if y is not None:
-        if y.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f"residual_norm: y must be f32, f16 or bf16, got {y.dtype}")
-        if tuple(y.shape) != (n, c):
-            raise ValueError(f"residual_norm: y must be [{n}, {c}] like x, got {tuple(y.shape)}")
-    if row_scale is not None:
-        if y is None:
-            raise ValueError("residual_norm: row_scale needs y")
-        if row_scale.dtype != torch.float32:
-            raise TypeError(f"residual_norm: row_scale must be f32, got {row_scale.dtype}")
-        if tuple(row_scale.shape) != (n,):
-            raise ValueError(f"residual_norm: row_scale must be [{n}], got {tuple(row_scale.shape)}")
-    for name, t in (("weight", weight), ("bias", bias)):
-        if t is None:
-            raise ValueError(f"residual_norm: {name} is None (a LayerNorm with affine parameters is expected)")
-        if t.dtype != torch.float32:
-            raise TypeError(f"residual_norm: {name} must be f32, got {t.dtype}")
-        if tuple(t.shape) != (c,):
-            raise ValueError(f"residual_norm: {name} must be [{c}], got {tuple(t.shape)}")
-    out_dtype = torch.float32 if out_dtype is None else out_dtype
-    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise TypeError(f"residual_norm: out_dtype must be f32, f16 or bf16, got {out_dtype}")
-    for name, t in tensors:
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"residual_norm: {name} must be contiguous")
+    out_dtype = _residual_norm_checked("residual_norm", (torch.float32,), x, y, row_scale, weight, bias, out_dtype)
     out = ResidualNorm.apply(x, y, row_scale, weight, bias, float(eps), out_dtype)
+    return (x, out) if y is None else out
+
+
+def residual_norm_stream(x, y, row_scale, weight, bias, eps=1e-5, out_dtype=None):
+    """residual_norm on a residual stream of any row type: x [n, c] f32, f16 or bf16 (under autocast every stage behind a TransitionDown
+    carries a half stream), z in x's dtype; y and o are typed independently, as there.  With a half x: z = x + row_scale[:, None] * y in
+    fp32, rounded once to x's dtype, and o is the LayerNorm of z as stored - what F.layer_norm(z) computes and the backward reads again;
+    the gradients of x and y are each rounded once from the fp32 gradient.  An f32 x gives residual_norm's bits.  Differentiable w.r.t.
+    x, y, weight and bias.  1 <= c <= 1024."""
+    out_dtype = _residual_norm_checked("residual_norm_stream", _ROW_DTYPES, x, y, row_scale, weight, bias, out_dtype)
+    out = ResidualNormStream.apply(x, y, row_scale, weight, bias, float(eps), out_dtype)
     return (x, out) if y is None else out
 
 

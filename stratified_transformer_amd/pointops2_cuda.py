@@ -176,6 +176,13 @@ def residual_norm_backward(n, c, grad_o, grad_z, z, stat, row_scale, weight, gra
     _opt(grad_y, None if grad_y is None else grad_y.dtype, (n, c), "grad_y")
     _opt(grad_z, F32, (n, c), "grad_z")
     _opt(row_scale, F32, (n,), "row_scale")
+    rows = _residual_norm_partial_rows(c, partials, grad_weight, grad_bias)
+    _call("residual_norm_backward_launcher", z, n, c, yt, ot, ptr(grad_o), ptr(grad_z), ptr(z), ptr(stat), ptr(row_scale), ptr(weight),
+          ptr(grad_x), ptr(grad_y), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), opts=opts)
+
+
+def _residual_norm_partial_rows(c, partials, grad_weight, grad_bias):
+    """the rows of the parameter gradients' workspace (0: none wanted), the three tensors checked"""
     rows = 0
     if partials is not None or grad_weight is not None or grad_bias is not None:
         for t, name in ((partials, "partials"), (grad_weight, "grad_weight"), (grad_bias, "grad_bias")):
@@ -186,7 +193,52 @@ def residual_norm_backward(n, c, grad_o, grad_z, z, stat, row_scale, weight, gra
         rows = int(partials.shape[0]) if partials.dim() == 3 else 0
         if not 1 <= rows <= RESIDUAL_NORM_PARTIAL_ROWS or tuple(partials.shape[1:]) != (2, c):
             raise ValueError(f"partials: expected shape [1 <= rows <= {RESIDUAL_NORM_PARTIAL_ROWS}, 2, {c}], got {list(partials.shape)}")
-    _call("residual_norm_backward_launcher", z, n, c, yt, ot, ptr(grad_o), ptr(grad_z), ptr(z), ptr(stat), ptr(row_scale), ptr(weight),
+    return rows
+
+
+def _stream_type(first, others):
+    """the row type of the residual stream: `first` (name, tensor) names it, every other stream tensor given must share its dtype"""
+    xt = _row_type(first[1], first[0])
+    for name, t in others:
+        if t is not None and t.dtype != first[1].dtype:
+            raise TypeError(f"{name}: expected {first[1].dtype} like {first[0]} (the stream tensors share one dtype), got {t.dtype}")
+    return xt
+
+
+def residual_norm_stream_forward(n, c, x, y, row_scale, weight, bias, eps, z, o, stat, *, opts=None):
+    """residual_norm_forward with x and z [n,c] of one dtype of f32 / f16 / bf16 (the residual stream): z = x + row_scale[:, None] * y
+    rounded once to that dtype, o = LayerNorm(z as stored), stat = (mean, rstd) per row"""
+    n, c = _residual_norm_sizes(n, c)
+    xt = _stream_type(("x", x), (("z", z),))
+    _chk((x, x.dtype, "x"), (weight, F32, "weight"), (bias, F32, "bias"), (stat, F32, "stat"))
+    _shaped(x, (n, c), "x"), _shaped(weight, (c,), "weight"), _shaped(bias, (c,), "bias"), _shaped(stat, (n, 2), "stat")
+    ot = _row_type(o, "o")
+    _opt(o, o.dtype, (n, c), "o")
+    yt = _row_type(y, "y") if y is not None else _lib.ROW_TYPES[F32]
+    _opt(y, None if y is None else y.dtype, (n, c), "y")
+    _opt(row_scale, F32, (n,), "row_scale")
+    _opt(z, x.dtype, (n, c), "z")
+    if row_scale is not None and y is None:
+        raise ValueError("row_scale: given without y")
+    _call("residual_norm_stream_forward_launcher", x, n, c, xt, yt, ot, ptr(x), ptr(y), ptr(row_scale), ptr(weight), ptr(bias), float(eps), ptr(z),
+          ptr(o), ptr(stat), opts=opts)
+
+
+def residual_norm_stream_backward(n, c, grad_o, grad_z, z, stat, row_scale, weight, grad_x, grad_y, partials, grad_weight, grad_bias, *, opts=None):
+    """residual_norm_backward with z, grad_z (or None) and grad_x [n,c] of one dtype of f32 / f16 / bf16 (the residual stream); grad_x and
+    grad_y are each rounded once from the fp32 gradient.  Every output is fully written."""
+    n, c = _residual_norm_sizes(n, c)
+    xt = _stream_type(("z", z), (("grad_z", grad_z), ("grad_x", grad_x)))
+    _chk((z, z.dtype, "z"), (stat, F32, "stat"), (weight, F32, "weight"), (grad_x, z.dtype, "grad_x"))
+    _shaped(z, (n, c), "z"), _shaped(stat, (n, 2), "stat"), _shaped(weight, (c,), "weight"), _shaped(grad_x, (n, c), "grad_x")
+    ot = _row_type(grad_o, "grad_o") if grad_o is not None else _lib.ROW_TYPES[F32]
+    _opt(grad_o, None if grad_o is None else grad_o.dtype, (n, c), "grad_o")
+    yt = _row_type(grad_y, "grad_y") if grad_y is not None else _lib.ROW_TYPES[F32]
+    _opt(grad_y, None if grad_y is None else grad_y.dtype, (n, c), "grad_y")
+    _opt(grad_z, z.dtype, (n, c), "grad_z")
+    _opt(row_scale, F32, (n,), "row_scale")
+    rows = _residual_norm_partial_rows(c, partials, grad_weight, grad_bias)
+    _call("residual_norm_stream_backward_launcher", z, n, c, xt, yt, ot, ptr(grad_o), ptr(grad_z), ptr(z), ptr(stat), ptr(row_scale), ptr(weight),
           ptr(grad_x), ptr(grad_y), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), opts=opts)
 
 
