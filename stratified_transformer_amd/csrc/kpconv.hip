@@ -3,6 +3,7 @@
 // (modules/KPConv/kernels.py, kernel_utils.py: KPConv_ops) - third party, not under the reference: PARITY UNPINNED.
 //
 //   w[i,k,n]  = max(0, 1 - |(support[j] - query[i]) - K[k]| / extent),  j = neighbors[i,n], 0 for j outside [0, n_s)
+//               (max as torch.clamp(min=0): a NaN coordinate gives a NaN influence; an infinitely distant point weighs 0)
 //   wf[i,k,:] = sum_n w[i,k,n] * feat[j,:]                              forward  (this file)
 //   gf[j,:]  += sum_k w[i,k,n] * grad_wf[i,k,:]                         backward (this file; w recomputed)
 // The product of wf [n_q, K*c] with the layer's weight [K*c, out] and its two gradients are matrix products (pointops.py).
@@ -70,7 +71,8 @@ __device__ __forceinline__ int stage_query(int i, int n_s, int n_nb, int n_kp, f
             const int k = small_div(t, inv_nv), n = t - k * n_valid;
             const float dx = rel[n] - kp[3 * k], dy = rel[n_nb + n] - kp[3 * k + 1], dz = rel[2 * n_nb + n] - kp[3 * k + 2];
             const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-            w[k * ws + n] = fmaxf(0.0f, 1.0f - d / extent);
+            const float v = 1.0f - d / extent;
+            w[k * ws + n] = v < 0.0f ? 0.0f : v;  // torch.clamp(min=0): a NaN stays NaN (fmaxf would give 0)
         }
     }
     return n_valid;

@@ -916,7 +916,8 @@ def kpconv(query_xyz, support_xyz, neighbors, feat, k_points, weight, extent):
     the shadow point of torch_points3d - are skipped); k_points [n_kp, 3]; weight [n_kp, c, out]; extent = the influence radius
     of a kernel point (KPConvLayer.point_influence).  feat may be f16 / bf16 (autocast): its rows are widened, the arithmetic and the
     result are fp32 and autograd casts the gradient back (as `_gather_operands` does for interpolation).  Differentiable w.r.t.
-    feat and weight only.  1 <= c <= 64, 1 <= n_nb <= 64, n_kp <= 32.  Third-party semantics (torch_points3d 1.3.0): PARITY UNPINNED."""
+    feat and weight only.  1 <= c <= 64, 1 <= n_nb <= 64, n_kp <= 32.  Non-finite values follow torch.clamp(min=0): a NaN coordinate
+    gives NaN influences (Inf - Inf too), an infinitely distant point weighs exactly 0, and a skipped entry reads no row.  Third-party semantics (torch_points3d 1.3.0): PARITY UNPINNED."""
     named = (("query_xyz", query_xyz), ("support_xyz", support_xyz), ("neighbors", neighbors), ("feat", feat), ("k_points", k_points), ("weight", weight))
     for name, t in named:
         if not t.is_cuda:
