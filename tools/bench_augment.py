@@ -20,7 +20,6 @@ Per (chain, shape, dtype):
 """
 import argparse
 import json
-import os
 import statistics
 import sys
 import time
@@ -28,39 +27,13 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import augment as A, scene  # noqa: E402
 from tests import augment_cases as cases  # noqa: E402
 from tests import augment_oracle as O  # noqa: E402
 
 NOT_MEASURED = ["a per-kernel profile (no run under rocprofv3 was taken)", "batches of more than 6 scenes", "achieved bytes per second",
                 "the loader's end-to-end step time with and without the device chain"]
-
-
-def spread(ts):
-    q = statistics.quantiles(ts, n=4)
-    return [round(min(ts), 4), round(q[0], 4), round(q[2], 4), round(max(ts), 4)]
-
-
-def timed_pair(fns, reps, warmup):
-    """alternate the callables; -> per callable (device ms list, host ms list, last result)"""
-    dev = [[] for _ in fns]
-    host = [[] for _ in fns]
-    out = [None] * len(fns)
-    for it in range(warmup + reps):
-        for k, fn in enumerate(fns):
-            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            start.record()
-            out[k] = fn()
-            end.record()
-            torch.cuda.synchronize()
-            if it >= warmup:
-                dev[k].append(start.elapsed_time(end))
-                host[k].append((time.perf_counter() - t0) * 1e3)
-    return [(dev[k], host[k], out[k]) for k in range(len(fns))]
 
 
 # ---- the chains as plain torch ops on one scene (storage dtype), replaying the draws `d` (tests/augment_cases.scene_draws' layout) ----
@@ -205,8 +178,8 @@ def measure(spec, coord_h, feat_h, ends, dtype, reps, warmup, host_reps):
     rng, gen = np.random.default_rng(0), torch.Generator(device="cuda").manual_seed(0)
     t(coord, feat, offset, rng=rng, generator=gen)
     records = t.last_draws.records
-    (fd, fh, _), (td, th, tres) = timed_pair([lambda: t(coord, feat, offset, rng=rng, generator=gen),
-                                             lambda: torch_batch(spec, coord, feat, ends, records)], reps, warmup)
+    (fd, fh, _), (td, th, tres) = timing.calls([lambda: t(coord, feat, offset, rng=rng, generator=gen),
+                                               lambda: torch_batch(spec, coord, feat, ends, records)], reps, warmup)
     got = t(coord, feat, offset, draws=A.Draws(records))
     diff = max(float((got[0] - tres[0]).abs().nan_to_num(0).max()), float((got[1] - tres[1]).abs().nan_to_num(0).max()))
     draws, lo = [], 0
@@ -226,8 +199,8 @@ def measure(spec, coord_h, feat_h, ends, dtype, reps, warmup, host_reps):
     same = bool(cases.same_bits(got[0].cpu().numpy(), hc.astype(coord_h.dtype if dtype == torch.float64 else np.float32))
                 and cases.same_bits(got[1].cpu().numpy(), hf.astype(np.float64 if dtype == torch.float64 else np.float32)))
     return {"rows": int(ends[-1]), "scenes": len(ends), "dtype": str(dtype).split(".")[1], "passes": t.last_counts["passes"],
-            "readbacks": t.last_counts["readbacks"], "fused_ms": round(statistics.median(fd), 4), "fused_ms_spread": spread(fd),
-            "fused_host_ms": round(statistics.median(fh), 4), "torch_ms": round(statistics.median(td), 4), "torch_ms_spread": spread(td),
+            "readbacks": t.last_counts["readbacks"], "fused_ms": round(statistics.median(fd), 4), "fused_ms_spread": timing.spread(fd),
+            "fused_host_ms": round(statistics.median(fh), 4), "torch_ms": round(statistics.median(td), 4), "torch_ms_spread": timing.spread(td),
             "torch_host_ms": round(statistics.median(th), 4), "torch_max_diff": diff, "host_ms": round(statistics.median(host_t), 2),
             "host_ms_spread": [round(min(host_t), 2), round(max(host_t), 2)], "host_upload_ms": round(statistics.median(up_t), 3),
             "bitwise_equal_to_host": same, "torch_over_fused": round(statistics.median(td) / statistics.median(fd), 2),
@@ -243,8 +216,7 @@ def main():
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_augment: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_augment")
     if a.reps < 20:
         raise SystemExit("bench_augment: at least 20 timed calls")
     rooms = [scene.make_room(a.points, seed=s).astype(np.float64) for s in range(a.scenes)]
@@ -261,11 +233,7 @@ def main():
                 result["results"][key] = measure(spec, c, f, ends, dtype, a.reps, a.warmup, a.host_reps)
                 print(key, json.dumps(result["results"][key]), file=sys.stderr, flush=True)
     result["not_measured"] = NOT_MEASURED
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -25,14 +25,11 @@ move, from the shapes (fused_bytes below); `achieved_bytes_per_s` = those bytes 
 included, so it is a call's rate, not a kernel's.  `faster_beyond_spread`: composite - fused > the composite's spread.
 """
 import argparse
-import json
-import os
 import statistics
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import compat, layers, pipeline, pointops as P, scene, standin  # noqa: E402
 
 DROP = 0.3
@@ -45,30 +42,6 @@ def fused_bytes(n, c, half):
     fwd = n * (4 * c + b * c + 4 + 4 * c + b * c + 8)
     bwd = n * (b * c + 4 * c + 4 * c + 8 + 4 + 4 * c + b * c)
     return fwd, bwd
-
-
-def windows(sides, reps, warmup, inner):
-    """sides: name -> fn(); -> name -> list of ms per iteration, the sides alternating window by window"""
-    times = {s: [] for s in sides}
-    for it in range(warmup + reps):
-        for s, fn in sides.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            if it >= warmup:
-                times[s].append(e0.elapsed_time(e1) / inner)
-    return times
-
-
-def summary(times, base, new):
-    r = {base + "_ms": round(statistics.median(times[base]), 5), new + "_ms": round(statistics.median(times[new]), 5),
-         base + "_spread_ms": round(max(times[base]) - min(times[base]), 5), new + "_spread_ms": round(max(times[new]) - min(times[new]), 5)}
-    r["ratio"] = round(r[base + "_ms"] / r[new + "_ms"], 3)
-    r["faster_beyond_spread"] = bool(r[base + "_ms"] - r[new + "_ms"] > r[base + "_spread_ms"])
-    return r
 
 
 def operator_case(n, c, amp, a):
@@ -102,8 +75,8 @@ def operator_case(n, c, amp, a):
     row = {"n": n, "c": c, "max_abs_diff_z": float((zc - zf).abs().max()), "max_abs_diff_o": float((oc.float() - of.float()).abs().max())}
     fwd_b, bwd_b = fused_bytes(n, c, amp)
     with torch.no_grad():
-        row["fwd"] = summary(windows({"composite": composite, "fused": fused}, a.reps, a.warmup, a.inner), "composite", "fused")
-    row["fwd_bwd"] = summary(windows({"composite": with_backward(composite), "fused": with_backward(fused)}, a.reps, a.warmup, a.inner), "composite", "fused")
+        row["fwd"] = timing.summary(timing.windows({"composite": composite, "fused": fused}, a.reps, a.warmup, a.inner), "composite", "fused")
+    row["fwd_bwd"] = timing.summary(timing.windows({"composite": with_backward(composite), "fused": with_backward(fused)}, a.reps, a.warmup, a.inner), "composite", "fused")
     row["fwd"]["bytes"], row["fwd_bwd"]["bytes"] = fwd_b, fwd_b + bwd_b
     for k in ("fwd", "fwd_bwd"):
         row[k]["achieved_bytes_per_s"] = round(row[k]["bytes"] / (row[k]["fused_ms"] * 1e-3), 1)
@@ -146,7 +119,7 @@ def half_stream_site(n, c, dt, a):
         zf, of = fused()
     assert zc.dtype == zf.dtype == oc.dtype == of.dtype == dt
     row = {"n": n, "c": c, "max_abs_diff_z": float((zc.float() - zf.float()).abs().max()), "max_abs_diff_o": float((oc.float() - of.float()).abs().max())}
-    row["fwd_bwd"] = summary(windows({"composite": with_backward(composite), "fused": with_backward(fused)}, a.reps, a.warmup, a.inner), "composite", "fused")
+    row["fwd_bwd"] = timing.summary(timing.windows({"composite": with_backward(composite), "fused": with_backward(fused)}, a.reps, a.warmup, a.inner), "composite", "fused")
     row["fwd_bwd"]["bytes"] = sum(stream_bytes(n, c))
     row["fwd_bwd"]["achieved_bytes_per_s"] = round(row["fwd_bwd"]["bytes"] / (row["fwd_bwd"]["fused_ms"] * 1e-3), 1)
     return row
@@ -182,7 +155,7 @@ def half_stream_blocks(a):
 
     try:
         layers.patch_classes(standin.BasicLayer, standin.WindowAttention, standin.TransitionDown)
-        times = windows({"unpatched": unpatched, "patched_half_stream_off": patched(False), "patched_half_stream_on": patched(True)}, a.reps, a.warmup, 1)
+        times = timing.windows({"unpatched": unpatched, "patched_half_stream_off": patched(False), "patched_half_stream_on": patched(True)}, a.reps, a.warmup, 1)
     finally:
         layers.HALF_STREAM = False
         layers.uninstall_fast_layers()
@@ -246,7 +219,7 @@ def blocks_leg(a, amp):
 
     try:
         layers.patch_classes(standin.BasicLayer, standin.WindowAttention, standin.TransitionDown)
-        r = summary(windows({"unpatched": unpatched, "patched": patched}, a.reps, a.warmup, 1), "unpatched", "patched")
+        r = timing.summary(timing.windows({"unpatched": unpatched, "patched": patched}, a.reps, a.warmup, 1), "unpatched", "patched")
     finally:
         layers.uninstall_fast_layers()
     # Under autocast TransitionDown's Linear hands the later stages HALF features: their residual stream is half, which the fused
@@ -281,8 +254,7 @@ def main():
     a = ap.parse_args()
     if a.reps < 5:
         raise SystemExit("bench_block: at least five repeats a side")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_block: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_block")
     if a.trace_loop:
         # for a run of its own under `rocprofv3 --kernel-trace --stats -- python tools/bench_block.py --trace-loop 160`: the fused site only
         for n, c in zip(_stage_rows(a.points, pipeline.s3dis_config()), (48, 96, 192, 384)):
@@ -303,12 +275,7 @@ def main():
         if not a.skip_blocks:
             result["blocks"]["autocast_f16"] = half_stream_blocks(a)
         result["not_measured"] = ["a counter profile", "bf16 timings beyond one site", "the unmodified model end to end"]
-        line = json.dumps(result)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "w") as f:
-                f.write(line + "\n")
-        return
+        return timing.emit(result, a.out)
     result = {"tool": "bench_block", "device": torch.cuda.get_device_name(0), "points": a.points, "drop_prob": DROP, "reps": a.reps, "warmup": a.warmup,
               "inner": a.inner, "operator": {}, "blocks": {}}
     rows = _stage_rows(a.points, pipeline.s3dis_config())
@@ -318,11 +285,7 @@ def main():
             result["blocks"][mode] = blocks_leg(a, amp)
     stage0 = [result["operator"][m][0]["fwd_bwd"]["faster_beyond_spread"] for m in ("fp32", "autocast_f16")]
     result["stage0_fwd_bwd_faster_beyond_spread"] = bool(all(stage0))
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

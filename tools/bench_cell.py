@@ -5,7 +5,7 @@ Meant to be run under `rocprofv3 --kernel-trace --stats` for per-kernel times (d
 """
 import os, sys
 import torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import scene, pipeline, fused
 
 
@@ -47,4 +47,5 @@ def main():
                   'fwd us', round(tf / reps * 1e3), 'bwd us', round(tb / reps * 1e3), flush=True)
 
 
-main()
+if __name__ == "__main__":
+    main()

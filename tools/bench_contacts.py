@@ -11,16 +11,13 @@ events around the call; objects() ends in a read-back, so `objects_host_ms` give
 with one scipy.spatial.distance.cdist per (edge instance, face instance) as the reference computes it, on the same instances and the
 same machine (median of 3; needs scipy).  The per-kernel split is taken in a run of its own under `rocprofv3 --kernel-trace --stats`."""
 import argparse
-import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import cluster  # noqa: E402
 
 FACE = {0: (2, 1), 5: (2, 0), 1: (0, 1), 4: (0, 0), 2: (1, 1), 3: (1, 0)}   # face class -> (axis, side)
@@ -65,23 +62,6 @@ def make_scene(points, seed=0):
     return coord[perm], pred[perm], n_boxes
 
 
-def device_ms(fn, reps, warmup):
-    """-> (median device ms, median host ms, last result)"""
-    dev_t, host_t, out = [], [], None
-    for it in range(warmup + reps):
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        start.record()
-        out = fn()
-        end.record()
-        torch.cuda.synchronize()
-        if it >= warmup:
-            dev_t.append(start.elapsed_time(end))
-            host_t.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(dev_t), statistics.median(host_t), out
-
-
 def host_loop(coord, instance, cls, size):
     """the reference's pairing loop with its dense cdist per pair -> the list of linked face instances per edge"""
     from scipy.spatial import distance
@@ -113,21 +93,20 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the host loop (the profiler run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_contacts: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_contacts")
     coord_h, pred_h, n_boxes = make_scene(a.points)
     coord, pred = torch.from_numpy(coord_h).cuda(), torch.from_numpy(pred_h).cuda()
     instance, cls, size = cluster.instances(coord, torch.zeros_like(coord), pred)
     n_inst = int(cls.numel())
 
-    objects_ms, objects_host_ms, (obj, object_of, n_objects) = device_ms(lambda: cluster.objects(coord, instance, cls, size), a.reps, a.warmup)
+    objects_ms, objects_host_ms, (obj, object_of, n_objects) = timing.device_ms(lambda: cluster.objects(coord, instance, cls, size), a.reps, a.warmup)
     objects_calls = dict(cluster.LAST_CONTACTS)
-    contacts_ms, contacts_host_ms, (count, min_d2) = device_ms(lambda: cluster.contacts(coord, instance, 0.08, n_inst), a.reps, a.warmup)
+    contacts_ms, contacts_host_ms, (count, min_d2) = timing.device_ms(lambda: cluster.contacts(coord, instance, 0.08, n_inst), a.reps, a.warmup)
     contacts_calls = dict(cluster.LAST_CONTACTS)
     call = cluster._Call("objects", cluster.LAST_CONTACTS, coord, instance)         # objects' count step, on its prologue's result
     r, r2 = cluster._radius(call.who, 0.08)
     p = cluster._labelled(call, coord, instance, n_inst)
-    count_ms, count_host_ms, _ = device_ms(lambda: cluster._contact_tables(call, p, r, r2, False), a.reps, a.warmup)
+    count_ms, count_host_ms, _ = timing.device_ms(lambda: cluster._contact_tables(call, p, r, r2, False), a.reps, a.warmup)
 
     result = {"tool": "bench_contacts", "device": torch.cuda.get_device_name(0), "points": len(coord_h), "boxes": n_boxes,
               "edge_point_share": round(float((pred_h >= 6).mean()), 4), "instances": n_inst, "face_instances": int((cls < 6).sum()),
@@ -149,11 +128,7 @@ def main():
         result["host_loop_links"] = len(pairs)
         linked = sorted({k for p in pairs for k in p})
         result["host_loop_agrees"] = bool(linked == np.nonzero((object_of.cpu().numpy() >= 0) & (cls_h < 6))[0].tolist())
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

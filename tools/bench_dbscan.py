@@ -11,16 +11,13 @@ components_and_ranking: every round with its read-back, then the ranking of the 
 the first launch is in total_ms only.
 `instances_ms`: cluster.instances on the same cloud with a zero shift."""
 import argparse
-import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import _lib, cluster, scene  # noqa: E402
 
 # a phase runs from its launcher's call to the next launcher's call, so it holds the torch work that follows the launch as well
@@ -35,14 +32,6 @@ def classes_by_position(xyz, n_classes=8):
     u = np.minimum(((xyz[:, 0] - lo[0]) / (hi[0] - lo[0]) * 4).astype(np.int64), 3)
     v = np.minimum(((xyz[:, 1] - lo[1]) / (hi[1] - lo[1]) * 2).astype(np.int64), 1)
     return (u * 2 + v) % n_classes
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
 
 
 def phase_times(fn):
@@ -74,23 +63,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_dbscan: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_dbscan")
     room = scene.make_room(a.points, 0)
     pred_h = classes_by_position(room)
     xyz, pred = torch.from_numpy(room).cuda(), torch.from_numpy(pred_h).cuda()
     eps = [0.1] * 6 + [0.15] * 2
     ms = [5] * 6 + [3] * 2
     run = lambda: cluster.dbscan(xyz, eps, ms, pred)
-    times = []
-    for it in range(a.warmup + a.reps):
-        t, (labels, core, n_clusters) = timed(run)
-        if it >= a.warmup:
-            times.append(t)
+    times, (labels, core, n_clusters) = timing.wall_times(run, a.reps, a.warmup)
     rounds, launches = cluster.LAST["rounds"], cluster.LAST["launches"]
     phases = [phase_times(run) for _ in range(a.reps)]
     zero = torch.zeros_like(xyz)
-    inst_times = [timed(lambda: cluster.instances(xyz, zero, pred))[0] for _ in range(a.warmup + a.reps)][a.warmup:]
+    inst_times = timing.wall_times(lambda: cluster.instances(xyz, zero, pred), a.reps, a.warmup)[0]
     inst = cluster.instances(xyz, zero, pred)
     result = {"tool": "bench_dbscan", "device": torch.cuda.get_device_name(0), "points": a.points, "classes": 8, "eps": eps, "min_samples": ms,
               "reps": a.reps, "warmup": a.warmup,
@@ -100,11 +84,7 @@ def main():
               "instances_ms": round(statistics.median(inst_times), 4),
               "clusters_per_class": n_clusters.tolist(), "core_points": int(core.sum()), "noise_points": int((labels < 0).sum()),
               "instances": int(inst[1].numel())}
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -17,29 +17,19 @@ same machine in the same run, on a scene of `--host-points` points - the oracles
 scene (`small_*`) and whether the boxes agree.
 Every GPU step runs under its own time limit (`--limit` seconds, SIGALRM ends the process: nothing more is started on the device)."""
 import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import timing  # first: it puts the repository root on sys.path
 from bench_contacts import make_scene  # noqa: E402
-from bench_evaltile import limited, timed  # noqa: E402
 from stratified_transformer_amd import cluster, evaluate  # noqa: E402
 
 NOT_MEASURED = ["a per-kernel profile (no run under rocprofv3 was taken)", "scenes of more than about 100k points", "a real model behind model_fn",
                 "half-precision logits or shifts", "scenes whose parts exceed voxel_max (the crop cover: tools/bench_evaltile.py)"]
-
-
-def host_ms(fn, reps, warmup):
-    times = [timed(fn)[0] for _ in range(warmup + reps)][warmup:]
-    return statistics.median(times)
 
 
 def vote_bench(m, classes, reps, warmup):
@@ -50,17 +40,8 @@ def vote_bench(m, classes, reps, warmup):
     idx = torch.randint(0, n_points, (m,), device="cuda", generator=g)
     plain, both = evaluate.SceneVotes(n_points, classes), evaluate.SceneVotes(n_points, classes, shifts=True)
     arms = {"vote_ms": lambda: plain.add(logits, idx), "vote_shift_ms": lambda: both.add(logits, idx, shift)}
-    times = {k: [] for k in arms}
-    for it in range(warmup + reps):
-        for name, fn in arms.items():                      # the arms take turns: one process, one device, the same clocks
-            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            start.record()
-            fn()
-            end.record()
-            torch.cuda.synchronize()
-            if it >= warmup:
-                times[name].append(start.elapsed_time(end))
+    # the arms take turns: one process, one device, the same clocks
+    times = {name: dev for name, (dev, _, _) in zip(arms, timing.calls(list(arms.values()), reps, warmup))}
     out = {k: round(statistics.median(v), 4) for k, v in times.items()}
     out.update({k.replace("_ms", "_ms_min"): round(min(v), 4) for k, v in times.items()})
     out.update(rows=m, classes=classes, points=n_points, extra_ms=round(out["vote_shift_ms"] - out["vote_ms"], 4), shift_bytes=m * 12 * 3,
@@ -82,11 +63,11 @@ def device_pass(coord_h, pred_h, classes, reps, warmup, voxel_size, voxel_max):
     feat = torch.arange(n, dtype=torch.float32, device="cuda")[:, None]
     model = lookup_model(table, shift_table, classes)
     out = {"points": n}
-    out["dense_points_ms"] = round(host_ms(lambda: evaluate.dense_points(coord), reps, warmup), 4)
+    out["dense_points_ms"] = round(timing.median_wall_ms(lambda: evaluate.dense_points(coord), reps, warmup), 4)
     out["dense_points_kept"] = int(evaluate.dense_points(coord)[1].shape[0])
-    out["detect_boxes_ms"] = round(host_ms(lambda: cluster.detect_boxes(coord, shift_table, table), reps, warmup), 4)
+    out["detect_boxes_ms"] = round(timing.median_wall_ms(lambda: cluster.detect_boxes(coord, shift_table, table), reps, warmup), 4)
     run = lambda: evaluate.detect_scene(model, coord, feat, voxel_size, voxel_max, classes, 0.04, feat_div=None)  # noqa: E731
-    out["detect_scene_ms"] = round(host_ms(run, reps, warmup), 4)
+    out["detect_scene_ms"] = round(timing.median_wall_ms(run, reps, warmup), 4)
     got = run()
     out.update(sets=got.n_sets, support_points=int(got.points.shape[0]), labels_right=bool(torch.equal(got.label, table)))
     return out, got, shift_table.cpu().numpy()
@@ -119,21 +100,20 @@ def main():
     ap.add_argument("--voxel-max", type=int, default=80000)
     ap.add_argument("--no-host", action="store_true", help="skip the numpy restatement")
     ap.add_argument("--limit", type=int, default=300)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detect_bench.json"))
+    ap.add_argument("--out", default=os.path.join(timing.ROOT, "profiles", "detect_bench.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_detect: needs the GPU (no CPU timing of the device path is meaningful)")
+    timing.need_gpu("bench_detect")
     result = {"tool": "bench_detect", "device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": a.warmup, "voxel_size": a.voxel_size,
               "voxel_max": a.voxel_max}
-    with limited(a.limit):
+    with timing.limited(a.limit):
         result["vote"] = vote_bench(a.rows, a.classes, a.reps, a.warmup)
     coord_h, pred_h, n_boxes = make_scene(a.points)
-    with limited(a.limit):
+    with timing.limited(a.limit):
         result["scene"], _, _ = device_pass(coord_h, pred_h, 18, a.reps, a.warmup, a.voxel_size, a.voxel_max)
     result["scene"]["boxes"] = n_boxes
     if not a.no_host:
         small_h, small_pred_h, small_boxes = make_scene(a.host_points)
-        with limited(a.limit):
+        with timing.limited(a.limit):
             small, got, shift_h = device_pass(small_h, small_pred_h, 18, a.reps, a.warmup, a.voxel_size, a.voxel_max)
         host, want = host_pass(small_h, small_pred_h, shift_h, 18, a.voxel_size, a.voxel_max)
         host.update(points=len(small_h), boxes=small_boxes, small_dense_points_ms=small["dense_points_ms"], small_detect_boxes_ms=small["detect_boxes_ms"],
@@ -142,10 +122,7 @@ def main():
                     ratio_to_host_pass=round(host["total_ms"] / small["detect_scene_ms"], 1))
         result["host"] = host
     result["not_measured"] = NOT_MEASURED
-    line = json.dumps(result)
-    print(line, flush=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -13,47 +13,17 @@ sort of the n distances, the update kernel with its read-back.  `host`: the nump
 `identical`: the device's crops, seeds and final priority equal the numpy loop's bit for bit at this size.
 Every GPU step runs under its own time limit (`--limit` seconds, SIGALRM ends the process: nothing more is started on the device)."""
 import argparse
-import json
 import os
-import signal
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import _lib, evaluate  # noqa: E402
 from stratified_transformer_amd._lib import ptr  # noqa: E402
 from tests import evaltile_oracle as O  # noqa: E402
-
-
-class limited:
-    """a GPU step under its own time limit: the alarm's default action ends the process"""
-
-    def __init__(self, seconds):
-        self.seconds = int(seconds)
-
-    def __enter__(self):
-        signal.signal(signal.SIGALRM, signal.SIG_DFL)
-        signal.alarm(self.seconds)
-
-    def __exit__(self, *exc):
-        signal.alarm(0)
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def median_ms(fn, reps, warmup):
-    return statistics.median([timed(fn)[0] for _ in range(warmup + reps)][warmup:])
 
 
 def main():
@@ -65,10 +35,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--host-reps", type=int, default=2)
     ap.add_argument("--limit", type=int, default=120)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "evaltile_bench.json"))
+    ap.add_argument("--out", default=os.path.join(timing.ROOT, "profiles", "evaltile_bench.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_evaltile: needs the GPU (no CPU timing of the device path is meaningful)")
+    timing.need_gpu("bench_evaltile")
     n, vm = a.points, a.voxel_max
     coord_h, priority_h = O.room(n, 0)
     coord_h = coord_h.astype(np.float32 if a.dtype == "f32" else np.float64)
@@ -81,8 +50,8 @@ def main():
     n_crops = int(want[0].shape[0])
 
     coord, priority = torch.from_numpy(coord_h).cuda(), torch.from_numpy(priority_h).cuda()
-    with limited(a.limit):
-        times = [timed(lambda: evaluate.crop_cover(coord, vm, priority))[0] for _ in range(a.warmup + a.reps)][a.warmup:]
+    with timing.limited(a.limit):
+        times = timing.wall_times(lambda: evaluate.crop_cover(coord, vm, priority), a.reps, a.warmup)[0]
         crops, seeds, final = evaluate.crop_cover(coord, vm, priority)
         identical = bool(np.array_equal(crops.cpu().numpy(), want[0]) and np.array_equal(seeds.cpu().numpy(), want[1])
                          and np.array_equal(final.cpu().numpy().view(np.uint64), want[2].view(np.uint64)))
@@ -96,15 +65,15 @@ def main():
     covered, report, prio = torch.zeros(n, dtype=torch.uint8, device="cuda"), torch.zeros(2, dtype=torch.int32, device="cuda"), priority.clone()
     seed_dist = lambda: _lib.call("pointops2_evaltile_seed_dist_launcher", n, is_f64, ptr(coord), ptr(prio), ptr(pv), ptr(pi), ptr(seed), ptr(dist),
                                   device=coord.device)
-    with limited(a.limit):
-        seed_dist_ms = median_ms(seed_dist, a.reps, a.warmup)
-        sort_ms = median_ms(lambda: torch.sort(dist, stable=True)[1][:vm].clone(), a.reps, a.warmup)
+    with timing.limited(a.limit):
+        seed_dist_ms = timing.median_wall_ms(seed_dist, a.reps, a.warmup)
+        sort_ms = timing.median_wall_ms(lambda: torch.sort(dist, stable=True)[1][:vm].clone(), a.reps, a.warmup)
         crop = torch.sort(dist, stable=True)[1][:vm].clone()
 
         def update():
             _lib.call("pointops2_evaltile_update_launcher", n, vm, is_f64, ptr(dist), ptr(crop), ptr(prio), ptr(covered), ptr(report), device=coord.device)
             return report.tolist()
-        update_ms = median_ms(update, a.reps, a.warmup)
+        update_ms = timing.median_wall_ms(update, a.reps, a.warmup)
 
     total = statistics.median(times)
     result = {"tool": "bench_evaltile", "device_name": torch.cuda.get_device_name(0), "points": n, "voxel_max": vm, "dtype": a.dtype, "crops": n_crops,
@@ -115,10 +84,7 @@ def main():
               "host": {"total_ms": round(min(host_times), 2), "per_crop_ms": round(min(host_times) / n_crops, 3), "reps": a.host_reps,
                        "cores": len(os.sched_getaffinity(0)), "numpy": np.__version__},
               "speedup_over_host_loop": round(min(host_times) / total, 2)}
-    line = json.dumps(result)
-    print(line, flush=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
+    timing.emit(result, a.out)
     if not identical:
         raise SystemExit("bench_evaltile: the device's crops differ from the numpy loop's")
 

@@ -9,14 +9,10 @@ block's convolution (gradients of x and weight).  Per shape and side: median ove
 each bracketed by events on the stream, the two sides alternating; `ratio_fwd_bwd` = torch / HIP (> 1: the HIP path is faster).
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import pointops as P, scene  # noqa: E402
 from stratified_transformer_amd.compat import kpconv_kernel_points  # noqa: E402
 
@@ -36,18 +32,6 @@ def kpconv_torch(query, support, nb, x, kp, weight, extent):
     return wf.reshape(wf.shape[0], -1) @ weight.reshape(-1, weight.shape[2])
 
 
-def timed(fn, x, weight, go, backward):
-    x.grad = weight.grad = None
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn(x, weight)
-    if backward:
-        out.backward(go)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1), out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=100000)
@@ -55,8 +39,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_kpconv: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_kpconv")
     n = a.points
     xyz = torch.from_numpy(scene.make_room(n, 0)).cuda()
     off = torch.tensor([n], dtype=torch.int32, device="cuda")
@@ -70,30 +53,26 @@ def main():
         x = torch.randn(n, c, device="cuda", generator=g).requires_grad_(x_grad)
         weight = (torch.randn(15, c, out_c, device="cuda", generator=g) * 0.2).requires_grad_(True)
         go = torch.randn(n, out_c, device="cuda", generator=g)
-        sides = {"hip": lambda x, w: P.kpconv(xyz, xyz, nb, x, kp, w, EXTENT), "torch": lambda x, w: kpconv_torch(xyz, xyz, nb, x, kp, w, EXTENT)}
-        times = {(s, b): [] for s in sides for b in (False, True)}
-        outs, grads = {}, {}
-        for it in range(a.warmup + a.reps):
-            for s, fn in sides.items():
-                for b in (False, True):
-                    ms, out = timed(fn, x, weight, go, b)
-                    if it >= a.warmup:
-                        times[(s, b)].append(ms)
-                outs[s], grads[s] = out.detach(), weight.grad.detach().clone()
+        sides = {"hip": lambda: P.kpconv(xyz, xyz, nb, x, kp, weight, EXTENT), "torch": lambda: kpconv_torch(xyz, xyz, nb, x, kp, weight, EXTENT)}
+
+        def clear():
+            x.grad = weight.grad = None
+
+        def backward(out):
+            out.backward(go)
+            return weight.grad
+
+        times, last = timing.fwd_bwd_windows(sides, clear, backward, a.reps, a.warmup)
+        outs, grads = {s: last[s][0].detach() for s in sides}, {s: last[s][1].detach() for s in sides}
         row = {"c": c, "out": out_c, "x_requires_grad": x_grad,
                "max_abs_diff_out": float((outs["hip"] - outs["torch"]).abs().max()),
                "max_rel_diff_grad_weight": float(((grads["hip"] - grads["torch"]).abs().max() / grads["torch"].abs().max()))}
         for s in sides:
-            row[s] = {"fwd_ms": round(statistics.median(times[(s, False)]), 4), "fwd_bwd_ms": round(statistics.median(times[(s, True)]), 4),
-                      "fwd_bwd_ms_min": round(min(times[(s, True)]), 4), "fwd_bwd_ms_max": round(max(times[(s, True)]), 4)}
+            row[s] = timing.fwd_bwd_summary(times, s)
         row["ratio_fwd"] = round(row["torch"]["fwd_ms"] / row["hip"]["fwd_ms"], 2)
         row["ratio_fwd_bwd"] = round(row["torch"]["fwd_bwd_ms"] / row["hip"]["fwd_bwd_ms"], 2)
         result["shapes"].append(row)
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -17,15 +17,11 @@ below); `achieved_bytes_per_s` = those bytes over the fused time - launch gaps, 
 rate, not a kernel's.  `faster_beyond_spread`: composite - fused > the composite's spread.
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import pointops as P  # noqa: E402
 
 IGNORE, WEIGHT = 255, 0.5
@@ -38,30 +34,6 @@ def fused_bytes(n, c, half):
     fwd = n * (b * c + 8 + 3 * b + 12 + 8)
     bwd = n * (b * c + 8 + 8 + 3 * b + 12 + b * c + 3 * b)
     return fwd, bwd
-
-
-def windows(sides, reps, warmup, inner):
-    """sides: name -> fn(); -> name -> list of ms per iteration, the sides alternating window by window"""
-    times = {s: [] for s in sides}
-    for it in range(warmup + reps):
-        for s, fn in sides.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            if it >= warmup:
-                times[s].append(e0.elapsed_time(e1) / inner)
-    return times
-
-
-def summary(times, base, new):
-    r = {base + "_ms": round(statistics.median(times[base]), 5), new + "_ms": round(statistics.median(times[new]), 5),
-         base + "_spread_ms": round(max(times[base]) - min(times[base]), 5), new + "_spread_ms": round(max(times[new]) - min(times[new]), 5)}
-    r["ratio"] = round(r[base + "_ms"] / r[new + "_ms"], 3)
-    r["faster_beyond_spread"] = bool(r[base + "_ms"] - r[new + "_ms"] > r[base + "_spread_ms"])
-    return r
 
 
 def iou_counts_torch(logits, target, classes):
@@ -119,10 +91,10 @@ def case(n, c, amp, a):
     return row, sides
 
 
-def timed(row, sides, amp, a):
+def timed_row(row, sides, amp, a):
     fwd_b, bwd_b = fused_bytes(row["n"], row["c"], amp)
     for key, pair in sides.items():
-        row[key] = summary(windows(pair, a.reps, a.warmup, a.inner), "composite", "fused")
+        row[key] = timing.summary(timing.windows(pair, a.reps, a.warmup, a.inner), "composite", "fused")
         row[key]["bytes"] = fwd_b + bwd_b
         row[key]["achieved_bytes_per_s"] = round(row[key]["bytes"] / (row[key]["fused_ms"] * 1e-3), 1)
     return row
@@ -138,8 +110,7 @@ def main():
     a = ap.parse_args()
     if a.reps < 5:
         raise SystemExit("bench_loss: at least five repeats a side")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_loss: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_loss")
     if a.trace_loop:
         # for a run of its own under `rocprofv3 --kernel-trace --stats -- python tools/bench_loss.py --trace-loop 200`: the fused side only
         for n, c in SHAPES:
@@ -156,13 +127,9 @@ def main():
     modes = (("fp32", False), ("autocast_f16", True))
     built = {mode: [case(n, c, amp, a) for n, c in SHAPES] for mode, amp in modes}   # all set up and run once before any timing
     for mode, amp in modes:
-        result["cases"][mode] = [timed(row, sides, amp, a) for row, sides in built[mode]]
+        result["cases"][mode] = [timed_row(row, sides, amp, a) for row, sides in built[mode]]
     result["all_faster_beyond_spread"] = bool(all(r[k]["faster_beyond_spread"] for rows in result["cases"].values() for r in rows for k in ("loss", "step")))
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

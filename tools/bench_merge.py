@@ -15,19 +15,14 @@ The host reference is the literal loop of tests/merge_oracle.py (per pair of set
 what the reference's cdist does) on the same machine, on a scene of `--host-points` points, where one pair's matrix still fits;
 `small_*` are the device's times on that same scene and `small_agrees` says whether both give the same sets and boxes."""
 import argparse
-import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bench_contacts import box, device_ms  # noqa: E402
+import timing  # first: it puts the repository root on sys.path
+from bench_contacts import box  # noqa: E402
 from stratified_transformer_amd import cluster  # noqa: E402
 
 
@@ -58,10 +53,10 @@ def parts_ms(coord, obj, n_objects, reps, warmup):
     r, r2 = cluster._radius(call.who, cluster.MERGE_RADIUS)
     p = cluster._labelled(call, coord, obj, n_objects, "n_objects")
     out = {}
-    out["grid_ms"], _, (pts, slabel, ranges) = device_ms(lambda: cluster._label_grid(call, p, r), reps, warmup)
-    out["boxes_ms"], _, (lo, hi, size) = device_ms(lambda: cluster._boxes(call, p), reps, warmup)
-    out["rows_ms"], _, rows = device_ms(lambda: cluster._rows(call, pts, slabel, ranges, p.n_labels, r2), reps, warmup)
-    out["unique_ms"], _, (pat, count) = device_ms(lambda: cluster._patterns(slabel, rows), reps, warmup)
+    out["grid_ms"], _, (pts, slabel, ranges) = timing.device_ms(lambda: cluster._label_grid(call, p, r), reps, warmup)
+    out["boxes_ms"], _, (lo, hi, size) = timing.device_ms(lambda: cluster._boxes(call, p), reps, warmup)
+    out["rows_ms"], _, rows = timing.device_ms(lambda: cluster._rows(call, pts, slabel, ranges, p.n_labels, r2), reps, warmup)
+    out["unique_ms"], _, (pat, count) = timing.device_ms(lambda: cluster._patterns(slabel, rows), reps, warmup)
     tables = cluster._merge_tables(call, lo, hi, size, pat, count)
     times = []
     for _ in range(reps):
@@ -84,13 +79,12 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the literal host loop")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_merge: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_merge")
     if a.reps < 20:
         raise SystemExit("bench_merge: at least 20 timed calls")
     coord_h, pred_h, n_boxes = make_scene(a.points, a.spacing)
     coord, obj, n_objects = objects_of(coord_h, pred_h)
-    merge_ms, merge_host_ms, (merged, set_of, boxes, n_sets) = device_ms(lambda: cluster.merge_objects(coord, obj, n_objects), a.reps, a.warmup)
+    merge_ms, merge_host_ms, (merged, set_of, boxes, n_sets) = timing.device_ms(lambda: cluster.merge_objects(coord, obj, n_objects), a.reps, a.warmup)
     calls = dict(cluster.LAST_MERGE)
     result = {"tool": "bench_merge", "device": torch.cuda.get_device_name(0), "points": len(coord_h), "boxes": n_boxes, "spacing": a.spacing,
               "objects": n_objects, "sets": n_sets, "radius": cluster.MERGE_RADIUS, "overlap": cluster.MERGE_OVERLAP,
@@ -101,7 +95,7 @@ def main():
         from tests import merge_oracle
         small_h, small_pred, small_boxes = make_scene(a.host_points, a.spacing)
         small, small_obj, small_n = objects_of(small_h, small_pred)
-        ms, host_ms, got = device_ms(lambda: cluster.merge_objects(small, small_obj, small_n), a.reps, a.warmup)
+        ms, host_ms, got = timing.device_ms(lambda: cluster.merge_objects(small, small_obj, small_n), a.reps, a.warmup)
         obj_h = small_obj.cpu().numpy()
         times = []
         for _ in range(3):
@@ -111,11 +105,7 @@ def main():
         result.update(small_points=len(small_h), small_boxes=small_boxes, small_objects=small_n, small_sets=got[3], small_merge_ms=round(ms, 4),
                       small_merge_host_ms=round(host_ms, 4), small_literal_loop_ms=round(statistics.median(times), 2),
                       small_agrees=bool(np.array_equal(got[1].cpu().numpy(), want_of) and np.array_equal(got[2].cpu().numpy(), want_boxes)))
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -19,15 +19,12 @@ every figure: median over `reps` windows of `inner` iterations between two devic
 kernel's.  `faster_beyond_spread`: composite - fused > the composite's spread.
 """
 import argparse
-import json
-import os
 import statistics
-import sys
 
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import layers, scene  # noqa: E402
 from stratified_transformer_amd import pointops as P  # noqa: E402
 
@@ -44,30 +41,6 @@ def fused_bytes(n, c, half, residual, training=True, backward=True):
         k["bn_bwd_kernel<sums>"] = n * c * 2 * b
         k["bn_bwd_kernel<dx>"] = n * c * 3 * b
     return k
-
-
-def windows(sides, reps, warmup, inner):
-    """sides: name -> fn(); -> name -> list of ms per iteration, the sides alternating window by window"""
-    times = {s: [] for s in sides}
-    for it in range(warmup + reps):
-        for s, fn in sides.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            if it >= warmup:
-                times[s].append(e0.elapsed_time(e1) / inner)
-    return times
-
-
-def summary(times, base, new):
-    r = {base + "_ms": round(statistics.median(times[base]), 5), new + "_ms": round(statistics.median(times[new]), 5),
-         base + "_spread_ms": round(max(times[base]) - min(times[base]), 5), new + "_spread_ms": round(max(times[new]) - min(times[new]), 5)}
-    r["ratio"] = round(r[base + "_ms"] / r[new + "_ms"], 3)
-    r["faster_beyond_spread"] = bool(r[base + "_ms"] - r[new + "_ms"] > r[base + "_spread_ms"])
-    return r
 
 
 def _act(pre, act):
@@ -123,8 +96,8 @@ def site(n, c, half, act, residual, eval_forward, a):
     return row, sides
 
 
-def timed(row, sides, a):
-    row.update(summary(windows(sides, a.reps, a.warmup, a.inner), "composite", "fused"))
+def timed_row(row, sides, a):
+    row.update(timing.summary(timing.windows(sides, a.reps, a.warmup, a.inner), "composite", "fused"))
     row["kernel_bytes"] = fused_bytes(row["n"], row["c"], row["rows"] == "f16", row["residual"], not row["eval_forward"], not row["eval_forward"])
     row["bytes"] = sum(row["kernel_bytes"].values())
     row["achieved_bytes_per_s"] = round(row["bytes"] / (row["fused_ms"] * 1e-3), 1)
@@ -155,17 +128,15 @@ def kernel_stats(db_path, loop, out_path):
     kernel,n,c,dtype,residual,calls,median_us,min_us,max_us,bytes,tbytes_per_s_at_median."""
     import csv
     import re
-    import sqlite3
-    rows = sqlite3.connect(db_path).execute("select name, start, end from kernels order by start").fetchall()
     per = {}
-    for name, start, end in rows:
+    for name, us in timing.kernel_times_db(db_path):
         m = re.search(r"(bn_\w+_kernel)(<[^>]*>)?", name)
         if m is None:
             continue
         key = m.group(1)
         if key == "bn_bwd_kernel":
             key += "<sums>" if "true" in (m.group(2) or "") else "<dx>"
-        per.setdefault(key, []).append((end - start) / 1000.0)
+        per.setdefault(key, []).append(us)
     cases, calls = trace_cases(), loop + 2
     with open(out_path, "w", newline="") as f:
         w = csv.writer(f)
@@ -231,8 +202,7 @@ def main():
         return kernel_stats(a.kernel_stats, a.trace_loop, a.out)
     if a.reps < 5:
         raise SystemExit("bench_norm: at least five repeats a side")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_norm: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_norm")
     if a.trace_loop:
         # for a run of its own under `rocprofv3 --kernel-trace --stats -- python tools/bench_norm.py --trace-loop 50`: the fused side only,
         # one site per (N, C, precision) - leaky_relu, with the residual at C = 48 - so that the per-kernel averages belong to one shape each
@@ -246,22 +216,18 @@ def main():
               "warmup": a.warmup, "inner": a.inner, "sites": [], "model": []}
     for args in site_cases():                      # (a case at a time: 600 000 x 48 rows in four copies a side are not kept for all cases at once)
         row, sides = site(*args, a)
-        result["sites"].append(timed(row, sides, a))
+        result["sites"].append(timed_row(row, sides, a))
         del sides
         torch.cuda.empty_cache()
     if not a.no_model:
         inner = max(2, a.inner // 4)
         for amp in (False, True):
             row, sides = model_case(100000, amp, a)
-            row.update(summary(windows(sides, a.reps, a.warmup, inner), "composite", "fused"))
+            row.update(timing.summary(timing.windows(sides, a.reps, a.warmup, inner), "composite", "fused"))
             result["model"].append(row)
     result["sites_faster_beyond_spread"] = sum(r["faster_beyond_spread"] for r in result["sites"])
     result["sites_total"] = len(result["sites"])
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -15,22 +15,18 @@ window within the one run; per variant the median over `windows` windows (after 
 upper quartile, max], in ms per step.
 """
 import argparse
-import csv
 import json
-import os
-import re
 import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing  # first: it puts the repository root on sys.path
 
 CHANNELS, DEPTHS, HEADS, CLASSES, TABLE_ROWS, KERNEL_POINTS, FEA_DIM = [48, 96, 192, 384], [2, 2, 6, 2], [3, 6, 12, 24], 13, 64, 15, 6
 HBM_BYTES_PER_S = 6.3e12        # what a float4 copy reaches on the chip
 UPDATE_BYTES_PER_ELEMENT = 28   # reads p, g, m, v; writes p, m, v
+KERNELS = r"optim_\w+_kernel|amp_update_scale|fillBuffer\w*"   # what a traced step launches
 NOT_MEASURED = ["a whole training step of the unmodified model with and without the fused step", "gradient clipping between unscale_ and step",
                 "hardware counters (no --pmc run was taken)", "parameter sets of other configurations"]
 
@@ -71,11 +67,6 @@ def numel(shape):
     return n
 
 
-def spread(ts):
-    q = statistics.quantiles(ts, n=4)
-    return [round(min(ts), 4), round(q[0], 4), round(q[2], 4), round(max(ts), 4)]
-
-
 class Variant:
     def __init__(self, name, shapes, make_opt, make_scaler, seed=0):
         gen = torch.Generator(device="cuda").manual_seed(seed)
@@ -97,15 +88,6 @@ class Variant:
             self.scaler.step(self.opt)
             self.scaler.update()
 
-    def window(self, steps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            self.step()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / steps
-
-
 def variants(shapes, only=None):
     from stratified_transformer_amd import optim
     kw = dict(weight_decay=0.01)
@@ -125,22 +107,18 @@ def variants(shapes, only=None):
     return out
 
 
-def summarize_trace(path, elements):
-    """kernel name -> calls, median / min / max us from a rocprofv3 kernel_trace.csv; the update kernel's share of the byte bound"""
-    per = {}
-    for r in csv.DictReader(open(path)):
-        m = re.search(r"optim_\w+_kernel|amp_update_scale|fillBuffer\w*", r["Kernel_Name"])
-        if m is not None:
-            per.setdefault(m.group(0), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    out = {k: dict(calls=len(v), median_us=round(statistics.median(v), 2), min_us=round(min(v), 2), max_us=round(max(v), 2)) for k, v in per.items()}
-    if "optim_adamw_kernel" in out:
-        t = out["optim_adamw_kernel"]["median_us"] * 1e-6
-        out["optim_adamw_kernel"]["bytes"] = UPDATE_BYTES_PER_ELEMENT * elements
-        out["optim_adamw_kernel"]["share_of_6.3TB/s"] = round(UPDATE_BYTES_PER_ELEMENT * elements / t / HBM_BYTES_PER_S, 3)
-    if "optim_check_kernel" in out:
-        t = out["optim_check_kernel"]["median_us"] * 1e-6
-        out["optim_check_kernel"]["bytes"] = 4 * elements
-        out["optim_check_kernel"]["share_of_6.3TB/s"] = round(4 * elements / t / HBM_BYTES_PER_S, 3)
+def byte_share(summary, kernel, nbytes):
+    """adds to a kernel's row of timing.kernel_summary the bytes it must move and their share of the byte bound at its median time"""
+    if kernel in summary:
+        summary[kernel]["bytes"] = nbytes
+        summary[kernel]["share_of_6.3TB/s"] = round(nbytes / (summary[kernel]["median_us"] * 1e-6) / HBM_BYTES_PER_S, 3)
+
+
+def trace_summary(path, elements):
+    """the optimizer step's kernels in a rocprofv3 kernel_trace.csv, with the update's and the check's share of the byte bound"""
+    out = timing.kernel_summary(timing.kernel_times_csv(path), KERNELS)
+    byte_share(out, "optim_adamw_kernel", UPDATE_BYTES_PER_ELEMENT * elements)
+    byte_share(out, "optim_check_kernel", 4 * elements)
     return out
 
 
@@ -159,15 +137,13 @@ def main():
     counts = dict(tensors=len(shapes), elements=elements, blocks_tensors=sum("blocks" in n for n, _ in shapes),
                   smallest=min(numel(s) for _, s in shapes), largest=max(numel(s) for _, s in shapes))
     if args.kernel_trace:
-        summary = summarize_trace(args.kernel_trace, elements)
+        summary = trace_summary(args.kernel_trace, elements)
         if args.merge:
-            result = json.load(open(args.merge))
-            result["kernel_trace"] = summary
-            with open(args.merge, "w") as f:
-                f.write(json.dumps(result) + "\n")
-        print(json.dumps(dict(kernel_trace=summary)))
+            timing.merge(args.merge, "kernel_trace", summary)
+        else:
+            print(json.dumps(dict(kernel_trace=summary)))
         return
-    assert torch.cuda.is_available(), "bench_optim.py needs the MI355X"
+    timing.need_gpu("bench_optim")
     print("parameter set:", counts, file=sys.stderr)
     if args.trace_steps:
         v = variants(shapes, only=["fused+scaler"])[0]
@@ -176,24 +152,14 @@ def main():
         torch.cuda.synchronize()
         print(json.dumps(dict(traced_steps=args.trace_steps, **counts)))
         return
-    vs = variants(shapes)
-    times = {v.name: [] for v in vs}
-    for w in range(args.warmup + args.windows):
-        for v in vs:
-            t = v.window(args.steps)
-            if w >= args.warmup:
-                times[v.name].append(t)
+    times = timing.wall_windows({v.name: v.step for v in variants(shapes)}, args.windows, args.warmup, args.steps)
     result = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, parameter_set=counts, steps_per_window=args.steps,
                   windows=args.windows, warmup_windows=args.warmup, unit="ms per step, host clock around a window that ends in a synchronise",
                   byte_bound_us=dict(update=round(UPDATE_BYTES_PER_ELEMENT * elements / HBM_BYTES_PER_S * 1e6, 1),
                                      check=round(4 * elements / HBM_BYTES_PER_S * 1e6, 1)),
-                  variants={k: dict(median_ms=round(statistics.median(v), 4), spread=spread(v)) for k, v in times.items()},
+                  variants={k: dict(median_ms=round(statistics.median(v), 4), spread=timing.spread(v)) for k, v in times.items()},
                   not_measured=NOT_MEASURED)
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, args.out)
 
 
 if __name__ == "__main__":

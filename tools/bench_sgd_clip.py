@@ -20,17 +20,13 @@ upper quartile, max], in ms per step.
 """
 import argparse
 import json
-import os
 import statistics
 import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import bench_optim as B  # noqa: E402
+import timing  # first: it puts the repository root on sys.path
+import bench_optim as B  # noqa: E402  (workload only: the parameter set, Variant, the traced kernels and their byte bounds)
 
 MAX_NORM = 1.0
 SGD_BYTES_PER_ELEMENT = 20   # reads p, g, buf; writes p, buf
@@ -97,14 +93,6 @@ def variants(shapes, only=None):
     return out, missing
 
 
-def merge(path, key, value):
-    result = json.load(open(path))
-    result[key] = value
-    with open(path, "w") as f:
-        f.write(json.dumps(result) + "\n")
-    print(json.dumps({key: value}))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=15)
@@ -126,17 +114,14 @@ def main():
         for side, paths in (("parent", args.parent_json), ("branch", args.branch_json)):
             runs = [json.load(open(path))["variants"] for path in paths]
             rows[side] = {k: [v[k] for v in runs] for k in ("fused+scaler", "fused")}   # one entry per run, in the order they were taken
-        merge(args.merge, "adamw_without_clipping", rows)
+        timing.merge(args.merge, "adamw_without_clipping", rows)
         return
     if args.kernel_trace:
-        summary = B.summarize_trace(args.kernel_trace, elements)
-        if "optim_sgd_kernel" in summary:
-            t = summary["optim_sgd_kernel"]["median_us"] * 1e-6
-            summary["optim_sgd_kernel"]["bytes"] = SGD_BYTES_PER_ELEMENT * elements
-            summary["optim_sgd_kernel"]["share_of_6.3TB/s"] = round(SGD_BYTES_PER_ELEMENT * elements / t / B.HBM_BYTES_PER_S, 3)
-        merge(args.merge, "kernel_trace:" + args.trace_leg, summary)
+        summary = B.trace_summary(args.kernel_trace, elements)
+        B.byte_share(summary, "optim_sgd_kernel", SGD_BYTES_PER_ELEMENT * elements)
+        timing.merge(args.merge, "kernel_trace:" + args.trace_leg, summary)
         return
-    assert torch.cuda.is_available(), "bench_sgd_clip.py needs the MI355X"
+    timing.need_gpu("bench_sgd_clip")
     print("parameter set:", counts, file=sys.stderr)
     if args.trace_steps:
         v = variants(shapes, only=[args.trace_leg + "/ours"])[0][0]
@@ -146,25 +131,16 @@ def main():
         print(json.dumps(dict(traced_steps=args.trace_steps, leg=args.trace_leg, **counts)))
         return
     vs, missing = variants(shapes)
-    times = {v.name: [] for v in vs}
-    for w in range(args.warmup + args.windows):
-        for v in vs:
-            t = v.window(args.steps)
-            if w >= args.warmup:
-                times[v.name].append(t)
+    times = timing.wall_windows({v.name: v.step for v in vs}, args.windows, args.warmup, args.steps)
     norms = {v.name: float(v.opt.last_grad_norm) for v in vs if getattr(v.opt, "last_grad_norm", None) is not None}
     result = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, parameter_set=counts, steps_per_window=args.steps,
                   windows=args.windows, warmup_windows=args.warmup, max_norm=MAX_NORM,
                   unit="ms per step, host clock around a window that ends in a synchronise",
                   byte_bound_us=dict(sgd_update=round(SGD_BYTES_PER_ELEMENT * elements / B.HBM_BYTES_PER_S * 1e6, 1),
                                      check_and_norm=round(4 * elements / B.HBM_BYTES_PER_S * 1e6, 1)),
-                  variants={k: dict(median_ms=round(statistics.median(v), 4), spread=B.spread(v)) for k, v in times.items()},
+                  variants={k: dict(median_ms=round(statistics.median(v), 4), spread=timing.spread(v)) for k, v in times.items()},
                   last_grad_norm=norms, not_available=missing, not_measured=NOT_MEASURED)
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, args.out)
 
 
 if __name__ == "__main__":

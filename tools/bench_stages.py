@@ -1,18 +1,8 @@
 """Per-op, per-stage timing of the attention operators on the bench scene (diagnostic; GPU box only)."""
-import os, sys
+import sys
 import torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import scene, pointops as P, pipeline
-
-
-def timeit(fn, n=10):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
 
 
 def main():
@@ -39,26 +29,26 @@ def main():
             for x in (q, k, v, tq, tk, tv): x.grad = None
             t.backward(g, retain_graph=True)
         res = {}
-        res['A1f'] = timeit(lambda: P.attention_step1_v2(q, k, b.index_1, b.offsets, 0))
-        res['A2f'] = timeit(lambda: P.dot_prod_with_idx_v3(q, b.offsets, 0, k, b.index_1, tq, tk, b.rel_idx))
-        res['A3f'] = timeit(lambda: P.segment_softmax(a1.detach(), b.offsets))
-        res['A4f'] = timeit(lambda: P.attention_step2_with_rel_pos_value_v2(sm.detach(), v, b.offsets, 0, b.index_1, tv, b.rel_idx))
-        res['A1b'] = timeit(lambda: bwd(a1, g_pairs))
-        res['A2b'] = timeit(lambda: bwd(a2, g_pairs))
-        res['A3b'] = timeit(lambda: bwd(sm, g_pairs))
-        res['A4b'] = timeit(lambda: bwd(out, s.grad_out))
+        res['A1f'] = timing.one_window_us(lambda: P.attention_step1_v2(q, k, b.index_1, b.offsets, 0))
+        res['A2f'] = timing.one_window_us(lambda: P.dot_prod_with_idx_v3(q, b.offsets, 0, k, b.index_1, tq, tk, b.rel_idx))
+        res['A3f'] = timing.one_window_us(lambda: P.segment_softmax(a1.detach(), b.offsets))
+        res['A4f'] = timing.one_window_us(lambda: P.attention_step2_with_rel_pos_value_v2(sm.detach(), v, b.offsets, 0, b.index_1, tv, b.rel_idx))
+        res['A1b'] = timing.one_window_us(lambda: bwd(a1, g_pairs))
+        res['A2b'] = timing.one_window_us(lambda: bwd(a2, g_pairs))
+        res['A3b'] = timing.one_window_us(lambda: bwd(sm, g_pairs))
+        res['A4b'] = timing.one_window_us(lambda: bwd(out, s.grad_out))
         from stratified_transformer_amd import fused
         fo = fused.window_attention(q, k, v, tq, tk, tv, b.offsets, b.index_1, b.rel_idx)
         fwd_sum, bwd_sum = sum(v_ for k_, v_ in res.items() if k_.endswith('f')), sum(v_ for k_, v_ in res.items() if k_.endswith('b'))
         tot = sum(res.values())
-        res['FUSEDf'] = timeit(lambda: fused.window_attention(q, k, v, tq, tk, tv, b.offsets, b.index_1, b.rel_idx))
-        res['FUSEDb'] = timeit(lambda: bwd(fo, s.grad_out))
+        res['FUSEDf'] = timing.one_window_us(lambda: fused.window_attention(q, k, v, tq, tk, tv, b.offsets, b.index_1, b.rel_idx))
+        res['FUSEDb'] = timing.one_window_us(lambda: bwd(fo, s.grad_out))
         res['ops_f'], res['ops_b'] = fwd_sum, bwd_sum
         for pat in ('even', 'odd'):
             plan = r[pat].cells
             co = fused.cell_attention(q, k, v, tq, tk, tv, plan)
-            res['CELLf_' + pat] = timeit(lambda: fused.cell_attention(q, k, v, tq, tk, tv, plan))
-            res['CELLb_' + pat] = timeit(lambda: bwd(co, s.grad_out))
+            res['CELLf_' + pat] = timing.one_window_us(lambda: fused.cell_attention(q, k, v, tq, tk, tv, plan))
+            res['CELLb_' + pat] = timing.one_window_us(lambda: bwd(co, s.grad_out))
         print('   cells even/odd', r['even'].cells.n_cells, r['odd'].cells.n_cells, 'P', r['even'].cells.n_pairs, r['odd'].cells.n_pairs,
               'nk_max', r['even'].cells.nk_max, r['odd'].cells.nk_max)
         print('stage', si, 'N', s.xyz.shape[0], 'M', M, 'h', st.num_heads, 'L', tq.shape[0], 'depth', st.depth,
@@ -68,4 +58,5 @@ def main():
     print('per step ms', {k_: round(v_, 2) for k_, v_ in total.items()}, 'sum', round(sum(total.values()), 2))
 
 
-main()
+if __name__ == "__main__":
+    main()

@@ -18,19 +18,14 @@ no machine here) on the same machine in the same run (median of 3), with scipy's
 beside `kept`); otherwise with the oracle's dense fp32 matrix on a scene of `--host-points` points, where it fits (`host_counts: "dense"`,
 `host_points` says the size, `small_*` are the device's times on that same scene)."""
 import argparse
-import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bench_contacts import device_ms, make_scene  # noqa: E402
+import timing  # first: it puts the repository root on sys.path
+from bench_contacts import make_scene  # noqa: E402
 from stratified_transformer_amd import cluster  # noqa: E402
 
 NOT_MEASURED = ["more than 16 objects", "clouds of millions of points", "a per-kernel profile (no run under rocprofv3 was taken)",
@@ -70,13 +65,13 @@ def parts_ms(coord, obj, n_objects, reps, warmup):
         return cluster._compact(mean, mean_object, keep, alive, n_kept, n_alive)
 
     out = {}
-    out["boxes_ms"], _, (lo, _, _) = device_ms(lambda: cluster._boxes(call, p), reps, warmup)
-    out["keys_sort_ms"], _, (skeys, order, slot, n_voxels) = device_ms(lambda: cluster._voxel_means(call, p, lo, voxel, vdims), reps, warmup)
-    out["means_ms"], _, (mean, mean_object, mean_size) = device_ms(lambda: cluster._means(call, p, n_voxels, skeys, order, slot), reps, warmup)
-    out["grid_ms"], _, (pts, _, _, ranges) = device_ms(
+    out["boxes_ms"], _, (lo, _, _) = timing.device_ms(lambda: cluster._boxes(call, p), reps, warmup)
+    out["keys_sort_ms"], _, (skeys, order, slot, n_voxels) = timing.device_ms(lambda: cluster._voxel_means(call, p, lo, voxel, vdims), reps, warmup)
+    out["means_ms"], _, (mean, mean_object, mean_size) = timing.device_ms(lambda: cluster._means(call, p, n_voxels, skeys, order, slot), reps, warmup)
+    out["grid_ms"], _, (pts, _, _, ranges) = timing.device_ms(
         lambda: cluster._grid(call, mean, mean_object, p.n_labels, n_voxels, p.origin, cell, dims), reps, warmup)
-    out["count_ms"], _, keep = device_ms(lambda: cluster._inliers(call, pts, ranges, r2, nb_points), reps, warmup)
-    out["compact_ms"], _, _ = device_ms(compact, reps, warmup)
+    out["count_ms"], _, keep = timing.device_ms(lambda: cluster._inliers(call, pts, ranges, r2, nb_points), reps, warmup)
+    out["compact_ms"], _, _ = timing.device_ms(compact, reps, warmup)
     out = {k: round(v, 4) for k, v in out.items()}
     out.update(voxel_dims=vdims, cells=dims, labelled_points=p.n_valid, voxels=n_voxels, longest_run=int(mean_size.max().item()),
                mean_run=round(p.n_valid / n_voxels, 3))
@@ -122,13 +117,12 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the host restatement")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_supports: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_supports")
     if a.reps < 20:
         raise SystemExit("bench_supports: at least 20 timed calls")
     coord_h, obj_h, n_objects, n_boxes = scene_with_strays(a.points, a.strays)
     coord, obj = torch.from_numpy(coord_h).cuda(), torch.from_numpy(obj_h).cuda()
-    ms, host_ms, (points, new_obj, source, n_new) = device_ms(lambda: cluster.clean_supports(coord, obj, n_objects), a.reps, a.warmup)
+    ms, host_ms, (points, new_obj, source, n_new) = timing.device_ms(lambda: cluster.clean_supports(coord, obj, n_objects), a.reps, a.warmup)
     calls = dict(cluster.LAST_SUPPORTS)
     result = {"tool": "bench_supports", "device": torch.cuda.get_device_name(0), "points": len(coord_h), "boxes": n_boxes, "objects": n_objects,
               "strays_per_object": a.strays, "voxel": cluster.SUPPORT_VOXEL, "radius": cluster.SUPPORT_RADIUS,
@@ -152,7 +146,7 @@ def main():
         else:
             small_h, small_obj_h, small_n, small_boxes = scene_with_strays(a.host_points, a.strays)
             small, small_obj = torch.from_numpy(small_h).cuda(), torch.from_numpy(small_obj_h).cuda()
-            small_ms, small_host_ms, got = device_ms(lambda: cluster.clean_supports(small, small_obj, small_n), a.reps, a.warmup)
+            small_ms, small_host_ms, got = timing.device_ms(lambda: cluster.clean_supports(small, small_obj, small_n), a.reps, a.warmup)
             loop_ms, want = timed_host(small_h, small_obj_h, small_n, None)
             result.update(host_counts="dense", host_points=len(small_h), small_boxes=small_boxes, small_objects=small_n,
                           small_supports_ms=round(small_ms, 4), small_supports_host_ms=round(small_host_ms, 4),
@@ -161,11 +155,7 @@ def main():
                                            and np.array_equal(want[1], got[1].cpu().numpy())),
                           ratio_to_host_loop=round(loop_ms / small_ms, 1))
     result["not_measured"] = NOT_MEASURED
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -11,15 +11,11 @@ features and of every parameter) of the two blocks' attention in a row, each bra
 alternating; `ratio_*` = pair list / plan (> 1: the plan is faster).
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 from torch import nn
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import index_build, layers, scene  # noqa: E402
 
 C, H, W, QUANT, DEPTH = 48, 3, 0.16, 0.01, 2
@@ -51,20 +47,6 @@ def stage(attns, feats, xyz, blocks, shifts, on_plan):
     return x
 
 
-def timed(fn, attns, feats, go, amp, backward):
-    feats.grad = None
-    attns.zero_grad(set_to_none=True)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-        out = fn(feats)
-    if backward:
-        out.backward(go.to(out.dtype))
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1), out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=100000)
@@ -72,8 +54,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_swin: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_swin")
     xyz = torch.from_numpy(scene.make_room(a.points, 0)).cuda()
     n = xyz.shape[0]
     offset = torch.tensor([n], dtype=torch.int32, device="cuda")
@@ -92,28 +73,26 @@ def main():
               "table_rows": rows, "depth": DEPTH, "cell_max_queries": cap, "reps": a.reps, "warmup": a.warmup,
               "patterns": [{"pairs": int(b.index_1.shape[0]), "cells": b.cells.n_cells, "windows": b.cells.n_parents, "keys_max": b.cells.nk_max}
                            for b in blocks]}
+
+    def clear():
+        feats.grad = None
+        attns.zero_grad(set_to_none=True)
+
     for mode, amp in (("fp32", False), ("autocast_f16", True)):
-        times = {(s, b): [] for s in sides for b in (False, True)}
-        outs = {}
-        for it in range(a.warmup + a.reps):
-            for s, fn in sides.items():
-                for b in (False, True):
-                    ms, out = timed(fn, attns, feats, go, amp, b)
-                    if it >= a.warmup:
-                        times[(s, b)].append(ms)
-                outs[s] = out.detach().float()
+        def forward(fn):
+            with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+                return fn(feats)
+
+        times, last = timing.fwd_bwd_windows({s: (lambda fn=fn: forward(fn)) for s, fn in sides.items()}, clear,
+                                             lambda out: out.backward(go.to(out.dtype)), a.reps, a.warmup)
+        outs = {s: last[s][0].detach().float() for s in sides}
         r = {"max_abs_diff_out": float((outs["plan"] - outs["pair_list"]).abs().max())}
         for s in sides:
-            r[s] = {"fwd_ms": round(statistics.median(times[(s, False)]), 4), "fwd_bwd_ms": round(statistics.median(times[(s, True)]), 4),
-                    "fwd_bwd_ms_min": round(min(times[(s, True)]), 4), "fwd_bwd_ms_max": round(max(times[(s, True)]), 4)}
+            r[s] = timing.fwd_bwd_summary(times, s)
         r["ratio_fwd"] = round(r["pair_list"]["fwd_ms"] / r["plan"]["fwd_ms"], 2)
         r["ratio_fwd_bwd"] = round(r["pair_list"]["fwd_bwd_ms"] / r["plan"]["fwd_bwd_ms"], 2)
         result[mode] = r
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

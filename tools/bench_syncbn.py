@@ -20,15 +20,12 @@ of `inner` iterations between two device events, in ms per iteration, the sides 
 side over its windows.  `gain_over_torch_chain_beyond_both_spreads`: torch_chain - sync > max(the two spreads).
 """
 import argparse
-import json
-import os
 import statistics
-import sys
 
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import pointops as P  # noqa: E402
 from stratified_transformer_amd import sharding  # noqa: E402
 
@@ -65,21 +62,6 @@ class TorchSyncChain(torch.autograd.Function):
         return grad_input, grad_weight, grad_bias, None, None, None, None
 
 
-def windows(sides, reps, warmup, inner):
-    times = {s: [] for s in sides}
-    for it in range(warmup + reps):
-        for s, fn in sides.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            if it >= warmup:
-                times[s].append(e0.elapsed_time(e1) / inner)
-    return times
-
-
 def site(n, c, half, a):
     g = torch.Generator(device="cuda").manual_seed(n + c)
     dt = torch.float16 if half else torch.float32
@@ -114,7 +96,7 @@ def site(n, c, half, a):
         for _ in range(a.inner):
             fn()
     torch.cuda.synchronize()
-    times = windows(sides, a.reps, a.warmup, a.inner)
+    times = timing.windows(sides, a.reps, a.warmup, a.inner)
     for name, t in times.items():
         row[name + "_ms"] = round(statistics.median(t), 5)
         row[name + "_spread_ms"] = round(max(t) - min(t), 5)
@@ -133,8 +115,7 @@ def main():
     a = ap.parse_args()
     if a.reps < 5:
         raise SystemExit("bench_syncbn: at least five repeats a side")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_syncbn: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_syncbn")
     sharding.all_gather_rows = local_gather                    # the collectives of the sync side: a local copy (module docstring)
     result = {"tool": "bench_syncbn", "device": torch.cuda.get_device_name(0), "negative_slope": SLOPE, "momentum": MOMENTUM, "reps": a.reps,
               "warmup": a.warmup, "inner": a.inner, "world_rows": WORLD,
@@ -146,11 +127,7 @@ def main():
             torch.cuda.empty_cache()
     result["sites_with_gain_over_torch_chain"] = sum(r["gain_over_torch_chain_beyond_both_spreads"] for r in result["sites"])
     result["sites_total"] = len(result["sites"])
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":

@@ -11,14 +11,10 @@ forward + backward (gradients of the features, the norm and the linear), each br
 alternating; `ratio_*` = composite / pooled (> 1: the pooled tail is faster).
 """
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # first: it puts the repository root on sys.path
 from stratified_transformer_amd import index_build, pointops as P, scene, standin  # noqa: E402
 
 RATIO, K = 0.25, 16
@@ -37,20 +33,6 @@ def pooled(td, feats, xyz, n_xyz, knn, offset, n_offset):
     return P.grouped_max(td.linear(td.norm(feats)).contiguous(), knn)
 
 
-def timed(fn, td, feats, go, amp, backward):
-    feats.grad = None
-    td.zero_grad(set_to_none=True)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-        out = fn(feats)
-    if backward:
-        out.backward(go.to(out.dtype))
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1), out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=100000)
@@ -58,8 +40,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_transition: needs the GPU (no CPU timing is meaningful)")
+    timing.need_gpu("bench_transition")
     xyz = torch.from_numpy(scene.make_room(a.points, 0)).cuda()
     off_host = [a.points]
     result = {"tool": "bench_transition", "device": torch.cuda.get_device_name(0), "points": a.points, "k": K, "ratio": RATIO,
@@ -81,30 +62,28 @@ def main():
         sides = {"pooled": lambda f: pooled(td, f, xyz, n_xyz, knn, offset, n_offset),
                  "composite": lambda f: composite(td, f, xyz, n_xyz, knn, offset, n_offset)}
         row = {"n": n, "m": m, "c_in": c_in, "c_out": c_out}
+
+        def clear():
+            feats.grad = None
+            td.zero_grad(set_to_none=True)
+
         for mode, amp in (("fp32", False), ("autocast_f16", True)):
-            times = {(s, b): [] for s in sides for b in (False, True)}
-            outs = {}
-            for it in range(a.warmup + a.reps):
-                for s, fn in sides.items():
-                    for b in (False, True):
-                        ms, out = timed(fn, td, feats, go, amp, b)
-                        if it >= a.warmup:
-                            times[(s, b)].append(ms)
-                    outs[s] = out.detach().float()
+            def forward(fn):
+                with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+                    return fn(feats)
+
+            times, last = timing.fwd_bwd_windows({s: (lambda fn=fn: forward(fn)) for s, fn in sides.items()}, clear,
+                                                 lambda out: out.backward(go.to(out.dtype)), a.reps, a.warmup)
+            outs = {s: last[s][0].detach().float() for s in sides}
             r = {"max_abs_diff_out": float((outs["pooled"] - outs["composite"]).abs().max())}
             for s in sides:
-                r[s] = {"fwd_ms": round(statistics.median(times[(s, False)]), 4), "fwd_bwd_ms": round(statistics.median(times[(s, True)]), 4),
-                        "fwd_bwd_ms_min": round(min(times[(s, True)]), 4), "fwd_bwd_ms_max": round(max(times[(s, True)]), 4)}
+                r[s] = timing.fwd_bwd_summary(times, s)
             r["ratio_fwd"] = round(r["composite"]["fwd_ms"] / r["pooled"]["fwd_ms"], 2)
             r["ratio_fwd_bwd"] = round(r["composite"]["fwd_bwd_ms"] / r["pooled"]["fwd_bwd_ms"], 2)
             row[mode] = r
         result["shapes"].append(row)
         xyz, off_host = n_xyz, n_host
-    line = json.dumps(result)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    timing.emit(result, a.out)
 
 
 if __name__ == "__main__":
