@@ -19,7 +19,7 @@
 // d = x - K and d * d over its rows in ascending order, K being the first value it saw in that channel - a shift inside the column's own
 // range, so the sums hold deviations, not magnitudes - and turns them into (count, mean, M2) = (cnt, K + S1 / cnt, S2 - S1 * (S1 / cnt)).
 // From there on partial results merge by Chan's formula only (delta = mean_b - mean_a; mean = mean_a + delta * n_b / n; M2 = M2_a + M2_b +
-// delta^2 * n_a n_b / n), in a fixed tree: the segments of a wave by an xor butterfly, the four waves in order through LDS
+// delta^2 * n_a n_b / n; the one place that leaves fp32: each merge is formed in double and rounded once), in a fixed tree: the segments of a wave by an xor butterfly, the four waves in order through LDS
 // (workgroup_columns, row_lanes.h), one row of `partials` [workgroups][3][C] per workgroup, and bn_stat_kernel merges those rows in
 // the order of column_reduce.  A constant column gives S1 = S2 = 0 and every delta 0: mean = K and M2 = 0 exactly.  The dgamma / dbeta
 // sums travel the same way with `+` as the merge.  No float atomics; every order is a function of the shapes alone: the same bits from
@@ -46,12 +46,15 @@ struct Moments {
 __device__ __forceinline__ Moments lanes_xor(Moments m, int st) {
     return Moments{__shfl_xor(m.n, st, WAVE), __shfl_xor(m.mean, st, WAVE), __shfl_xor(m.m2, st, WAVE)};
 }
-// Chan et al.: the moments of the union of two disjoint sets
+// Chan et al.: the moments of the union of two disjoint sets.  Each result is formed in double and rounded once: in fp32 the mean took three
+// roundings the size of delta per level of the tree, and with one row a lane (n <= rows_per_wg) delta is the column's whole spread - 7 rows
+// of 8 channels left dx at five times torch's error, outside the tests' bar; rounded once it is at twice.  A merge runs once per lane
+// and level after the row loop, never per row.
 __device__ __forceinline__ Moments chan_merge(Moments a, Moments b) {
     if (b.n == 0.0f) return a;
     if (a.n == 0.0f) return b;
-    const float n = a.n + b.n, delta = b.mean - a.mean;
-    return Moments{n, a.mean + delta * (b.n / n), (a.m2 + b.m2) + (delta * delta) * (a.n * b.n / n)};
+    const double na = a.n, nb = b.n, n = na + nb, delta = (double)b.mean - (double)a.mean;
+    return Moments{(float)n, (float)((double)a.mean + delta * (nb / n)), (float)(((double)a.m2 + (double)b.m2) + (delta * delta) * (na * nb / n))};
 }
 
 __device__ __forceinline__ float bn_act(float pre, int act, float slope) {

@@ -26,8 +26,8 @@ Measured on one MI355X (max abs error against float64, fused / composite; leaky_
     fp32  c=1    n=333 (no residual)   o 3.9e-07 / 1.9e-07   dx 2.6e-07 / 1.3e-07   dgamma 5.2e-06 / 2.5e-06   dbeta 4.9e-07 / 4.9e-07
     fp32  c=1024 n=3        o 8.1e-07 / 2.3e-06   dx 8.4e-06 / 1.6e-05   dgamma 8.9e-07 / 3.7e-06   dbeta 2.4e-07 / 2.4e-07
     fp32  c=48   n=333 misaligned   o 6.4e-07 / 4.6e-07   dx 3.6e-07 / 3.6e-07   dgamma 1.2e-05 / 1.3e-05   dbeta 6.8e-06 / 9.6e-06
-    fp32  c=100  n=333 (16 channels a lane)   o 5.8e-07 / 5.9e-07   dx 4.0e-07 / 4.0e-07   dgamma 1.6e-05 / 1.9e-05   dbeta 8.0e-06 / 8.7e-06
-    fp32  c=96   n=333 misaligned (the same)  o 6.8e-07 / 8.1e-07   dx 4.2e-07 / 4.7e-07   dgamma 1.4e-05 / 1.7e-05   dbeta 9.7e-06 / 9.2e-06
+    fp32  c=100  n=333 (25 chunks in a 32-lane segment)   o 5.8e-07 / 5.9e-07   dx 4.0e-07 / 4.0e-07   dgamma 1.6e-05 / 1.9e-05   dbeta 8.0e-06 / 8.7e-06
+    fp32  c=96   n=333 misaligned (16 channels a lane)  o 6.8e-07 / 8.1e-07   dx 4.2e-07 / 4.7e-07   dgamma 1.4e-05 / 1.7e-05   dbeta 9.7e-06 / 9.2e-06
     fp32  c=48   n=400000   o 1.1e-06 / 1.0e-06   dx 6.8e-07 / 5.6e-07   dgamma 1.4e-02 / 2.0e-02   dbeta 8.2e-03 / 7.4e-03   (sums of about 1e5)
     f16   c=48   n=333      o 1.9e-03 / 2.8e-03   dx 1.9e-03 / 1.9e-03   dgamma 1.0e-05 / 1.5e-03   dbeta 9.2e-06 / 1.1e-03
     bf16  c=48   n=333      o 1.5e-02 / 2.0e-02   dx 9.9e-03 / 9.9e-03   dgamma 1.0e-05 / 9.5e-03   dbeta 6.9e-06 / 1.0e-02
@@ -201,7 +201,9 @@ def _check(P, p, label, mode=None):
 
 
 FP32_CASES = [(c, n, False) for c in (12, 48, 96, 384) for n in (2, 5, 333, 4099)] + [(7, 65, False), (1, 333, False), (1024, 3, False), (48, 333, True),
-                                                                                          (100, 333, False), (96, 333, True)]   # the last two: one channel a lane, 16 a lane
+                                                                                          (100, 333, False), (96, 333, True), (70, 333, False)]
+# (7 and 1: one channel a lane in a segment; 100: 25 chunks in a 32-lane segment; 96 misaligned and 70: one channel a lane, 16 a lane -
+# tests/row_lanes_cases.py restates the choice, tests/test_row_lanes_hip.py runs every instance and segment width)
 
 
 @pytest.mark.parametrize("with_res", [True, False])

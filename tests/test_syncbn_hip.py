@@ -28,6 +28,7 @@ Measured on one MI355X (max abs error against float64, fused / composite; leaky_
     fp32  1+1+1+1+1+1+1+2    c=12    o 2.7e-07 / 2.7e-07   dx 2.2e-07 / 1.5e-07   dgamma 2.5e-07 / 4.9e-07   dbeta 1.8e-08 / 1.8e-08   running_mean 2.0e-08 / 2.0e-08   running_var 2.0e-07 / 2.0e-07
     fp32  2050+2049          c=48    o 8.3e-07 / 8.3e-07   dx 4.9e-07 / 5.1e-07   dgamma 6.1e-05 / 1.3e-04   dbeta 5.2e-05 / 5.2e-05   running_mean 2.9e-08 / 3.4e-08   running_var 2.7e-07 / 2.7e-07
     fp32  3+2                c=1024  o 6.2e-07 / 5.9e-07   dx 1.4e-06 / 1.0e-06   dgamma 7.1e-07 / 1.2e-06   dbeta 2.4e-07 / 2.4e-07   running_mean 5.5e-08 / 5.5e-08   running_var 2.7e-07 / 2.7e-07
+    (c=100: 25 chunks in a 32-lane segment; c=96 misaligned and c=70: one channel a lane, 16 a lane)
     fp32  200+133            c=100   o 7.1e-07 / 9.8e-07   dx 5.1e-07 / 4.6e-07   dgamma 1.0e-05 / 1.1e-05   dbeta 6.2e-06 / 6.1e-06   running_mean 6.2e-08 / 6.2e-08   running_var 2.6e-07 / 2.6e-07
     fp32  200+133 misaligned c=96    o 6.8e-07 / 7.5e-07   dx 4.4e-07 / 3.9e-07   dgamma 9.4e-06 / 1.2e-05   dbeta 4.8e-06 / 4.2e-06   running_mean 5.4e-08 / 5.4e-08   running_var 2.3e-07 / 2.3e-07
     f16   200+133            c=48    o 2.0e-03 / 3.8e-03   dx 9.2e-04 / 3.0e-03   dgamma 8.6e-06 / 2.1e-02   dbeta 6.5e-06 / 2.5e-02   running_mean 3.5e-08 / 3.5e-08   running_var 2.4e-07 / 2.4e-07
@@ -217,7 +218,8 @@ def test_world_one_gives_batch_norm_acts_bits(P):
 
 
 @pytest.mark.parametrize("sizes,c,misaligned", [((5, 0, 328), 48, False), ((1, 1, 1, 1, 1, 1, 1, 2), 12, False), ((2050, 2049), 48, False),
-                                                ((3, 2), 1024, False), ((200, 133), 100, False), ((200, 133), 96, True)])
+                                                ((3, 2), 1024, False), ((200, 133), 100, False), ((200, 133), 96, True),
+                                                ((200, 133), 70, False)])
 @pytest.mark.parametrize("with_res", [True, False])
 def test_emulated_ranks_fp32(P, sizes, c, misaligned, with_res):
     _check(P, sizes, c, rname="f32" if with_res else None, misaligned=misaligned)
