@@ -815,6 +815,27 @@ void residual_norm_stream_backward_launcher(int n, int c, int x_type, int y_type
                                             const void *z, const float *stat, const float *s, const float *gamma, void *grad_x, void *grad_y,
                                             float *partials, int partial_rows, float *grad_gamma, float *grad_beta);
 
+/* ---- the parameter gradients of a Linear layer over point rows (csrc/linear_grads.hip): with x [n, in] the layer's input and
+ * g [n, out] the gradient of its output, both row-contiguous and each of its own row type (POINTOPS2_ROWS_F32, _F16 or _BF16, widened
+ * exactly),
+ *   grad_weight[o, i] = sum_n g[n, o] * x[n, i]        grad_bias[o] = sum_n g[n, o]
+ * in fp32 on the matrix cores (v_mfma_f32_16x16x4_f32: per element a chain of fp32 fused multiply-adds in ascending row order), from
+ * ONE read of x and g.  The rows are cut into G = pointops2_linear_grads_partial_rows(n, in, out) chunks of POINTOPS2_LINEAR_GRADS_ROWS
+ * rows - a function of n alone (1 for n == 0; 0 for arguments out of range) - and the work is two launches:
+ *   linear_grads_partial_launcher: chunk c writes its sums to block c of partials [G][out][in + 1] (caller-allocated fp32; column `in`
+ *       of a row is the bias partial).  Every element of every block is written; rows behind n and columns behind in / out enter the
+ *       products as zeros.  partial_rows must be G.
+ *   linear_grads_reduce_launcher: grad_weight [out, in] and, with has_bias != 0, grad_bias [out] = the sum of the partial_rows blocks in
+ *       ascending chunk order.  Both are fully written (n == 0: zeros); has_bias == 0: grad_bias is not touched and may be NULL.
+ * No float atomics: the same operands give the same bits on every run, wherever they lie.  1 <= in, out <= 1536, n >= 0.  Recorded as
+ * errors, nothing enqueued: a shape or row type out of range, a partial_rows other than G (partial) or < 1 (reduce), a NULL operand. */
+#define POINTOPS2_LINEAR_GRADS_ROWS 512
+int pointops2_linear_grads_partial_rows(int n, int in, int out);
+void linear_grads_partial_launcher(int n, int in, int out, int x_type, int g_type, const void *x, const void *g, float *partials,
+                                   int partial_rows);
+void linear_grads_reduce_launcher(int in, int out, int has_bias, const float *partials, int partial_rows, float *grad_weight,
+                                  float *grad_bias);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ import sys
 
 __all__ = ["install", "build", "dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "scene_eval",
            "clean_supports", "box_supports", "scene_predict", "dense_points", "detect_boxes", "detect_scene", "install_fused_blocks", "segmentation_loss",
-           "fuse_batch_norms", "unfuse_batch_norms", "fuse_sync_batch_norms"]
+           "fuse_batch_norms", "unfuse_batch_norms", "fuse_sync_batch_norms", "fuse_linear_grads", "unfuse_linear_grads"]
 
 
 def __getattr__(name):
@@ -41,6 +41,9 @@ def __getattr__(name):
         from . import layers
         return layers.install_fused_blocks
     if name in ("fuse_batch_norms", "unfuse_batch_norms", "fuse_sync_batch_norms"):  # layers.*: BatchNorm1d / SyncBatchNorm + activation (+ residual) of the stem and the heads on csrc/batchnorm.hip
+        from . import layers
+        return getattr(layers, name)
+    if name in ("fuse_linear_grads", "unfuse_linear_grads"):  # layers.*: grad_weight / grad_bias of the nn.Linear modules on csrc/linear_grads.hip
         from . import layers
         return getattr(layers, name)
     if name == "segmentation_loss":  # pointops.segmentation_loss: cross-entropy, L1 shift, their sum and the IoU counts on csrc/seg_loss.hip

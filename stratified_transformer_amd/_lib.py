@@ -132,6 +132,8 @@ SIGNATURES = {
     "optim_step_launcher": [I, I, I, P, P, Z, P, P, I, D, P],
     "residual_norm_stream_forward_launcher": [I, I, I, I, I, P, P, P, P, P, F, P, P, P],
     "residual_norm_stream_backward_launcher": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, P],
+    "linear_grads_partial_launcher": [I, I, I, I, I, P, P, P, I],
+    "linear_grads_reduce_launcher": [I, I, I, P, I, P, P],
 }
 # entry points with a non-void result
 RESULTS = {
@@ -149,6 +151,7 @@ RESULTS = {
     "pointops2_evaltile_max_parts": ([], I),
     "pointops2_optim_workspace_bytes": ([I, I], Z),
     "pointops2_optim_step_workspace_bytes": ([I, I, Q], Z),
+    "pointops2_linear_grads_partial_rows": ([I, I, I], I),
 }
 # kind of optim_step_launcher (POINTOPS2_OPTIM_*)
 OPTIM_KINDS = {"adamw": 0, "sgd": 1}
@@ -157,6 +160,8 @@ OPTIM_KINDS = {"adamw": 0, "sgd": 1}
 CELL_FWD = {"error": -1, "none": 0, "mfma64": 1, "mfma80": 2, "valu80": 3, "valu160": 4}
 # storage type of the rows of a packed qkv (POINTOPS2_ROWS_*): cell_attention_qkv_*_launcher, grouped_max_*_launcher
 ROW_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+# rows of a chunk of linear_grads_partial_launcher (POINTOPS2_LINEAR_GRADS_ROWS): its partials have ceil(n / LINEAR_GRADS_ROWS) blocks
+LINEAR_GRADS_ROWS = 512
 # activation of batch_norm_act_*_launcher (POINTOPS2_ACT_*)
 ACTIVATIONS = {"none": 0, "relu": 1, "leaky_relu": 2, "tanh": 3}
 

@@ -45,6 +45,10 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
     BatchNorm1d + activation (+ the ResBlock's shortcut add) as one pointops.batch_norm_act call (csrc/batchnorm.hip).
     `fuse_sync_batch_norms(model)` takes nn.SyncBatchNorm sites too and runs pointops.sync_batch_norm_act wherever the module synchronises.
 
+  * The parameter gradients of the nn.Linear layers (off by default): `fuse_linear_grads(model)` binds, per instance, a forward that is
+    F.linear with grad_weight / grad_bias from pointops.linear_param_grads (csrc/linear_grads.hip) where linear_grads_worth_it admits
+    the shape at that call, and F.linear untouched everywhere else.
+
 Numbers: the same sums in another order (tests/test_hip_parity.py::test_installed_fast_layers_against_the_reference_layer:
 output and every parameter gradient of a depth-2 BasicLayer with TransitionDown against the reference's own run, <= 1e-3).
 """
@@ -834,6 +838,87 @@ def unfuse_batch_norms(model):
     """Removes what fuse_batch_norms or fuse_sync_batch_norms bound: every module of `model` runs its class's forward again"""
     for m in model.modules():
         if _bn_fused(m):
+            del m.__dict__["forward"]
+
+
+# ---- the parameter gradients of nn.Linear on csrc/linear_grads.hip (fuse_linear_grads; off by default) ----
+# Bound per instance exactly as the batch norms above.  The forward and grad_x stay torch's calls; only grad_weight / grad_bias move,
+# and only where linear_grads_worth_it admits the shape.
+def linear_grads_worth_it(n, in_features, out_features, row_type):
+    """Whether the bound nn.Linear forward takes pointops.linear_rows for n rows of `row_type` (torch.float32, torch.float16 or
+    torch.bfloat16) through an in -> out layer.  A rule of the four arguments alone, written from the measurement of
+    tools/bench_linear.py (profiles/linear_grads_bench.json), not tuned at run time: it admits the classes of shapes at
+    which one bound nn.Linear forward + backward was faster than the unbound one beyond the unbound side's spread (DESIGN.md 4.23 names
+    the one admitted shape whose gain lay inside the spread in the recorded run).
+      fp32 rows:  n >= 50 000 (every layer of the first stage and the heads), or n >= 20 000 with in * out >= 32 768 (fc1, fc2 of the
+                  second stage; its qkv and proj were inside the spread)
+      f16 rows:   n >= 50 000 with in * out >= 4 608 (qkv, fc1, fc2 of the first stage; 48 -> 48 was inside the spread)
+      bf16 rows:  never (not measured)
+    Everything smaller is bound by the host on both sides, or - a large result over few rows - is torch's by a margin."""
+    n, size = int(n), int(in_features) * int(out_features)
+    if row_type == torch.float32:
+        return n >= 50000 or (n >= 20000 and size >= 32768)
+    if row_type == torch.float16:
+        return n >= 50000 and size >= 4608
+    return False
+
+
+def fused_linear_forward(self, input):
+    """nn.Linear.forward with grad_weight / grad_bias on csrc/linear_grads.hip where every condition holds at this call (a GPU tensor of
+    f32 / f16 / bf16 rows, contiguous once flattened; a gradient is wanted and grad mode is on; in, out <= 1536; linear_grads_worth_it
+    admits the shape); F.linear(input, self.weight, self.bias), untouched, everywhere else."""
+    F = torch.nn.functional
+    x, w, b = input, self.weight, self.bias
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 2 and torch.is_grad_enabled()
+            and (w.requires_grad or (b is not None and b.requires_grad))
+            and w.is_cuda and w.device == x.device and 1 <= w.shape[0] <= P.LINEAR_GRADS_MAX_DIM and 1 <= w.shape[1] <= P.LINEAR_GRADS_MAX_DIM
+            and x.shape[-1] == w.shape[1] and w.dtype in _ROW_DTYPES and (b is None or b.dtype in _ROW_DTYPES)):
+        return F.linear(x, w, b)
+    if hasattr(torch, "get_autocast_dtype"):
+        autocast, row_type = torch.is_autocast_enabled("cuda"), torch.get_autocast_dtype("cuda")
+    else:
+        autocast, row_type = torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype()
+    row_type = row_type if autocast else x.dtype
+    if row_type not in _ROW_DTYPES or x.dtype not in _ROW_DTYPES:
+        return F.linear(x, w, b)
+    if not autocast and (w.dtype != x.dtype or (b is not None and b.dtype != x.dtype)):
+        return F.linear(x, w, b)  # (torch's own error, or its own promotion)
+    n = x.numel() // x.shape[-1]
+    if not x.is_contiguous() or not linear_grads_worth_it(n, int(w.shape[1]), int(w.shape[0]), row_type):
+        return F.linear(x, w, b)
+    if not autocast:
+        return P.linear_rows(x, w, b)
+    if x.dtype != row_type:
+        x = x.to(row_type)  # (the cast autocast makes for F.linear; differentiable)
+    with torch.autocast(device_type="cuda", enabled=False):
+        return P.linear_rows(x, w, b)
+
+
+def _linear_fused(m):
+    f = m.__dict__.get("forward")
+    return f is not None and getattr(f, "__func__", None) is fused_linear_forward
+
+
+def fuse_linear_grads(model):
+    """Binds fused_linear_forward on every nn.Linear of `model` (exactly nn.Linear, not a subclass) and returns their names in module
+    order.  An instance that already carries someone else's forward is left alone.  No parameter is added, replaced or renamed.
+    Whether a call takes the fused backward is decided at that call (fused_linear_forward).  unfuse_linear_grads(model) undoes it."""
+    import types
+    names = []
+    for name, m in model.named_modules():
+        if type(m) is not torch.nn.Linear:
+            continue
+        if "forward" in m.__dict__ and not _linear_fused(m):
+            continue  # someone else's instance-level forward: left alone
+        m.__dict__["forward"] = types.MethodType(fused_linear_forward, m)
+        names.append(name)
+    return names
+
+
+def unfuse_linear_grads(model):
+    """Removes what fuse_linear_grads bound: every nn.Linear of `model` runs its class's forward again"""
+    for m in model.modules():
+        if _linear_fused(m):
             del m.__dict__["forward"]
 
 

@@ -1145,6 +1145,109 @@ def residual_norm_stream(x, y, row_scale, weight, bias, eps=1e-5, out_dtype=None
 
 
 # ---------------------------------------------------------------------------------------------
+# the parameter gradients of a Linear over point rows: grad_weight and grad_bias from one read of x and grad_out (csrc/linear_grads.hip)
+# ---------------------------------------------------------------------------------------------
+LINEAR_GRADS_ROWS = pointops_cuda.LINEAR_GRADS_ROWS  # R: the rows are summed in chunks of R, the chunks in ascending order
+LINEAR_GRADS_MAX_DIM = pointops_cuda.LINEAR_GRADS_MAX_DIM
+
+
+def linear_param_grads(x, grad_out, bias=True):
+    """(grad_weight [out, in] f32, grad_bias [out] f32 or None) of y = F.linear(x, W, b): grad_out.t() @ x and grad_out.sum(0) over the
+    rows, in fp32 on the matrix cores from one read of both operands (two launches: per-chunk partial sums, then their sum in a fixed
+    order; no float atomics, the same bits on every run).  x [..., in] and grad_out [..., out] are flattened over their leading
+    dimensions and may each be f32, f16 or bf16 (widened exactly).  1 <= in, out <= 1536; any row count, 0 included (zeros).  Runs the
+    kernels whatever the shape - whether that pays is the caller's question (layers.linear_grads_worth_it).  Not differentiable: it is
+    what a backward calls."""
+    op = "linear_param_grads"
+    for name, t in (("x", x), ("grad_out", grad_out)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{op}: {name} must be a tensor, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise RuntimeError(f"{op}: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+        if t.dtype not in _ROW_DTYPES:
+            raise TypeError(f"{op}: {name} must be f32, f16 or bf16, got {t.dtype}")
+        if t.dim() < 2:
+            raise ValueError(f"{op}: {name} must be [..., features], got {tuple(t.shape)}")
+    if grad_out.device != x.device:
+        raise RuntimeError(f"{op}: grad_out is on {grad_out.device}, x on {x.device}")
+    if tuple(x.shape[:-1]) != tuple(grad_out.shape[:-1]):
+        raise ValueError(f"{op}: x {tuple(x.shape)} and grad_out {tuple(grad_out.shape)} must agree in their leading dimensions")
+    n_in, n_out = x.shape[-1], grad_out.shape[-1]
+    if not (1 <= n_in <= LINEAR_GRADS_MAX_DIM and 1 <= n_out <= LINEAR_GRADS_MAX_DIM):
+        raise ValueError(f"{op}: in and out must be in [1, {LINEAR_GRADS_MAX_DIM}], got x {tuple(x.shape)}, grad_out {tuple(grad_out.shape)}")
+    n = x.numel() // n_in
+    if n >= 2 ** 31:
+        raise ValueError(f"{op}: {n} rows: the row count must fit an int32")
+    return _linear_param_grads_rows(x.detach().reshape(n, n_in), grad_out.detach().reshape(n, n_out), bias)
+
+
+def _linear_param_grads_rows(x2, g2, bias):
+    """linear_param_grads behind its checks: x2 [n, in], g2 [n, out] GPU rows of f32 / f16 / bf16 on one device, in, out <= 1536.  Straight
+    to the two launchers - a backward calls this once per Linear, and at the model's small stages the host's time per call is what
+    the device waits for.  The library itself refuses a row count of `partials` other than its own."""
+    x2, g2 = x2.contiguous(), g2.contiguous()
+    (n, n_in), n_out, dev = x2.shape, g2.shape[1], x2.device
+    rows = max(1, -(-n // LINEAR_GRADS_ROWS))
+    partials = torch.empty((rows, n_out, n_in + 1), dtype=torch.float32, device=dev)
+    grad_w = torch.empty((n_out, n_in), dtype=torch.float32, device=dev)
+    grad_b = torch.empty((n_out,), dtype=torch.float32, device=dev) if bias else None
+    types = _lib.ROW_TYPES
+    pointops_cuda._call("linear_grads_partial_launcher", x2, n, n_in, n_out, types[x2.dtype], types[g2.dtype], x2.data_ptr(), g2.data_ptr(),
+                        partials.data_ptr(), rows)
+    pointops_cuda._call("linear_grads_reduce_launcher", x2, n_in, n_out, int(bias), partials.data_ptr(), rows, grad_w.data_ptr(),
+                        grad_b.data_ptr() if bias else None)
+    return grad_w, grad_b
+
+
+class LinearRows(Function):
+    """F.linear(x, weight, bias) whose backward takes grad_weight and grad_bias from linear_param_grads; the forward and grad_x are
+    torch's own calls on the same operands.  weight / bias of another dtype than x are cast to x's first - the cast autocast makes -
+    and their gradients come back in the parameters' own dtypes: fp32 parameters get the fp32 sums unrounded."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        w = weight if weight.dtype == x.dtype else weight.to(x.dtype)
+        b = bias if bias is None or bias.dtype == x.dtype else bias.to(x.dtype)
+        ctx.save_for_backward(x, w)
+        ctx.param_dtypes = (weight.dtype, None if bias is None else bias.dtype)
+        return torch.nn.functional.linear(x, w, b)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad
+        grad_x = grad_out @ w if need_x else None
+        grad_w = grad_b = None
+        if need_w or need_b:
+            n_in = x.shape[-1]
+            grad_w, grad_b = _linear_param_grads_rows(x.reshape(-1, n_in), grad_out.reshape(x.numel() // n_in, -1), bool(need_b))
+            w_dtype, b_dtype = ctx.param_dtypes
+            grad_w = (grad_w if w_dtype == torch.float32 else grad_w.to(w_dtype)) if need_w else None
+            if grad_b is not None and b_dtype != torch.float32:
+                grad_b = grad_b.to(b_dtype)
+        return grad_x, grad_w, grad_b
+
+
+def linear_rows(x, weight, bias=None):
+    """F.linear(x, weight, bias) for GPU rows x [..., in] of f32 / f16 / bf16 with the parameter gradients on csrc/linear_grads.hip
+    (LinearRows).  Call it with autocast off: the operands are used as given, weight and bias cast to x's dtype."""
+    op = "linear_rows"
+    if not (torch.is_tensor(x) and torch.is_tensor(weight)):
+        raise TypeError(f"{op}: x and weight must be tensors")
+    if not (x.is_cuda and weight.is_cuda):
+        raise RuntimeError(f"{op}: expected GPU tensors (the pointops2 HIP path has no CPU fallback), got x on {x.device}, weight on {weight.device}")
+    if x.dtype not in _ROW_DTYPES:
+        raise TypeError(f"{op}: x must be f32, f16 or bf16, got {x.dtype}")
+    if weight.dim() != 2 or x.dim() < 2 or x.shape[-1] != weight.shape[1]:
+        raise ValueError(f"{op}: x must be [..., in] and weight [out, in], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"{op}: bias must be [{weight.shape[0]}], got {tuple(bias.shape)}")
+    if not (1 <= weight.shape[0] <= LINEAR_GRADS_MAX_DIM and 1 <= weight.shape[1] <= LINEAR_GRADS_MAX_DIM):
+        raise ValueError(f"{op}: in and out must be in [1, {LINEAR_GRADS_MAX_DIM}], got weight {tuple(weight.shape)}")
+    return LinearRows.apply(x, weight, bias)
+
+
+# ---------------------------------------------------------------------------------------------
 # BatchNorm1d over point rows + activation + residual add: the glue of the stem and the heads (csrc/batchnorm.hip)
 # ---------------------------------------------------------------------------------------------
 def _batch_norm_partials(n, c, width, like):

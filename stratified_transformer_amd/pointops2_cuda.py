@@ -242,6 +242,56 @@ def residual_norm_stream_backward(n, c, grad_o, grad_z, z, stat, row_scale, weig
           ptr(grad_x), ptr(grad_y), ptr(partials), rows, ptr(grad_weight), ptr(grad_bias), opts=opts)
 
 
+# csrc/linear_grads.hip (no counterpart in the reference's launcher set: grad_weight and grad_bias of a Linear over point rows)
+LINEAR_GRADS_MAX_DIM = 1536
+LINEAR_GRADS_ROWS = _lib.LINEAR_GRADS_ROWS  # rows of a chunk: one block of `partials` each
+
+
+def _linear_grads_sizes(in_features, out_features):
+    in_features, out_features = int(in_features), int(out_features)
+    for name, v in (("in", in_features), ("out", out_features)):
+        if not 1 <= v <= LINEAR_GRADS_MAX_DIM:
+            raise ValueError(f"{name}: expected 1 <= {name} <= {LINEAR_GRADS_MAX_DIM}, got {v}")
+    return in_features, out_features
+
+
+def linear_grads_partial_rows(n, in_features, out_features):
+    """blocks of the `partials` of n rows: ceil(n / LINEAR_GRADS_ROWS), 1 for n == 0; a function of n alone.  No launch, no GPU."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n: expected a row count >= 0, got {n}")
+    in_features, out_features = _linear_grads_sizes(in_features, out_features)
+    return int(_lib.lib().pointops2_linear_grads_partial_rows(n, in_features, out_features))
+
+
+def linear_grads_partial(n, in_features, out_features, x, g, partials, *, opts=None):
+    """partials [G, out, in + 1] f32 (fully written; column `in` is the bias partial) <- x [n, in], g [n, out], each f32 / f16 / bf16;
+    G = linear_grads_partial_rows(n, in, out)"""
+    rows = linear_grads_partial_rows(n, in_features, out_features)
+    n, (in_features, out_features) = int(n), _linear_grads_sizes(in_features, out_features)
+    xt, gt = _row_type(x, "x"), _row_type(g, "g")
+    _chk((x, x.dtype, "x"), (g, g.dtype, "g"), (partials, F32, "partials"))
+    _shaped(x, (n, in_features), "x"), _shaped(g, (n, out_features), "g")
+    if partials.dim() != 3 or tuple(partials.shape[1:]) != (out_features, in_features + 1):
+        raise ValueError(f"partials: expected shape [rows, {out_features}, {in_features + 1}], got {list(partials.shape)}")
+    # (a wrong row count is the library's own rejection: it knows G)
+    _call("linear_grads_partial_launcher", partials, n, in_features, out_features, xt, gt, ptr(x), ptr(g), ptr(partials), int(partials.shape[0]),
+          opts=opts)
+    return rows
+
+
+def linear_grads_reduce(in_features, out_features, partials, grad_weight, grad_bias, *, opts=None):
+    """grad_weight [out, in] f32, grad_bias [out] f32 or None (fully written) <- partials [G, out, in + 1] f32, added in ascending order"""
+    in_features, out_features = _linear_grads_sizes(in_features, out_features)
+    _chk((partials, F32, "partials"), (grad_weight, F32, "grad_weight"))
+    if partials.dim() != 3 or partials.shape[0] < 1 or tuple(partials.shape[1:]) != (out_features, in_features + 1):
+        raise ValueError(f"partials: expected shape [rows >= 1, {out_features}, {in_features + 1}], got {list(partials.shape)}")
+    _shaped(grad_weight, (out_features, in_features), "grad_weight")
+    _opt(grad_bias, F32, (out_features,), "grad_bias")
+    _call("linear_grads_reduce_launcher", partials, in_features, out_features, int(grad_bias is not None), ptr(partials), int(partials.shape[0]),
+          ptr(grad_weight), ptr(grad_bias), opts=opts)
+
+
 # csrc/batchnorm.hip (no counterpart in the reference's launcher set: BatchNorm1d + activation + residual add of the stem and the heads)
 BATCH_NORM_MAX_C = 1024
 BATCH_NORM_PARTIAL_ROWS = 1024  # most workgroups of the two reductions: one row of `partials` each
