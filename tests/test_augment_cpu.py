@@ -14,13 +14,13 @@ Bounds (float64 inputs; eps = 2^-53):
     covered by the factor 1 + 2^-40.
 """
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from stratified_transformer_amd import _lib, augment as A, dataprep, pointops
+from tests import abi_header
 from tests import augment_cases as cases
 from tests import augment_oracle as O
 
@@ -253,14 +253,11 @@ def test_launchers_are_declared_bound_and_exported():
     I, P, Q = _lib.I, _lib.P, _lib.Q
     assert _lib.SIGNATURES["pointops2_augment_pass_launcher"] == [I] * 6 + [P] * 10
     assert _lib.SIGNATURES["pointops2_augment_blur_launcher"] == [Q, I, I, P, P, P]
-    for name in ("pointops2_augment_pass_launcher", "pointops2_augment_blur_launcher"):
-        assert name in _lib.exported_symbols() and hasattr(_lib.lib(), name)
-    text = open(os.path.join(ROOT, "include", "pointops2_hip.h")).read()
-    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define POINTOPS2_AUGMENT_(\w+)\s+(\d+)", text)}
-    assert {k.lower()[3:]: v for k, v in defines.items() if k.startswith("OP_") and k != "OP_NOP"} == A.OP
-    assert (defines["PARAMS"], defines["MAX_OPS"], defines["STAT_WORDS"]) == (A.PARAMS, A.MAX_OPS, A.STAT_WORDS)
-    assert (defines["HAS_FEAT"], defines["STORE"], defines["STATS"]) == (A.HAS_FEAT, A.STORE, A.STATS)
-    assert defines["MAX_SCENES"] == 1024
+    defines = abi_header.codes("POINTOPS2_AUGMENT_")
+    assert {k[3:]: v for k, v in defines.items() if k.startswith("op_") and k != "op_nop"} == A.OP
+    assert (defines["params"], defines["max_ops"], defines["stat_words"]) == (A.PARAMS, A.MAX_OPS, A.STAT_WORDS)
+    assert (defines["has_feat"], defines["store"], defines["stats"]) == (A.HAS_FEAT, A.STORE, A.STATS)
+    assert defines["max_scenes"] == 1024
     assert "augment.hip" in open(os.path.join(_lib.CSRC, "Makefile")).read()
 
 

@@ -1,45 +1,30 @@
 """CPU: the C-ABI surface of the cell attention on the packed qkv projection (ABI version 5).  No HIP compute runs here."""
 import ctypes
-import os
-import re
-import subprocess
 
 import torch
 
 from stratified_transformer_amd import _lib, index_build
+from tests import abi_header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "pointops2_hip.h")
 NEW = ("cell_attention_qkv_forward_launcher", "cell_attention_qkv_backward_launcher")
 
 
 def test_header_compiles_as_c_with_the_packed_prototypes(tmp_path):
     """The header is C: a C99 translation unit that takes the address of both launchers with their full prototypes and uses the
     row-type constants compiles without warnings."""
-    src = tmp_path / "abi.c"
-    src.write_text('#include "pointops2_hip.h"\n'
-                   "typedef void (*fwd_t)(const pointops2_cell_plan *, int, int, int, const void *, int, float, const float *, const float *,\n"
-                   "                      const float *, float *, float *, float *);\n"
-                   "typedef void (*bwd_t)(const pointops2_cell_plan *, int, int, int, const float *, const void *, int, float, const float *,\n"
-                   "                      const float *, const float *, const float *, const float *, float *, float *, float *, float *, float *);\n"
-                   "fwd_t f = cell_attention_qkv_forward_launcher;\nbwd_t b = cell_attention_qkv_backward_launcher;\n"
-                   "int row_types[3] = {POINTOPS2_ROWS_F32, POINTOPS2_ROWS_F16, POINTOPS2_ROWS_BF16};\n")
-    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
-                    str(tmp_path / "abi.o")], check=True)
-    text = open(HEADER).read()
-    rows = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define POINTOPS2_ROWS_(\w+)\s+(\d+)", text)}
-    assert rows == {"F32": 0, "F16": 1, "BF16": 2}
-    assert _lib.ROW_TYPES == {torch.float32: rows["F32"], torch.float16: rows["F16"], torch.bfloat16: rows["BF16"]}
+    abi_header.compile_c(
+        "typedef void (*fwd_t)(const pointops2_cell_plan *, int, int, int, const void *, int, float, const float *, const float *,\n"
+        "                      const float *, float *, float *, float *);\n"
+        "typedef void (*bwd_t)(const pointops2_cell_plan *, int, int, int, const float *, const void *, int, float, const float *,\n"
+        "                      const float *, const float *, const float *, const float *, float *, float *, float *, float *, float *);\n"
+        "fwd_t f = cell_attention_qkv_forward_launcher;\nbwd_t b = cell_attention_qkv_backward_launcher;\n"
+        "int row_types[3] = {POINTOPS2_ROWS_F32, POINTOPS2_ROWS_F16, POINTOPS2_ROWS_BF16};\n", tmp_path, "abi", link=False)
+    rows = abi_header.codes("POINTOPS2_ROWS_")
+    assert rows == {"f32": 0, "f16": 1, "bf16": 2}
+    assert _lib.ROW_TYPES == {torch.float32: rows["f32"], torch.float16: rows["f16"], torch.bfloat16: rows["bf16"]}
 
 
 def test_library_exports_the_packed_launchers_at_abi_version_5():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    l = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert hasattr(l, name), name
-        assert name in _lib.SIGNATURES and name in _lib.exported_symbols()
-    assert _lib.lib().pointops2_abi_version() == 5
     # plan, h, hdim, L, qkv, row_type, scale, three tables, out, ml, pbuf
     I, P, F = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
     assert _lib.SIGNATURES[NEW[0]] == [P, I, I, I, P, I, F, P, P, P, P, P, P]

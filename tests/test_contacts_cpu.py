@@ -4,7 +4,6 @@ components, the host pairing of stratified_transformer_amd.cluster.link_objects 
 contacts / objects that need no GPU.  No HIP compute runs here."""
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,7 +14,6 @@ from stratified_transformer_amd import _lib, cluster
 from tests import contacts_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAUNCHERS = ["pointops2_contacts_count_launcher", "pointops2_contacts_min_launcher"]
 F, L = torch.float32, torch.int64
 
 
@@ -170,18 +168,6 @@ def test_rule_5_numbering_by_ascending_smallest_face():
     links = {(6, 1): 10, (6, 4): 10, (7, 0): 10, (7, 5): 10, (8, 2): 10}
     object_of, n = _link(cls, links)
     assert n == 3 and object_of == [0, 1, 2, -1, 1, 0, 1, 0, 2]
-
-
-def test_launchers_are_declared_and_exported():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pointops2_hip.h")).read(), flags=re.S)
-    kinds = {"int": _lib.I, "float": _lib.F}
-    for name in LAUNCHERS:
-        m = re.search(r"void\s+" + name + r"\s*\(([^)]*)\)", text)
-        assert m, f"{name} is not declared in include/pointops2_hip.h"
-        want = [_lib.P if "*" in a else kinds[a.split()[0]] for a in m.group(1).split(",")]
-        assert _lib.SIGNATURES[name] == want, name
-        assert name in _lib.exported_symbols() and hasattr(_lib.lib(), name)
-    assert _lib.lib().pointops2_abi_version() == 5  # additions only
 
 
 def test_public_interface():

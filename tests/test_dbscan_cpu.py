@@ -3,7 +3,6 @@
 stratified_transformer_amd.cluster: declarations, argument checks, the missing CPU path, N == 0.  No HIP compute runs here."""
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,8 +13,6 @@ from stratified_transformer_amd import _lib, cluster
 from tests import dbscan_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAUNCHERS = ["pointops2_dbscan_keys_launcher", "pointops2_dbscan_prepare_launcher", "pointops2_dbscan_core_launcher",
-             "pointops2_dbscan_round_launcher", "pointops2_dbscan_label_launcher"]
 
 
 @pytest.fixture(scope="module")
@@ -86,19 +83,6 @@ def test_oracle_rules_on_a_hand_built_case():
     # groups: numbers restart per group, group -1 is left out
     labels, core, n = O.dbscan(np.concatenate([xyz, xyz]), [eps, eps], [4, 4], np.array([1] * 10 + [0] * 9 + [-1]))
     assert labels.tolist() == ([0] * 4 + [1] * 4 + [0, -1]) * 2 and n.tolist() == [2, 2] and not core[-1]
-
-
-def test_launchers_are_declared_and_exported():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pointops2_hip.h")).read(), flags=re.S)
-    I, P, D = _lib.I, _lib.P, _lib.D
-    kinds = {"int": I, "double": D}
-    for name in LAUNCHERS:
-        m = re.search(r"void\s+" + name + r"\s*\(([^)]*)\)", text)
-        assert m, f"{name} is not declared in include/pointops2_hip.h"
-        want = [P if "*" in a else kinds[a.split()[0]] for a in m.group(1).split(",")]
-        assert _lib.SIGNATURES[name] == want, name
-        assert name in _lib.exported_symbols() and hasattr(_lib.lib(), name)
-    assert _lib.lib().pointops2_abi_version() == 5  # additions only
 
 
 def test_public_interface():

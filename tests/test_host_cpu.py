@@ -1,10 +1,6 @@
-"""CPU: host-side logic of the product (index build orchestration, third-party shims, the C-ABI
-surface).  No HIP compute is executed here (there is no GPU in the build container)."""
-import ctypes
+"""CPU: host-side logic of the product (index build orchestration, third-party shims, the cell forward
+dispatch).  No HIP compute is executed here (there is no GPU in the build container)."""
 import inspect
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,8 +9,7 @@ import torch
 import stratified_transformer_amd as sta
 from stratified_transformer_amd import _lib, compat, index_build
 from oracle import index_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import abi_header
 
 
 def _t(a):
@@ -137,31 +132,7 @@ def test_operator_signatures_match_reference_api():
     assert list(inspect.signature(P.interpolation).parameters) == ["xyz", "new_xyz", "feat", "offset", "new_offset", "k"]
 
 
-# ---- C ABI ------------------------------------------------------------------------------------
-def _header_functions():
-    text = open(os.path.join(ROOT, "include", "pointops2_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b([a-z_0-9]+)\s*\(", " ".join(l for l in text.splitlines() if not l.strip().startswith("#")))) - {"defined"})
-
-
-def test_library_exports_every_symbol_of_the_header():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    names = _header_functions()
-    assert len(names) >= 30
-    l = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(l, n), f"{n} declared in include/pointops2_hip.h but not exported"
-    assert set(_lib.exported_symbols()) == set(names), set(_lib.exported_symbols()) ^ set(names)
-    # and the reverse: every ABI-named symbol the library exports is declared in the header
-    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    abi = {l.split()[-1] for l in nm.splitlines() if l.strip()}
-    abi = {n for n in abi if n.startswith("pointops2_") or n.endswith("_launcher")}
-    assert len(abi) >= 30
-    assert abi <= set(names), f"exported but not declared in include/pointops2_hip.h: {sorted(abi - set(names))}"
-    assert _lib.lib().pointops2_abi_version() >= 3
-
-
+# ---- cell forward dispatch (the header against its Python mirrors: tests/test_abi_cpu.py) ----
 def _cell_plan_struct(n_points, n_pairs, n_keyslots, table_rows):
     """a pointops2_cell_plan with the host fields the forward dispatch reads and no device arrays"""
     return index_build.CellPlanStruct(n_points=n_points, n_cells=1, n_parents=1, n_pairs=n_pairs, n_keyslots=n_keyslots, table_rows=table_rows)
@@ -172,9 +143,7 @@ def test_cell_forward_dispatch_table():
     fp32 with L <= 80 runs on the matrix cores unless n_points * h >= 96000 and the cells average fewer than 15 queries
     (n_pairs / n_keyslots); L in 81..160 and bf16 storage run the VALU kernels; d != 16, L > 160 and tables the plan was not
     built for are errors."""
-    text = open(os.path.join(ROOT, "include", "pointops2_hip.h")).read()
-    codes = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define POINTOPS2_CELL_FWD_(\w+)\s+\(?(-?\d+)\)?", text)}
-    assert codes == _lib.CELL_FWD
+    assert abi_header.codes("POINTOPS2_CELL_FWD_") == _lib.CELL_FWD
     v = _lib.cell_forward_variant
     small, big = 15 * 10, 149  # n_pairs over 10 key slots: an average of 15.0 / 14.9 queries per cell
     for L, mfma in ((1, "mfma64"), (64, "mfma64"), (65, "mfma80"), (80, "mfma80")):
@@ -200,26 +169,6 @@ def test_cell_forward_dispatch_table():
         # nothing to launch: no plan, no points
         assert v(None, 1, 64, bf16=bf16) == "none"
         assert v(_cell_plan_struct(0, 0, 0, 64), 1, 64, bf16=bf16) == "none"
-
-
-def test_launch_opts_struct_matches_the_header(tmp_path):
-    """_lib.LaunchOpts mirrors pointops2_launch_opts field by field: a layout mismatch would hand the library misplaced
-    pointers without any error.  The host C compiler reports sizeof and every offsetof of the header's struct."""
-    fields = [name for name, _ in _lib.LaunchOpts._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pointops2_hip.h"\nint main(void) {\n'
-                   + "".join(f'printf("{f} %zu\\n", offsetof(pointops2_launch_opts, {f}));\n' for f in fields)
-                   + 'printf("sizeof %zu\\n", sizeof(pointops2_launch_opts));\nreturn 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
-                   check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got.pop("sizeof")) == ctypes.sizeof(_lib.LaunchOpts)
-    assert {f: int(v) for f, v in got.items()} == {f: getattr(_lib.LaunchOpts, f).offset for f in fields}
-    # and the header declares no field the ctypes mirror lacks
-    text = open(os.path.join(ROOT, "include", "pointops2_hip.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", text[text.index("typedef struct pointops2_launch_opts"):text.index("} pointops2_launch_opts;")], flags=re.S)
-    assert re.findall(r"(\w+);", body) == fields
 
 
 def test_product_path_fails_loudly_without_gpu_tensors():

