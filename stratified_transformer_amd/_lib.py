@@ -224,7 +224,15 @@ def check_tensor(t, dtype, name):
     return t
 
 
+def check_tensors(*triples):
+    """check_tensor for each (tensor, dtype, name)"""
+    for t, dt, name in triples:
+        check_tensor(t, dt, name)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+# the current device's index without torch.cuda.current_device's lazy-init check (a launch has device tensors: torch is initialised)
+_current_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device
 
 
 CALLS = [0]  # library launcher calls so far (bench.py: per pass)
@@ -232,8 +240,23 @@ CALLS = [0]  # library launcher calls so far (bench.py: per pass)
 
 def call(name, *args, device=None, opts=None):
     """Launch `name` on torch's current stream of `device` and surface library errors.  opts: LaunchOpts for this launch
-    (None: the reference's arguments alone)."""
+    (None: the reference's arguments alone).
+
+    The library works on the CURRENT HIP device: the side streams and events of ForkJoin (csrc/misc.hip), the
+    hipFuncSetAttribute of allow_big_lds, num_cus() and the held-CU events are all state of whichever device was current
+    when they were first touched.  So this function, and no caller, makes the operands' device current: `device` None or
+    without an index means the current device; an index equal to the current device's builds no guard object (the usual
+    case, and these calls are bound by the host); any other index runs the whole sequence - set_stream, set_launch_opts,
+    the launcher, last_error - under torch.cuda.device(device)."""
     CALLS[0] += 1
+    if device is not None and device.index is not None and device.index != _current_device():
+        with torch.cuda.device(device):
+            _launch(name, args, device, opts)
+    else:
+        _launch(name, args, device, opts)
+
+
+def _launch(name, args, device, opts):
     l = lib()
     if _raw_stream is not None and device is not None and device.index is not None:
         stream = _raw_stream(device.index)  # the raw hipStream_t, without building a torch.cuda.Stream object

@@ -30,7 +30,6 @@ the nine prepared runs per point) build it here, csrc/radius_grid.h walks it on 
 The stages on a labelled cloud share the prologue `_labelled` (with `_scan`, the read-back up front) and the one-group grid `_label_grid`.
 """
 import collections
-import contextlib
 import ctypes
 import itertools
 
@@ -167,8 +166,7 @@ class _Call:
 
     def launch(self, name, *args):
         self.count("launches")
-        with contextlib.nullcontext() if self.dev.index == torch.cuda.current_device() else torch.cuda.device(self.dev):
-            _lib.call(name, *args, device=self.dev)
+        _lib.call(name, *args, device=self.dev)
 
     def read(self, *tensors):
         """ONE transfer: the tensors (of one dtype) concatenated, brought to the host and split again -> a numpy array per tensor, in its

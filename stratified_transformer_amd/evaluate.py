@@ -81,26 +81,27 @@ def crop_cover(coord, voxel_max, priority=None):
     report = torch.zeros(2, dtype=torch.int32, device=dev)
     crops, seeds = [], []
     LAST["crops"], LAST["reads"] = 0, 0
-    with torch.cuda.device(dev):
-        while True:
-            if len(crops) == n:
-                raise RuntimeError(f"crop_cover: {n} crops have not covered the {n} points")
-            _lib.call("pointops2_evaltile_seed_dist_launcher", n, is_f64, ptr(coord), ptr(priority), ptr(part_value), ptr(part_index), ptr(seed),
-                      ptr(dist), device=dev)
-            crop = torch.sort(dist, stable=True)[1][:voxel_max].clone()
-            _lib.call("pointops2_evaltile_update_launcher", n, voxel_max, is_f64, ptr(dist), ptr(crop), ptr(priority), ptr(covered), ptr(report),
-                      device=dev)
-            crops.append(crop)
-            seeds.append(seed.clone())
-            n_covered, status = report.tolist()                      # the one small read-back per crop
-            LAST["crops"], LAST["reads"] = len(crops), LAST["reads"] + 1
-            if status == STATUS_DMAX_ZERO:
-                raise ValueError(f"crop_cover: the {voxel_max} points nearest to seed point {int(seed)} (crop {len(crops) - 1}) coincide with it "
-                                 f"(largest distance 0; {n_covered} of {n} points covered): the reference's loop divides 0 / 0 here and never ends")
-            if status != 0:
-                raise RuntimeError(f"crop_cover: the sort returned an index outside [0, {n}) (status {status})")
-            if n_covered == n:
-                break
+    # (no device guard: the two launches get theirs from _lib.call; the sort, the clones and the read-backs are torch operators on
+    # tensors of `dev`, which run on their operands' device whichever is current)
+    while True:
+        if len(crops) == n:
+            raise RuntimeError(f"crop_cover: {n} crops have not covered the {n} points")
+        _lib.call("pointops2_evaltile_seed_dist_launcher", n, is_f64, ptr(coord), ptr(priority), ptr(part_value), ptr(part_index), ptr(seed),
+                  ptr(dist), device=dev)
+        crop = torch.sort(dist, stable=True)[1][:voxel_max].clone()
+        _lib.call("pointops2_evaltile_update_launcher", n, voxel_max, is_f64, ptr(dist), ptr(crop), ptr(priority), ptr(covered), ptr(report),
+                  device=dev)
+        crops.append(crop)
+        seeds.append(seed.clone())
+        n_covered, status = report.tolist()                      # the one small read-back per crop
+        LAST["crops"], LAST["reads"] = len(crops), LAST["reads"] + 1
+        if status == STATUS_DMAX_ZERO:
+            raise ValueError(f"crop_cover: the {voxel_max} points nearest to seed point {int(seed)} (crop {len(crops) - 1}) coincide with it "
+                             f"(largest distance 0; {n_covered} of {n} points covered): the reference's loop divides 0 / 0 here and never ends")
+        if status != 0:
+            raise RuntimeError(f"crop_cover: the sort returned an index outside [0, {n}) (status {status})")
+        if n_covered == n:
+            break
     return torch.stack(crops), torch.cat(seeds), priority
 
 
@@ -142,9 +143,8 @@ class SceneVotes:
     def add(self, logits, idx):
         logits, idx = self._rows(logits, idx)
         n_points, classes = self.pred.shape
-        with torch.cuda.device(self.pred.device):
-            _lib.call("pointops2_evaltile_vote_launcher", logits.shape[0], classes, n_points, _lib.ROW_TYPES[logits.dtype], ptr(logits), ptr(idx),
-                      ptr(self._stamp), ptr(self.pred), ptr(self._status), device=self.pred.device)
+        _lib.call("pointops2_evaltile_vote_launcher", logits.shape[0], classes, n_points, _lib.ROW_TYPES[logits.dtype], ptr(logits), ptr(idx),
+                  ptr(self._stamp), ptr(self.pred), ptr(self._status), device=self.pred.device)
 
     def _check(self):
         if int(self._status.item()) != 0:
@@ -178,10 +178,9 @@ class SceneShiftVotes(SceneVotes):
             raise RuntimeError(f"SceneVotes.add: shift on {shift.device}, the votes on {self.pred.device}")
         shift = shift.detach().contiguous()
         n_points, classes = self.pred.shape
-        with torch.cuda.device(self.pred.device):
-            _lib.call("pointops2_evaltile_vote_shift_launcher", logits.shape[0], classes, n_points, _lib.ROW_TYPES[logits.dtype], ptr(logits),
-                      _lib.ROW_TYPES[shift.dtype], ptr(shift), ptr(idx), ptr(self._stamp), ptr(self.pred), ptr(self.shift), ptr(self._status),
-                      device=self.pred.device)
+        _lib.call("pointops2_evaltile_vote_shift_launcher", logits.shape[0], classes, n_points, _lib.ROW_TYPES[logits.dtype], ptr(logits),
+                  _lib.ROW_TYPES[shift.dtype], ptr(shift), ptr(idx), ptr(self._stamp), ptr(self.pred), ptr(self.shift), ptr(self._status),
+                  device=self.pred.device)
 
 
 def intersection_and_union(output, target, K, ignore_index=255):

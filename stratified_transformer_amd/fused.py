@@ -38,14 +38,14 @@ class WindowAttention(Function):
         L = table_q.shape[0]
         assert table_k.shape[0] == L and table_v.shape[0] == L
         P._check_pair_list("window_attention", N, index0_offsets, index1, rel_idx)
-        pointops_cuda._chk((q, torch.float32, "q"), (k, torch.float32, "k"), (v, torch.float32, "v"),
+        _lib.check_tensors((q, torch.float32, "q"), (k, torch.float32, "k"), (v, torch.float32, "v"),
                            (table_q, torch.float32, "table_q"), (table_k, torch.float32, "table_k"), (table_v, torch.float32, "table_v"),
                            (index0_offsets, torch.int32, "index0_offsets"), (index1, torch.int32, "index1"), (rel_idx, torch.int32, "rel_idx"))
         attn = torch.empty((M, h), dtype=torch.float32, device=q.device)
         out = torch.zeros((N, h, hdim), dtype=torch.float32, device=q.device)
         opts = _lib.with_table_rows(P.pair_opts(index0_offsets, index1), L)  # (the pair walkers take their rows in window order, csrc/common.h)
-        pointops_cuda._call("window_logits_softmax_forward_launcher", q, int(index0_offsets.shape[0]) - 1, M, h, hdim,
-                            ptr(q), ptr(index0_offsets), ptr(k), ptr(index1), ptr(table_q), ptr(table_k), ptr(rel_idx), ptr(attn), opts=opts)
+        _lib.call("window_logits_softmax_forward_launcher", int(index0_offsets.shape[0]) - 1, M, h, hdim, ptr(q), ptr(index0_offsets), ptr(k),
+                  ptr(index1), ptr(table_q), ptr(table_k), ptr(rel_idx), ptr(attn), device=q.device, opts=opts)
         pointops_cuda.attention_step2_with_rel_pos_value_forward_cuda_v2(N, M, h, hdim, 0, attn, v, index0_offsets, index1, table_v, rel_idx, out,
                                                                          opts=opts)
         ctx.save_for_backward(q, k, v, table_q, table_k, table_v, index0_offsets, index1, rel_idx, attn)
@@ -68,10 +68,10 @@ class WindowAttention(Function):
             # two walks (by query, by key) + the three table gradients: DESIGN.md 4.5
             grad_logit, grad_q, grad_k, grad_v = e(M, h), e(N, h, hdim), e(NK, h, hdim), e(v.shape[0], h, hdim)
             grad_tq, grad_tk, grad_tv = z(L, h, hdim, 3), z(L, h, hdim, 3), z(L, h, hdim, 3)
-            pointops_cuda._chk((grad_out, torch.float32, "grad_out"))
-            pointops_cuda._call("window_attention_backward_launcher", q, int(offs.shape[0]) - 1, M, h, hdim, ptr(grad_out), ptr(q), ptr(k),
-                                ptr(v), ptr(attn), ptr(offs), ptr(index1), ptr(table_q), ptr(table_k), ptr(table_v), ptr(rel_idx),
-                                ptr(grad_logit), ptr(grad_q), ptr(grad_k), ptr(grad_v), ptr(grad_tq), ptr(grad_tk), ptr(grad_tv), opts=opts)
+            _lib.check_tensors((grad_out, torch.float32, "grad_out"))
+            _lib.call("window_attention_backward_launcher", int(offs.shape[0]) - 1, M, h, hdim, ptr(grad_out), ptr(q), ptr(k), ptr(v), ptr(attn),
+                      ptr(offs), ptr(index1), ptr(table_q), ptr(table_k), ptr(table_v), ptr(rel_idx), ptr(grad_logit), ptr(grad_q), ptr(grad_k),
+                      ptr(grad_v), ptr(grad_tq), ptr(grad_tk), ptr(grad_tv), device=dev, opts=opts)
             return grad_q, grad_k, grad_v, grad_tq, grad_tk, grad_tv, None, None, None
         # the operators' own backward launchers, in autograd's order
         grad_attn = e(M, h)
@@ -79,7 +79,7 @@ class WindowAttention(Function):
         pointops_cuda.attention_step2_with_rel_pos_value_backward_cuda_v2(N, M, h, hdim, 0, grad_out, offs, index1, attn, v, table_v, rel_idx,
                                                                           grad_attn, grad_v, grad_tv, opts=opts)
         grad_logit = e(M, h)
-        pointops_cuda._call("segment_softmax_backward_launcher", attn, int(offs.shape[0]) - 1, M, h, ptr(attn), ptr(grad_attn), ptr(offs), ptr(grad_logit))
+        _lib.call("segment_softmax_backward_launcher", int(offs.shape[0]) - 1, M, h, ptr(attn), ptr(grad_attn), ptr(offs), ptr(grad_logit), device=dev)
         # A1 and A2 receive the same gradient; grad_k is accumulated by both into one buffer
         gq1, gq2 = e(N, h, hdim), e(N, h, hdim)
         grad_k = z(NK, h, hdim)
@@ -148,7 +148,7 @@ class CellAttention(Function):
         st = q.dtype  # storage type of q / k / v / tables: fp32, or bf16 (fp32 arithmetic and outputs either way)
         if st not in (torch.float32, torch.bfloat16):
             raise TypeError("cell_attention: q / k / v / tables must all be float32 or all bfloat16, got %s" % st)
-        pointops_cuda._chk((q, st, "q"), (k, st, "k"), (v, st, "v"), (table_q, st, "table_q"), (table_k, st, "table_k"), (table_v, st, "table_v"))
+        _lib.check_tensors((q, st, "q"), (k, st, "k"), (v, st, "v"), (table_q, st, "table_q"), (table_k, st, "table_k"), (table_v, st, "table_v"))
         assert table_k.shape == table_q.shape and table_v.shape == table_q.shape
         out, ml, pbuf = _cell_forward_buffers(plan, N, h, q.device)
         _lib.call("cell_attention_forward_launcher" if st == torch.float32 else "cell_attention_forward_bf16_launcher", plan.c_arg(), h, hdim, L, ptr(q), ptr(k), ptr(v), ptr(table_q), ptr(table_k), ptr(table_v),
@@ -164,7 +164,7 @@ class CellAttention(Function):
         N, h, hdim = q.shape
         L = table_q.shape[0]
         grad_out = grad_out.contiguous()
-        pointops_cuda._chk((grad_out, torch.float32, "grad_out"))
+        _lib.check_tensors((grad_out, torch.float32, "grad_out"))
         grad_q = (torch.zeros if plan.partial else torch.empty)(q.shape, dtype=torch.float32, device=q.device)
         gsbuf, (grad_k, grad_v, gtq, gtk, gtv) = _cell_backward_buffers(plan, pbuf, k, v, table_q, table_k, table_v)
         _lib.call("cell_attention_backward_launcher" if q.dtype == torch.float32 else "cell_attention_backward_bf16_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(q), ptr(k), ptr(v), ptr(out), ptr(table_q),
@@ -195,7 +195,7 @@ class CellAttentionQKV(Function):
         if qkv.dtype not in _lib.ROW_TYPES:
             raise TypeError("cell_attention_qkv: qkv must be float32, float16 or bfloat16, got %s" % qkv.dtype)
         f32 = torch.float32
-        pointops_cuda._chk((qkv, qkv.dtype, "qkv"), (table_q, f32, "table_q"), (table_k, f32, "table_k"), (table_v, f32, "table_v"))
+        _lib.check_tensors((qkv, qkv.dtype, "qkv"), (table_q, f32, "table_q"), (table_k, f32, "table_k"), (table_v, f32, "table_v"))
         assert table_k.shape == table_q.shape and table_v.shape == table_q.shape
         out, ml, pbuf = _cell_forward_buffers(plan, N, h, qkv.device)
         _lib.call("cell_attention_qkv_forward_launcher", plan.c_arg(), h, hdim, L, ptr(qkv), _lib.ROW_TYPES[qkv.dtype], float(scale), ptr(table_q),
@@ -211,7 +211,7 @@ class CellAttentionQKV(Function):
         N, _, h, hdim = qkv.shape
         L = table_q.shape[0]
         grad_out = grad_out.contiguous()
-        pointops_cuda._chk((grad_out, torch.float32, "grad_out"))
+        _lib.check_tensors((grad_out, torch.float32, "grad_out"))
         gsbuf, (grad_qkv, gtq, gtk, gtv) = _cell_backward_buffers(plan, pbuf, qkv, table_q, table_k, table_v)
         _lib.call("cell_attention_qkv_backward_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(qkv), _lib.ROW_TYPES[qkv.dtype], ctx.scale,
                   ptr(out), ptr(table_q), ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_qkv), ptr(gtq), ptr(gtk), ptr(gtv), device=qkv.device)

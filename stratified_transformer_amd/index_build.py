@@ -296,7 +296,7 @@ def stage_partitions_hip(xyz, offset, window_size, one_sort=True, cell_max_queri
     w32 = np.float32(window_size)
     i32 = dict(dtype=torch.int32, device=dev)
     names = ("small", "small_shift", "large", "large_shift")
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev):   # one guard for the whole chain: inside it _lib.call sees dev as current and builds none
         ws_bytes = int(l.pointops2_index_workspace_bytes(N))
         bbox = torch.empty(6, dtype=torch.float32, device=dev)
         _lib.call("pointops2_bbox_launcher", N, ptr(xyz), ptr(bbox), device=dev)
@@ -380,7 +380,7 @@ def _stage_index_hip(ctx, xyz, offset, quant_size, downsample_idx, cell_table_ro
     parts, ws, ws_bytes, bbox, w32 = ctx["parts"], ctx["ws"], ctx["ws_bytes"], ctx["bbox"], ctx["w32"]
     overflow = ctx.get("overflow")
     qgl = int(swin)   # (the model's quant_grid_length, swin3d_transformer.py:109, in the caller's Python arithmetic)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev):   # one guard for the whole chain: inside it _lib.call sees dev as current and builds none
         sampled = torch.zeros(N, **i32)
         out = [None, None]   # [plain, shifted]
         pending = []

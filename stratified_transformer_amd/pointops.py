@@ -71,9 +71,8 @@ def _csc_build(index0_offsets, index1, n_keys):
     if M > 0:
         nbytes = int(_lib.lib().pointops2_csc_workspace_bytes(max(N, n_keys), M))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("pointops2_csc_build", N, M, ptr(index0_offsets), ptr(index1), ptr(offsets), ptr(pair), ptr(query),
-                      ptr(ws), nbytes, device=dev, opts=_lib.LaunchOpts(key_rows=int(n_keys)))
+        _lib.call("pointops2_csc_build", N, M, ptr(index0_offsets), ptr(index1), ptr(offsets), ptr(pair), ptr(query),
+                  ptr(ws), nbytes, device=dev, opts=_lib.LaunchOpts(key_rows=int(n_keys)))
     else:
         offsets.zero_()
     return offsets, pair, query
@@ -160,9 +159,8 @@ def csr_matches(offsets, index):
     if not index.is_cuda or index.device != offsets.device or offsets.dim() != 1 or index.dim() != 1 or offsets.shape[0] < 1:
         raise RuntimeError("csr_matches: offsets [N+1] and index [M] must be 1-d tensors on the same GPU")
     bad = torch.empty(1, dtype=torch.int32, device=offsets.device)
-    with torch.cuda.device(offsets.device):
-        _lib.call("pointops2_csr_matches_launcher", int(offsets.shape[0]) - 1, int(index.shape[0]), ptr(offsets), ptr(index),
-                  1 if index.dtype == torch.int64 else 0, ptr(bad), device=offsets.device)
+    _lib.call("pointops2_csr_matches_launcher", int(offsets.shape[0]) - 1, int(index.shape[0]), ptr(offsets), ptr(index),
+              1 if index.dtype == torch.int64 else 0, ptr(bad), device=offsets.device)
     return bad[0] == 0
 
 
@@ -719,8 +717,7 @@ class SegmentSoftmax(Function):
         M, h = src.shape
         N = offsets.shape[0] - 1
         out = torch.empty_like(src)
-        with torch.cuda.device(src.device):
-            _lib.call("segment_softmax_forward_launcher", N, M, h, ptr(src), ptr(offsets), ptr(out), device=src.device)
+        _lib.call("segment_softmax_forward_launcher", N, M, h, ptr(src), ptr(offsets), ptr(out), device=src.device)
         if valid is not None and M > 0:  # a device-side verdict (compat.scatter_softmax): poison instead of a host round trip
             out[0] = torch.where(valid, out[0], torch.full_like(out[0], float("nan")))
         ctx.save_for_backward(out, offsets)
@@ -734,8 +731,7 @@ class SegmentSoftmax(Function):
         grad_out = grad_out.contiguous()
         _lib.check_tensor(grad_out, torch.float32, "grad_out")
         grad_src = torch.empty_like(out)
-        with torch.cuda.device(out.device):
-            _lib.call("segment_softmax_backward_launcher", N, M, h, ptr(out), ptr(grad_out), ptr(offsets), ptr(grad_src), device=out.device)
+        _lib.call("segment_softmax_backward_launcher", N, M, h, ptr(out), ptr(grad_out), ptr(offsets), ptr(grad_src), device=out.device)
         return grad_src, None, None
 
 
@@ -1192,10 +1188,10 @@ def _linear_param_grads_rows(x2, g2, bias):
     grad_w = torch.empty((n_out, n_in), dtype=torch.float32, device=dev)
     grad_b = torch.empty((n_out,), dtype=torch.float32, device=dev) if bias else None
     types = _lib.ROW_TYPES
-    pointops_cuda._call("linear_grads_partial_launcher", x2, n, n_in, n_out, types[x2.dtype], types[g2.dtype], x2.data_ptr(), g2.data_ptr(),
-                        partials.data_ptr(), rows)
-    pointops_cuda._call("linear_grads_reduce_launcher", x2, n_in, n_out, int(bias), partials.data_ptr(), rows, grad_w.data_ptr(),
-                        grad_b.data_ptr() if bias else None)
+    _lib.call("linear_grads_partial_launcher", n, n_in, n_out, types[x2.dtype], types[g2.dtype], x2.data_ptr(), g2.data_ptr(),
+              partials.data_ptr(), rows, device=dev)
+    _lib.call("linear_grads_reduce_launcher", n_in, n_out, int(bias), partials.data_ptr(), rows, grad_w.data_ptr(),
+              grad_b.data_ptr() if bias else None, device=dev)
     return grad_w, grad_b
 
 

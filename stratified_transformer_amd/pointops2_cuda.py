@@ -8,8 +8,8 @@ the reference's own `lib/pointops2/functions/pointops.py` (`import pointops2_cud
 pointops.py:11) binds to it unchanged.
 
 Stricter than the reference shims (which validate nothing, e.g. attention_cuda_v2.cpp:7-16): dtype,
-device and contiguity are checked, launches go to torch's current stream under a device guard, and
-native errors are raised as RuntimeError.
+device and contiguity are checked, launches go to torch's current stream of the operands' device
+(_lib.call makes it current), and native errors are raised as RuntimeError.
 
 Every function takes a keyword-only `opts` (_lib.LaunchOpts, the launch options of this one call; the reference's
 pointops.py passes none).  The rel-pos _v2 / _v3 functions add the tables' row count L themselves.
@@ -22,17 +22,11 @@ from ._lib import ptr
 F32, I32 = torch.float32, torch.int32
 
 
-def _chk(*pairs):
-    for t, dt, name in pairs:
-        _lib.check_tensor(t, dt, name)
+_chk = _lib.check_tensors
 
 
 def _call(name, ref, *args, opts=None):
-    if ref.device.index == torch.cuda.current_device():  # the usual case: no device switch, no guard object
-        _lib.call(name, *args, device=ref.device, opts=opts)
-    else:
-        with torch.cuda.device(ref.device):
-            _lib.call(name, *args, device=ref.device, opts=opts)
+    _lib.call(name, *args, device=ref.device, opts=opts)
 
 
 # sampling/sampling_cuda.cpp
