@@ -42,7 +42,7 @@ const char *pointops2_last_error(void);
  * cell_attention_qkv_*_launcher pair).  Entry points that are only ADDED leave it: the kpconv_aggregate_*_launcher pair came in at
  * version 5, the grouped_max_*_launcher pair, the five pointops2_dbscan_*_launcher, the pointops2_evaltile_* entry points, the two
  * pointops2_contacts_*_launcher, pointops2_label_boxes_launcher / pointops2_reach_rows_launcher and the three
- * pointops2_supports_*_launcher, the two pointops2_augment_*_launcher optim_adamw_step_launcher and optim_step_launcher after them - a caller that needs them looks the symbols up. */
+ * pointops2_supports_*_launcher, the two pointops2_augment_*_launcher optim_adamw_step_launcher, optim_step_launcher and the gather_add_*_launcher pair after them - a caller that needs them looks the symbols up. */
 int pointops2_abi_version(void);
 /* Diagnostic: how long (ticks of the 100 MHz clock, default 2 s) a workgroup of the round sampler waits at its grid barrier before
  * the sampler gives up and pointops2_last_error() reports the call's indices invalid (tests force the path with a tiny value). */
@@ -449,6 +449,31 @@ void grouped_max_forward_launcher(int m, int n_s, int k, int c, int row_type, co
                                   unsigned char *arg);
 void grouped_max_backward_launcher(int m, int n_s, int k, int c, int row_type, const void *grad_out, const unsigned char *arg,
                                    const int *src_offsets, const int *src_pair, void *grad_feat);
+
+/* ---- gather-add: the decoder's Upsample behind its kNN search (model/stratified_transformer.py:341): the weighted sum of k source rows
+ * (lib/pointops2/functions/pointops.py:767-769) and the add of the support row, in one pass (csrc/upsample.hip) ----
+ *   forward:  t = 0; for i = 0 .. k-1: t = t + (float(feat[idx[n,i], ch]) * weight[n,i]);  out[n,ch] = float(base[n,ch]) + t (base
+ *             NULL: out = t).  Each product is rounded, then each add; nothing is contracted to an FMA: the reference's loop and its
+ *             `+`, operation for operation.  An idx entry outside [0, m) is skipped and never read.  out [n,c] fp32 is FULLY WRITTEN:
+ *             no zero-fill.
+ *   backward: grad_feat[j,ch] = sum over the pairs (n,i) with idx[n,i] == j of (grad_out[n,ch] * weight[n,i]), gathered by source row
+ *             through the key-major view of idx: src_offsets [m+1] / src_pair [n*k] are what pointops2_csc_build yields for the CSR
+ *             offsets = {0, k, 2k, ...}, index1 = idx with launch_opts.key_rows = m (pair id = n * k + i, ascending per source row;
+ *             idx entries outside [0, m) must be kept out of that build - key them to an extra row m).  fp32 accumulation from 0 in
+ *             pair order, each product rounded before its add, one rounding to feat's row type; grad_feat [m,c] (feat_type) is FULLY
+ *             WRITTEN, a source row nobody references gets exact zeros: no float atomics, no zero-fill, bitwise reproducible.
+ *             Offsets and pair ids are clamped / skipped, never followed outside the arrays.  base's gradient is grad_out itself.
+ * feat [m,c]: feat_type, base [n,c]: base_type, each POINTOPS2_ROWS_F32, _F16 or _BF16 independently of the other (the two Linears
+ * in front yield half under autocast), widened exactly; base_type is not read when base is NULL.  idx [n,k] int32; weight [n,k],
+ * out and grad_out [n,c] fp32.  1 <= k <= 64, 1 <= c <= 1024 and n * k < 2^31, otherwise an error is recorded and nothing is
+ * launched.  n = 0 is a no-op of the forward, m = 0 of the backward; with m = 0 the forward writes base (or zeros), with n = 0 the
+ * backward writes zeros.  Rows of whole 16-byte chunks of feat (c % 4 == 0 for fp32, c % 8 == 0 for the halves) on aligned operands
+ * (feat, out, grad_out, grad_feat and an fp32 base to 16 bytes, a half base to 8) take the chunked kernels, anything else one thread
+ * per element: same bits. */
+void gather_add_forward_launcher(int n, int m, int k, int c, int feat_type, int base_type, const void *feat, const int *idx,
+                                 const float *weight, const void *base, float *out);
+void gather_add_backward_launcher(int n, int m, int k, int c, int feat_type, const float *grad_out, const float *weight,
+                                  const int *src_offsets, const int *src_pair, void *grad_feat);
 
 /* ---- residual add + DropPath row scale + LayerNorm in one pass over the rows: the glue of a pre-norm block
  * (model/stratified_transformer.py:245-246 and the next block's :241; model/swin3d_transformer.py:206-210) ----

@@ -23,7 +23,7 @@ model/stratified_transformer.py imports and runs unmodified under PyTorch-ROCm.
 import sys
 
 __all__ = ["install", "build", "dbscan", "instances", "contacts", "objects", "label_boxes", "merge_objects", "box_detection", "scene_eval",
-           "clean_supports", "box_supports", "scene_predict", "dense_points", "detect_boxes", "detect_scene", "install_fused_blocks", "segmentation_loss",
+           "clean_supports", "box_supports", "scene_predict", "dense_points", "detect_boxes", "detect_scene", "install_fused_blocks", "install_fast_decoder", "segmentation_loss",
            "fuse_batch_norms", "unfuse_batch_norms", "fuse_sync_batch_norms", "fuse_linear_grads", "unfuse_linear_grads"]
 
 
@@ -40,6 +40,9 @@ def __getattr__(name):
     if name == "install_fused_blocks":  # layers.install_fused_blocks: the blocks' residual / DropPath / LayerNorm glue on csrc/rownorm.hip
         from . import layers
         return layers.install_fused_blocks
+    if name == "install_fast_decoder":  # layers.install_fast_decoder: Upsample's interpolation and add on csrc/upsample.hip
+        from . import layers
+        return layers.install_fast_decoder
     if name in ("fuse_batch_norms", "unfuse_batch_norms", "fuse_sync_batch_norms"):  # layers.*: BatchNorm1d / SyncBatchNorm + activation (+ residual) of the stem and the heads on csrc/batchnorm.hip
         from . import layers
         return getattr(layers, name)

@@ -134,6 +134,8 @@ SIGNATURES = {
     "residual_norm_stream_backward_launcher": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, P],
     "linear_grads_partial_launcher": [I, I, I, I, I, P, P, P, I],
     "linear_grads_reduce_launcher": [I, I, I, P, I, P, P],
+    "gather_add_forward_launcher": [I, I, I, I, I, I, P, P, P, P, P],
+    "gather_add_backward_launcher": [I, I, I, I, I, P, P, P, P, P],
 }
 # entry points with a non-void result
 RESULTS = {
@@ -158,7 +160,7 @@ OPTIM_KINDS = {"adamw": 0, "sgd": 1}
 
 # codes of pointops2_cell_forward_variant (POINTOPS2_CELL_FWD_* of include/pointops2_hip.h): the forward kernel a cell launch runs
 CELL_FWD = {"error": -1, "none": 0, "mfma64": 1, "mfma80": 2, "valu80": 3, "valu160": 4}
-# storage type of the rows of a packed qkv (POINTOPS2_ROWS_*): cell_attention_qkv_*_launcher, grouped_max_*_launcher
+# storage type of the rows of a packed qkv (POINTOPS2_ROWS_*): cell_attention_qkv_*_launcher, grouped_max_*_launcher, gather_add_*_launcher
 ROW_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 # rows of a chunk of linear_grads_partial_launcher (POINTOPS2_LINEAR_GRADS_ROWS): its partials have ceil(n / LINEAR_GRADS_ROWS) blocks
 LINEAR_GRADS_ROWS = 512

@@ -19,58 +19,19 @@
 //             does, per query and channel).  fp32 accumulation in pair order, one rounding to the row type, every row of grad_feat
 //             written: no atomics, no zero-fill, the same bits from run to run.
 // Channel counts that are no multiple of the chunk (or operands that are not 16-byte aligned) take one thread per element.
-#include "row_types.h"
+#include "gather_rows.h"
 
 namespace p2 {
 namespace {
 
 constexpr int GM_MAX_K = 64, GM_MAX_C = 1024;
-constexpr int GM_WAVES = 4;   // per workgroup
+constexpr int GM_WAVES = GATHER_WAVES;
 constexpr int FWD_NB = 16;    // neighbours in flight per lane (the model's k: one batch)
 constexpr int BWD_NB = 4;     // pairs in flight per lane (m * k / n_s = 4 at ratio 0.25, k = 16)
 constexpr int NO_ARG = 255;
 
-// one 16-byte chunk of a row of storage type RT (row_types.h): VEC elements, widened exactly, compared / summed in fp32
-template <typename RT> struct Chunk {
-    static constexpr int VEC = 16 / (int)sizeof(RT);
-    uint4 bits;
-    __device__ __forceinline__ float get(int e) const {
-        const unsigned w[4] = {bits.x, bits.y, bits.z, bits.w};
-        if constexpr (sizeof(RT) == 4) return __uint_as_float(w[e]);
-        else return widen_bits<RT>((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu));
-    }
-    static __device__ __forceinline__ uint4 pack(const float *v) {
-        unsigned w[4];
-        if constexpr (sizeof(RT) == 4) {
-#pragma unroll
-            for (int e = 0; e < 4; e++) w[e] = __float_as_uint(v[e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) w[e] = narrow_bits<RT>(v[2 * e]) | (narrow_bits<RT>(v[2 * e + 1]) << 16);
-        }
-        return make_uint4(w[0], w[1], w[2], w[3]);
-    }
-};
-__device__ __forceinline__ uint4 ld16(const void *base, size_t byte_offset) {
-    return *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(base) + byte_offset);
-}
-__device__ __forceinline__ void st16(void *base, size_t byte_offset, uint4 v) {
-    *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(base) + byte_offset) = v;
-}
-
 // MaxPool1d's update: the first entry, a larger value, or the first NaN
 __device__ __forceinline__ bool takes(float x, float best, int arg) { return arg == NO_ARG || x > best || (x != x && best == best); }
-
-// rows of a wave: `chunks` < 64 -> 64 / chunks rows side by side, lane = (row, chunk); else one row, the lanes stride over its chunks
-struct RowLanes {
-    int sub, chunk0, per_wave;
-    __device__ __forceinline__ RowLanes(int chunks) {
-        const int lane = lane_id();
-        per_wave = chunks < WAVE ? WAVE / chunks : 1;
-        sub = chunks < WAVE ? lane / chunks : 0;
-        chunk0 = lane - sub * chunks;
-    }
-};
 
 template <typename RT>
 __global__ __launch_bounds__(GM_WAVES * WAVE) void grouped_max_fwd_kernel(int m, int n_s, int k, int c, int chunks, const void *__restrict__ feat,
@@ -147,12 +108,6 @@ __global__ __launch_bounds__(256) void grouped_max_fwd_scalar_kernel(int m, int 
         st_elem(&reinterpret_cast<RT *>(out)[t], best);  // (exact: best is an element of feat, or 0)
         if (arg != nullptr) arg[t] = (unsigned char)a;
     }
-}
-
-// the pairs [p0, p1) of source row j, clamped into the pair list whatever the offsets hold
-__device__ __forceinline__ void pair_range(const int *__restrict__ src_offsets, long long j, int n_pairs, int &p0, int &p1) {
-    p0 = min(max(src_offsets[j], 0), n_pairs);
-    p1 = min(max(src_offsets[j + 1], p0), n_pairs);
 }
 
 template <typename RT>
@@ -247,20 +202,10 @@ const char *grouped_max_bad_args(int m, int n_s, int k, int c, int row_type) {
     if ((long long)m * k > 0x7fffffffLL) return "grouped_max: m * k does not fit the int32 pair ids";
     return nullptr;
 }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // 16-byte chunks per row when the chunked kernels apply (whole chunks, aligned operands), else 0
 inline int row_chunks(int c, int vec, const void *a, const void *b, const unsigned char *arg) {
     if (c % vec != 0 || !aligned16(a) || !aligned16(b) || (reinterpret_cast<uintptr_t>(arg) & 3u) != 0) return 0;
     return c / vec;
-}
-inline int chunked_grid(int rows, int chunks) {
-    const int per_wave = chunks < WAVE ? WAVE / chunks : 1;
-    const int want = div_up(div_up(rows, per_wave), GM_WAVES), cap = num_cus() * 64;
-    return want < cap ? want : cap;
-}
-inline int scalar_grid(long long total) {
-    const long long want = div_up64(total, 256), cap = (long long)num_cus() * 64;
-    return (int)(want < cap ? want : cap);
 }
 
 template <typename RT>

@@ -7,7 +7,7 @@
 `install_fast_layers()` (or `stratified_transformer_amd.install(fast_layers=True)`) rebinds these methods on the classes of
 the UNMODIFIED model file; the modules' own parameters are used as they are (`qkv`, `proj`, the three rel-pos tables, `norm1`,
 `mlp`, `downsample`, ...), so checkpoints, optimizers and the rest of the model (`SwinTransformerBlock.forward`, `TransitionDown`,
-`Upsample`, stem, classifier) are untouched.  What changes is WHERE the index work and the attention run:
+`Upsample`, stem, classifier) are untouched unless their own installer below is called.  What changes is WHERE the index work and the attention run:
 
   * BasicLayer.forward builds the stage's index ONCE (the reference rebuilds the pair list for every block, :302-317, although
     only two patterns exist per stage): FPS through the operator API (bit-exact, resumed later by TransitionDown's call), then
@@ -48,6 +48,10 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
   * The parameter gradients of the nn.Linear layers (off by default): `fuse_linear_grads(model)` binds, per instance, a forward that is
     F.linear with grad_weight / grad_bias from pointops.linear_param_grads (csrc/linear_grads.hip) where linear_grads_worth_it admits
     the shape at that call, and F.linear untouched everywhere else.
+
+  * The decoder (off by default): `install_fast_decoder()` / `patch_upsample_class()` rebind Upsample.forward (:339-342) to upsample_forward -
+    the interpolation of linear2(feats) and the add of linear1(support_feats) as one pointops.interpolate_add (csrc/upsample.hip) on the
+    rows as the Linears left them, with an atomic-free backward; the kNN search stays pointops.knnquery.
 
 Numbers: the same sums in another order (tests/test_hip_parity.py::test_installed_fast_layers_against_the_reference_layer:
 output and every parameter gradient of a depth-2 BasicLayer with TransitionDown against the reference's own run, <= 1e-3).
@@ -513,6 +517,39 @@ def transition_down_forward(self, feats, xyz, offset):
     return pooled.squeeze(-1), t["n_xyz"], t["n_offset"]
 
 
+def _norm_linear(seq, rows):
+    """seq(rows) for one of Upsample's `Sequential(LayerNorm, Linear)`: the LayerNorm as one pointops.residual_norm pass (no residual
+    operand) that writes the dtype the Linear wants, where _norm_ok and the dtype rules of _fused_block admit the rows; the two
+    modules as torch runs them everywhere else"""
+    if not (isinstance(seq, torch.nn.Sequential) and len(seq) == 2 and type(seq[1]) is torch.nn.Linear and rows.dim() == 2
+            and 1 <= rows.shape[1] <= 1024 and _norm_ok(seq[0], rows.shape[1])):
+        return seq(rows)
+    half = rows.dtype in (torch.float16, torch.bfloat16)
+    odt = _glue_dtype(rows.device)
+    if odt is None or not (rows.dtype == torch.float32 or (half and HALF_STREAM)) or (half and odt != rows.dtype):
+        return seq(rows)
+    residual_norm = P.residual_norm_stream if half else P.residual_norm
+    _, normed = residual_norm(rows.contiguous(), None, None, seq[0].weight, seq[0].bias, seq[0].eps, odt)
+    return seq[1](normed)
+
+
+def upsample_forward(self, feats, xyz, support_xyz, offset, support_offset, support_feats=None):
+    """Replacement of Upsample.forward (model/stratified_transformer.py:339-342), same arguments, same three results: the interpolation
+    of linear2(feats) onto the support points and the add of linear1(support_feats) as ONE pointops.interpolate_add (csrc/upsample.hip)
+    that reads both halves where the Linears left them - under autocast no fp32 copy of the half rows, no zero-filled result, no
+    separate add - and an atomic-free backward.  Both LayerNorms run on pointops.residual_norm where _norm_linear admits the rows.
+    The kNN search and the weights are `pointops.interpolation`'s own.  The original forward runs for CPU tensors, for
+    `support_feats is None` and for rows that are not [N, C] f32 / f16 / bf16."""
+    rows = (feats, support_feats)
+    if support_feats is None or not all(torch.is_tensor(t) and t.is_cuda and t.dim() == 2 and t.dtype in _ROW_DTYPES for t in rows) \
+            or not (xyz.is_cuda and support_xyz.is_cuda and 1 <= int(self.out_channels) <= 1024):
+        return _original(self)(self, feats, xyz, support_xyz, offset, support_offset, support_feats)
+    a = _norm_linear(self.linear1, support_feats)                                                                                  # :341
+    b = _norm_linear(self.linear2, feats)
+    out = P.interpolate_add(xyz, support_xyz, b, offset, support_offset, base=a)
+    return out, support_xyz, support_offset
+
+
 def swin_window_attention_forward(self, feats, xyz, index_0, index_0_offsets, n_max, index_1, shift_size):
     """Replacement of the Swin3D WindowAttention.forward (model/swin3d_transformer.py:132-178), same arguments, same result: on the
     cell plan swin_basic_layer_forward handed over, else on the pair list it was given (rel-pos index :151-154 by torch, clamped)."""
@@ -629,6 +666,27 @@ def install_fused_blocks(module=None):
         blk = getattr(m, "SwinTransformerBlock", None)
         swin = getattr(m, "__name__", "").endswith("swin3d_transformer")
         done += patch_block_classes(None if swin else blk, blk if swin else None)
+    return done
+
+
+def patch_upsample_class(cls=None):
+    """Rebinds `forward` of an Upsample class (any class with the reference's attribute names: linear1, linear2, out_channels) to
+    upsample_forward; returns what was patched.  uninstall_fast_layers() restores it."""
+    return _patch(((cls, upsample_forward),))
+
+
+def install_fast_decoder(module=None):
+    """Patches Upsample of the reference's model module(s): the imported module (or a list).  Default: the modules install_fused_blocks
+    takes.  Off by default and independent of install_fast_layers / install_fused_blocks, which patch what they patched before."""
+    import importlib
+    if module is None:
+        mods = [importlib.import_module("model.stratified_transformer")]
+        mods += [sys.modules[m] for m in ("model.stratified_transformer_backup", "model.swin3d_transformer") if m in sys.modules]
+    else:
+        mods = list(module) if isinstance(module, (list, tuple)) else [module]
+    done = []
+    for m in mods:
+        done += patch_upsample_class(getattr(m, "Upsample", None))
     return done
 
 

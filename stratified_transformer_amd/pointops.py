@@ -1009,6 +1009,101 @@ def grouped_max(feat, idx):
 
 
 # ---------------------------------------------------------------------------------------------
+# gather-add: Upsample's weighted sum of k gathered rows and its add (model/stratified_transformer.py:341) on typed rows
+# ---------------------------------------------------------------------------------------------
+GATHER_ADD_VIEWS = 0  # key-major views built so far (tests: none without a gradient of feat)
+
+
+class GatherAdd(Function):
+    """out = base + sum_i weight[:, i] * feat[idx[:, i]] in fp32 (csrc/upsample.hip).  The backward gathers by source row through the
+    key-major view of idx, which the FORWARD builds (the indices are known there; the sort is off the backward's chain): no atomics,
+    bitwise reproducible.  base's gradient is the incoming one; weight gets none."""
+
+    @staticmethod
+    def forward(ctx, feat, idx, weight, base, need):
+        (n, k), (m, c) = idx.shape, feat.shape
+        out = torch.empty((n, c), dtype=torch.float32, device=feat.device)
+        if n > 0:
+            pointops_cuda.gather_add_forward(n, m, k, c, feat, idx, weight, base, out)
+        ctx.feat_dtype, ctx.shape = feat.dtype, (n, m, k, c)
+        if need:
+            # pointops2_csc_build follows every key, so the entries the forward skipped are keyed to an extra row m, behind the m + 1
+            # offsets the kernel reads
+            global GATHER_ADD_VIEWS
+            GATHER_ADD_VIEWS += 1
+            keys = torch.where((idx >= 0) & (idx < m), idx, torch.full_like(idx, m)).view(-1)
+            rows = torch.arange(0, n * k + 1, k, dtype=torch.int32, device=idx.device)
+            src_offsets, src_pair, _ = _csc_build(rows, keys, m + 1)
+            ctx.save_for_backward(weight, src_offsets, src_pair)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        n, m, k, c = ctx.shape
+        grad_feat = None
+        if ctx.needs_input_grad[0]:
+            weight, src_offsets, src_pair = ctx.saved_tensors
+            grad_feat = torch.empty((m, c), dtype=ctx.feat_dtype, device=grad_out.device)
+            if m > 0:
+                pointops_cuda.gather_add_backward(n, m, k, c, grad_out.contiguous(), weight, src_offsets[:m + 1], src_pair, grad_feat)
+        return grad_feat, None, None, grad_out if ctx.needs_input_grad[3] else None, None
+
+
+def gather_add(feat, idx, weight, base=None):
+    """out[n, :] = base[n, :] + sum_i weight[n, i] * feat[idx[n, i], :] -> [n, c] fp32, one HIP pass (csrc/upsample.hip): the sum in the
+    order i = 0 .. k-1 from zero, every product and every add rounded in fp32 (the reference's loop pointops.py:767-769 and the `+` of
+    Upsample, model/stratified_transformer.py:341, operation for operation).  feat [m, c] and base [n, c] (or None: the sum alone) are
+    f32, f16 or bf16 rows, each of its own dtype, read where a Linear left them and widened exactly; idx [n, k] int32 / int64; weight
+    [n, k] f32.  Entries of idx outside [0, m) are skipped.  Differentiable w.r.t. feat (gathered by source row, fp32 sums in pair
+    order, one rounding to feat's dtype; no float atomics, bitwise reproducible) and base (the incoming gradient; autograd casts it to
+    base's dtype).  weight gets NO gradient: where the coordinates need one, interpolation_v2 is the path.  1 <= k <= 64,
+    1 <= c <= 1024, n * k < 2^31."""
+    tensors = [("feat", feat), ("idx", idx), ("weight", weight), ("base", base)]
+    for name, t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"gather_add: {name}: expected a GPU tensor (the pointops2 HIP path has no CPU fallback), got {t.device}")
+    for name, t in tensors[1:]:
+        if t is not None and t.device != feat.device:
+            raise RuntimeError(f"gather_add: {name} is on {t.device}, feat on {feat.device}")
+    if feat.dim() != 2:
+        raise ValueError(f"gather_add: feat must be [m, c], got {tuple(feat.shape)}")
+    if feat.dtype not in _ROW_DTYPES:
+        raise TypeError(f"gather_add: feat must be f32, f16 or bf16, got {feat.dtype}")
+    if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 2:
+        raise ValueError(f"gather_add: idx must be an int32 / int64 [n, k], got {idx.dtype} {tuple(idx.shape)}")
+    (n, k), (m, c) = idx.shape, feat.shape
+    if not 1 <= k <= 64:
+        raise ValueError(f"gather_add: k must be in [1, 64], got idx {tuple(idx.shape)}")
+    if not 1 <= c <= 1024:
+        raise ValueError(f"gather_add: c must be in [1, 1024], got feat {tuple(feat.shape)}")
+    if n * k >= 2 ** 31:
+        raise ValueError(f"gather_add: n * k must be below 2^31, got idx {tuple(idx.shape)}")
+    if weight.dtype != torch.float32:
+        raise TypeError(f"gather_add: weight must be f32, got {weight.dtype}")
+    if tuple(weight.shape) != (n, k):
+        raise ValueError(f"gather_add: weight must be [{n}, {k}] like idx, got {tuple(weight.shape)}")
+    if base is not None:
+        if base.dtype not in _ROW_DTYPES:
+            raise TypeError(f"gather_add: base must be f32, f16 or bf16, got {base.dtype}")
+        if tuple(base.shape) != (n, c):
+            raise ValueError(f"gather_add: base must be [{n}, {c}], got {tuple(base.shape)}")
+        base = base.contiguous()
+    if idx.dtype == torch.int64:
+        idx = idx.clamp(-1, m).to(torch.int32)
+    need = bool(feat.requires_grad) and torch.is_grad_enabled()  # (needs_input_grad is set under no_grad too)
+    return GatherAdd.apply(feat.contiguous(), idx.contiguous(), weight.detach().contiguous(), base, need)
+
+
+def interpolate_add(xyz, new_xyz, feat, offset, new_offset, base=None, k=3):
+    """base + interpolation(xyz, new_xyz, feat, offset, new_offset, k) -> [n, c] fp32 without the fp32 copy of a half feat, the zero-filled
+    result and the separate add: knnquery and the inverse-distance weights exactly as `interpolation` takes them (the same bits), then
+    gather_add.  Differentiable w.r.t. feat and base."""
+    assert xyz.is_contiguous() and new_xyz.is_contiguous()
+    idx, dist = knnquery(k, xyz, new_xyz, offset, new_offset)
+    return gather_add(feat, idx, _inverse_distance_weights(dist), base)
+
+
+# ---------------------------------------------------------------------------------------------
 # residual add + DropPath row scale + LayerNorm: the glue between the GEMMs of a pre-norm block (csrc/rownorm.hip)
 # ---------------------------------------------------------------------------------------------
 def _residual_norm_forward(kernel, ctx, x, y, row_scale, weight, bias, eps, out_dtype):

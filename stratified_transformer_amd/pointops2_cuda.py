@@ -119,6 +119,37 @@ def grouped_max_backward(m, n_s, k, c, grad_out, arg, src_offsets, src_pair, gra
           opts=opts)
 
 
+# csrc/upsample.hip (no counterpart in the reference's launcher set: Upsample's weighted sum of k gathered rows and its add, typed rows)
+def gather_add_forward(n, m, k, c, feat, idx, weight, base, out, *, opts=None):
+    """out [n,c] f32 (fully written) <- feat [m,c] f32 / f16 / bf16, idx [n,k] int32, weight [n,k] f32, base [n,c] f32 / f16 / bf16 or None"""
+    n, m, k, c = int(n), int(m), int(k), int(c)
+    rt = _row_type(feat, "feat")
+    _chk((feat, feat.dtype, "feat"), (idx, I32, "idx"), (weight, F32, "weight"), (out, F32, "out"))
+    _shaped(feat, (m, c), "feat"), _shaped(idx, (n, k), "idx"), _shaped(weight, (n, k), "weight"), _shaped(out, (n, c), "out")
+    bt = 0
+    if base is not None:
+        bt = _row_type(base, "base")
+        _chk((base, base.dtype, "base"))
+        _shaped(base, (n, c), "base")
+    _call("gather_add_forward_launcher", feat, n, m, k, c, rt, bt, ptr(feat), ptr(idx), ptr(weight), ptr(base), ptr(out), opts=opts)
+
+
+def gather_add_backward(n, m, k, c, grad_out, weight, src_offsets, src_pair, grad_feat, *, opts=None):
+    """grad_feat [m,c] f32 / f16 / bf16 (fully written) <- grad_out [n,c] f32, weight [n,k] f32, the key-major view of idx:
+    src_offsets (m + 1 entries), src_pair (n * k entries), int32"""
+    n, m, k, c = int(n), int(m), int(k), int(c)
+    rt = _row_type(grad_feat, "grad_feat")
+    _chk((grad_out, F32, "grad_out"), (weight, F32, "weight"), (src_offsets, I32, "src_offsets"), (src_pair, I32, "src_pair"),
+         (grad_feat, grad_feat.dtype, "grad_feat"))
+    _shaped(grad_out, (n, c), "grad_out"), _shaped(weight, (n, k), "weight"), _shaped(grad_feat, (m, c), "grad_feat")
+    if src_offsets.numel() != m + 1:
+        raise ValueError(f"src_offsets: expected {m + 1} entries, got {src_offsets.numel()}")
+    if src_pair.numel() != n * k:
+        raise ValueError(f"src_pair: expected {n * k} entries, got {src_pair.numel()}")
+    _call("gather_add_backward_launcher", grad_out, n, m, k, c, rt, ptr(grad_out), ptr(weight), ptr(src_offsets), ptr(src_pair), ptr(grad_feat),
+          opts=opts)
+
+
 # csrc/rownorm.hip (no counterpart in the reference's launcher set: residual add, DropPath row scale and LayerNorm of a pre-norm block)
 RESIDUAL_NORM_MAX_C = 1024
 RESIDUAL_NORM_PARTIAL_ROWS = 1024  # most workgroups of the backward: one row of `partials` each

@@ -6,7 +6,7 @@ The four loops - which one a tool uses is part of what its numbers mean, so they
 
     windows       device events around a window of `inner` calls, the second event synchronised, no synchronise in front; the sides
                   alternate window by window.  `prepare` runs ahead of a window's first event (gradients cleared outside the timed region).
-                  bench_block, bench_norm, bench_loss, bench_syncbn; bench_kpconv, bench_transition, bench_swin (inner 1, with prepare);
+                  bench_block, bench_norm, bench_loss, bench_syncbn; bench_kpconv, bench_transition, bench_swin, bench_upsample (inner 1, with prepare);
                   bench_ops, bench_stages (one_window_us: one window of one side)
     calls         one call at a time: synchronise, host clock, event, the call, event, synchronise; the callables alternate.  Device and
                   host ms per call.  bench_augment, bench_detect's vote, knn_only; as device_ms (medians of one callable) bench_contacts,
