@@ -1,6 +1,7 @@
 // The loss tail of a segmentation training step in one pass over the logits (tool/train.py:336-362: CrossEntropyLoss(ignore_index) on the
 // [N, C] class logits, L1Loss on the [N, 3] shift head, their weighted sum; train_backup.py:403: intersectionAndUnionGPU of the argmax),
-// and its backward in one pass.  All arithmetic in fp32 on exactly widened operands, nothing fused (-ffp-contract=off, no fmaf here):
+// and its backward in one pass.  All arithmetic in fp32 on exactly widened operands, nothing fused (-ffp-contract=off, no fmaf here); the
+// forward's |shift_pred - shift| alone is taken in double, as the sum it goes into, so that l1 is the float64 value rounded once:
 //
 //   forward   m_n = max_c x[n,c]     ls_n = log(sum_c exp(x[n,c] - m_n))     stat[n] = (m_n, ls_n)     (lse_n = m_n + ls_n)
 //             logp[n,c] = (x[n,c] - m_n) - ls_n        row n is VALID when 0 <= target[n] < C and target[n] != ignore_index
@@ -149,7 +150,9 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_fwd_kernel(int n, int c, 
         }
         if (shift_pred != nullptr) {
             const size_t s0 = (size_t)row0 * 3;
-            for (int le = tid; le < tr * 3; le += SL_THREADS) l1 += (double)fabsf(load_elem(shift_pred, s0 + le, s_type) - shift[s0 + le]);
+            // the difference in double, where the sum is kept: an fp32 difference rounds each term, and a few rows' l1 then ends a whole
+            // fp32 step off the float64 value (seen at n = 1: 5.96e-08 on 0.7995); so the one rounding is the finish kernel's
+            for (int le = tid; le < tr * 3; le += SL_THREADS) l1 += fabs((double)load_elem(shift_pred, s0 + le, s_type) - (double)shift[s0 + le]);
         }
         __syncthreads();  // the tile and, after the last one, the histogram
     }
