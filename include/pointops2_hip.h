@@ -414,6 +414,48 @@ void cell_attention_qkv_backward_launcher(const pointops2_cell_plan *plan, int h
                                           const float *pbuf, float *gsbuf, float *grad_qkv, float *grad_table_q, float *grad_table_k,
                                           float *grad_table_v);
 
+/* ---- deterministic backward of the cell attention: no float atomics, the same bits from run to run ----
+ * The three backward launchers above add dK, dV and the table gradients across workgroups with float atomics, in the order the
+ * workgroups arrive.  The three below take the same arguments, compute the same sums and fix their order: a store pass, then a sum
+ * pass per destination, as separate launches (no tickets or flags between workgroups).
+ *   1  the sweeps store a chunk's key-side rows to key_partials [2, K, h, 16] fp32 (K = plan->n_keyslots; plane 0: dK, plane 1: dV) at
+ *      slot cell_kbase[cell] + (position of the key in the cell's list): every slot of every cell is written exactly once
+ *   2  the table bodies run on a grid of R = pointops2_cell_table_partial_rows(plan, h) workgroups per body and head; each stores its
+ *      whole image of L * 48 sums, zeros included, to table_partials [3 = q, k, v][R][h][L * 48] fp32
+ *   3  cell_key_grads_reduce_launcher:   grad[i, :] = ((0 + partials[order[a]]) + partials[order[a + 1]]) + ... over
+ *      a .. b - 1 = slot_offsets[i] .. slot_offsets[i + 1] - 1 IN THAT ORDER, fp32; a point without a slot gets 0.  grad: n rows of h * 16
+ *      floats, row_stride floats apart (h * 16, or 3 * h * 16 for the k / v third of a packed [N, 3, h, 16] gradient: pass the third's
+ *      first row); partials [K, h, 16]; every row of grad is written
+ *   4  cell_table_grads_reduce_launcher: grad_table[x] = ((0 + p[0][x]) + p[1][x]) + ... over the partial_rows images IN ASCENDING
+ *      ORDER, fp32, for the three tables [L, h, 16, 3] in one launch; every element is written
+ * slot_offsets [N + 1], slot_order [K]: the key-major view of plan->cell_keys - per point its key slots, ascending (pointops2_csc_build
+ * on index0_offsets = 0 .. K, index1 = cell_keys).  grad_q as in the launchers above; grad_k, grad_v (the k and v thirds of grad_qkv)
+ * and the table gradients are fully WRITTEN, not accumulated: no zero-fill, and none of the partial buffers (sizes in floats; the
+ * composites check them).  Errors, nothing enqueued: those of the launchers above; a plan that is a share of the cells (task_step > 1
+ * or a task_list: the ranks' sums would meet in an all-reduce of no fixed order); a NULL operand; a partial buffer that is too small.
+ * Reproducible for one build of the library on one device model: R follows the device's CU count (not the CUs free at the moment of
+ * the launch, as the grids of the launchers above), so another device groups the table sums differently. */
+int pointops2_cell_table_partial_rows(const pointops2_cell_plan *plan, int h);
+void cell_key_grads_reduce_launcher(int n, int h, const int *slot_offsets, const int *slot_order, const float *partials, float *grad, int row_stride);
+void cell_table_grads_reduce_launcher(int partial_rows, int h, int L, const float *table_partials, float *grad_table_q, float *grad_table_k,
+                                      float *grad_table_v);
+void cell_attention_det_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const float *q, const float *k,
+                                          const float *v, const float *out, const float *table_q, const float *table_k, const float *table_v,
+                                          const float *pbuf, float *gsbuf, float *grad_q, float *grad_k, float *grad_v, float *grad_table_q,
+                                          float *grad_table_k, float *grad_table_v, const int *slot_offsets, const int *slot_order, float *key_partials,
+                                          size_t key_partial_floats, float *table_partials, size_t table_partial_floats);
+void cell_attention_det_backward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const uint16_t *q,
+                                               const uint16_t *k, const uint16_t *v, const float *out, const uint16_t *table_q, const uint16_t *table_k,
+                                               const uint16_t *table_v, const float *pbuf, float *gsbuf, float *grad_q, float *grad_k, float *grad_v,
+                                               float *grad_table_q, float *grad_table_k, float *grad_table_v, const int *slot_offsets,
+                                               const int *slot_order, float *key_partials, size_t key_partial_floats, float *table_partials,
+                                               size_t table_partial_floats);
+void cell_attention_qkv_det_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const void *qkv, int row_type,
+                                              float scale, const float *out, const float *table_q, const float *table_k, const float *table_v,
+                                              const float *pbuf, float *gsbuf, float *grad_qkv, float *grad_table_q, float *grad_table_k,
+                                              float *grad_table_v, const int *slot_offsets, const int *slot_order, float *key_partials,
+                                              size_t key_partial_floats, float *table_partials, size_t table_partial_floats);
+
 /* ---- KPConv stem (model/stratified_transformer.py:344-392: KPConvLayer of torch_points3d 1.3.0, rigid kernel points, linear
  * influence, sum aggregation; third party, not under the reference: PARITY UNPINNED) ----
  * With j = neighbors[i, n] (a j outside [0, n_s) - the -1 padding of a ball query, or n_s, the original's shadow point - is skipped):

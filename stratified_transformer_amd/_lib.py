@@ -96,6 +96,11 @@ SIGNATURES = {
     "cell_attention_backward_bf16_launcher": [P, I, I, I] + [P] * 16,
     "cell_attention_qkv_forward_launcher": [P, I, I, I, P, I, F] + [P] * 6,
     "cell_attention_qkv_backward_launcher": [P, I, I, I, P, P, I, F] + [P] * 10,
+    "cell_key_grads_reduce_launcher": [I, I, P, P, P, P, I],
+    "cell_table_grads_reduce_launcher": [I, I, I, P, P, P, P],
+    "cell_attention_det_backward_launcher": [P, I, I, I] + [P] * 16 + [P, P, P, Z, P, Z],
+    "cell_attention_det_backward_bf16_launcher": [P, I, I, I] + [P] * 16 + [P, P, P, Z, P, Z],
+    "cell_attention_qkv_det_backward_launcher": [P, I, I, I, P, P, I, F] + [P] * 10 + [P, P, P, Z, P, Z],
     "kpconv_aggregate_forward_launcher": [I, I, I, I, I, P, P, P, P, P, F, P],
     "kpconv_aggregate_backward_launcher": [I, I, I, I, I, P, P, P, P, F, P, P],
     "grouped_max_forward_launcher": [I, I, I, I, I, P, P, P, P],
@@ -154,6 +159,7 @@ RESULTS = {
     "pointops2_optim_workspace_bytes": ([I, I], Z),
     "pointops2_optim_step_workspace_bytes": ([I, I, Q], Z),
     "pointops2_linear_grads_partial_rows": ([I, I, I], I),
+    "pointops2_cell_table_partial_rows": ([P, I], I),
 }
 # kind of optim_step_launcher (POINTOPS2_OPTIM_*)
 OPTIM_KINDS = {"adamw": 0, "sgd": 1}

@@ -380,9 +380,19 @@ __global__ __launch_bounds__(CA_WAVES * 64) void cell_fwd_kernel(pointops2_cell_
 // 4 * NPA atomics (slot s = (lane >> 4) + 4 kk of pass t: key j0 + s * NPA + t - the NPA keys of a slot are consecutive dwords) are
 // requested together before the first pass: an id loaded where it is used costs a memory round trip per atomic, and from the second
 // one on that wait also covers the atomic before it.
-template <int NPA, typename T, bool PK>
-__device__ __forceinline__ void flush_key_grads(float *scr, const float4 (&acc)[NPA], rsrc_t rs_key, int j0, int nkc, float *__restrict__ grad,
+// DET (the deterministic launchers, cell_det.hip): no atomics and no key ids.  `grad` is a partial buffer [K, h, 16] and a lane stores
+// its own four floats of key slot kb + j0 + p * NPA + t (kb: the cell's first key slot): the four lanes of a slot write one 64-byte
+// row.  Every slot of every cell is written exactly once; cell_key_grads_reduce sums a point's slots in a fixed order.
+template <int NPA, typename T, bool PK, bool DET>
+__device__ __forceinline__ void flush_key_grads(float *scr, const float4 (&acc)[NPA], rsrc_t rs_key, int kb, int j0, int nkc, float *__restrict__ grad,
                                                 const LaneCtx<T, PK> &x) {
+    if constexpr (DET) {
+        float *row = grad + (size_t)(kb + j0 + x.p * NPA) * x.C + x.hoff;
+#pragma unroll
+        for (int t = 0; t < NPA; t++)
+            if (x.p * NPA + t < nkc) stg4(row + (size_t)t * x.C, acc[t]);
+        return;
+    }
     unsigned keys[4][NPA];
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) bload_words<NPA>(rs_key, (j0 + ((x.lane >> 4) + 4 * kk) * NPA) * 4, keys[kk]);  // (past the end: key 0, unused)
@@ -403,7 +413,7 @@ __device__ __forceinline__ void flush_key_grads(float *scr, const float4 (&acc)[
 }
 
 // sweep A: grad_attn = <go, v + Tv>, gs = p (grad_attn - <go, out>) stored, dV += p go
-template <int NPA, int TS, typename RT, typename T, bool PK>
+template <int NPA, int TS, typename RT, typename T, bool PK, bool DET>
 __device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T, PK> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_p, rsrc_t rs_g,
                                                  float *scr, const float *__restrict__ go, const float *__restrict__ out,
                                                  const RT *__restrict__ v, float *__restrict__ grad_v, int j0, int nkc) {
@@ -456,11 +466,11 @@ __device__ __forceinline__ void bwd_sweep_values(const LaneCtx<T, PK> &x, const 
         }
     }
     if (ct.nq > 0 && c == 0) bstore_floats<NPA>(rs_g, ((ct.nq - 1) * ct.nk + j0 + p * NPA) * 4, gs_pv, nvalid);
-    flush_key_grads<NPA, T, PK>(scr, dv4, cb.key, j0, nkc, grad_v, x);
+    flush_key_grads<NPA, T, PK, DET>(scr, dv4, cb.key, ct.kb, j0, nkc, grad_v, x);
 }
 
 // sweep B: dQ = sum gs (k + Tq), dK += gs (q + Tk)
-template <int NPA, int TS, typename RT, typename T, bool PK>
+template <int NPA, int TS, typename RT, typename T, bool PK, bool DET>
 __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T, PK> &x, const CellTask &ct, const CellBufs &cb, rsrc_t rs_g, float *scr,
                                                const RT *__restrict__ q, const RT *__restrict__ k, float *__restrict__ grad_q,
                                                float *__restrict__ grad_k, int ch, int j0, int nkc) {
@@ -525,10 +535,11 @@ __device__ __forceinline__ void bwd_sweep_keys(const LaneCtx<T, PK> &x, const Ce
         i_pv = i;
     }
     if (ct.nq > 0 && p == 0) store_dq(i_pv, tot_pv);
-    flush_key_grads<NPA, T, PK>(scr, dk4, cb.key, j0, nkc, grad_k, x);
+    flush_key_grads<NPA, T, PK, DET>(scr, dk4, cb.key, ct.kb, j0, nkc, grad_k, x);
 }
 
-template <int NP, int LCAP, typename RT, typename T, bool PK>
+// DET: grad_k / grad_v are the partial buffers [K, h, 16] of flush_key_grads (plain stores), not the gradients
+template <int NP, int LCAP, typename RT, typename T, bool PK, bool DET = false>
 __global__ __launch_bounds__(CA_WAVES_BWD * 64) void cell_bwd_kernel(pointops2_cell_plan pl, int h, int L, const float *__restrict__ go,
                                                                  const RT *__restrict__ q, const RT *__restrict__ k,
                                                                  const RT *__restrict__ v, int rs, float qscale, const float *__restrict__ out,
@@ -557,13 +568,13 @@ __global__ __launch_bounds__(CA_WAVES_BWD * 64) void cell_bwd_kernel(pointops2_c
         for (int ch = 0; ch < nch; ch++) {
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
-                bwd_sweep_values<decltype(tag)::value, TS, RT, T, PK>(x, ct, cb, rs_p, rs_g, scr, go, out, v, grad_v, j0, nkc);
+                bwd_sweep_values<decltype(tag)::value, TS, RT, T, PK, DET>(x, ct, cb, rs_p, rs_g, scr, go, out, v, grad_v, j0, nkc);
             });
         }
         for (int ch = 0; ch < nch; ch++) {
             const int j0 = ch * 16 * NP, nkc = min(16 * NP, ct.nk - j0);
             dispatch_passes<NP>((nkc + 15) >> 4, [&](auto tag) {
-                bwd_sweep_keys<decltype(tag)::value, TS, RT, T, PK>(x, ct, cb, rs_g, scr, q, k, grad_q, grad_k, ch, j0, nkc);
+                bwd_sweep_keys<decltype(tag)::value, TS, RT, T, PK, DET>(x, ct, cb, rs_g, scr, q, k, grad_q, grad_k, ch, j0, nkc);
             });
         }
     }
@@ -612,7 +623,9 @@ struct CellTableGeo {
 };
 
 // X: rows of XT, xs elements apart; SC: taken times xscale as the forward took q (round_rows)
-template <int TA, bool BYKEY, bool SC, typename XT>
+// DET (the deterministic launchers): grad_table is this body's partial buffer [gridDim.x, h, L * 48]; the workgroup stores its whole sum
+// image there, zeros included (a workgroup without work stores zeros), and cell_table_grads_reduce adds the rows in ascending order.
+template <int TA, bool BYKEY, bool SC, typename XT, bool DET = false>
 __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &pl, int h, int L, const float *__restrict__ wbuf, size_t plane,
                                                      const XT *__restrict__ X, int xs, float xscale, float *__restrict__ grad_table) {
     constexpr int D = 16;
@@ -759,24 +772,29 @@ __device__ __forceinline__ void cell_table_grad_body(const pointops2_cell_plan &
         }
         __syncthreads();
     }
-    for (int x = threadIdx.x; x < L * 48; x += CT_WAVES * 64) {
-        const float val = sum[x];
-        if (val != 0.f) unsafeAtomicAdd(grad_table + ((size_t)(x / 48) * h + head) * 48 + x % 48, val);
+    if constexpr (DET) {
+        float *dst = grad_table + ((size_t)blockIdx.x * h + head) * (size_t)(L * 48);
+        for (int x = threadIdx.x; x < L * 48; x += CT_WAVES * 64) dst[x] = sum[x];
+    } else {
+        for (int x = threadIdx.x; x < L * 48; x += CT_WAVES * 64) {
+            const float val = sum[x];
+            if (val != 0.f) unsafeAtomicAdd(grad_table + ((size_t)(x / 48) * h + head) * 48 + x % 48, val);
+        }
     }
 }
 
 // the three table gradients of a block as ONE grid (blockIdx.z: 0 = key side, the longest, first in dispatch order; 1 = query side;
 // 2 = value side): each of them alone is short of independent work on the small stages, together they overlap
-template <int TA, typename T, bool PK>
+template <int TA, typename T, bool PK, bool DET = false>
 __global__ __launch_bounds__(CT_WAVES * 64) void cell_table_grad3_kernel(pointops2_cell_plan pl, int h, int L, const float *__restrict__ gsbuf,
                                                                          const float *__restrict__ pbuf, size_t plane,
                                                                          const T *__restrict__ q, const T *__restrict__ k,
                                                                          const float *__restrict__ grad_out, float *__restrict__ gtq,
                                                                          float *__restrict__ gtk, float *__restrict__ gtv, int rs, float qscale) {
     const int xs = PK ? rs : h * 16;
-    if (blockIdx.z == 0) cell_table_grad_body<TA, true, false, T>(pl, h, L, gsbuf, plane, k, xs, 1.0f, gtk);
-    else if (blockIdx.z == 1) cell_table_grad_body<TA, false, PK, T>(pl, h, L, gsbuf, plane, q, xs, qscale, gtq);
-    else cell_table_grad_body<TA, false, false, float>(pl, h, L, pbuf, plane, grad_out, h * 16, 1.0f, gtv);
+    if (blockIdx.z == 0) cell_table_grad_body<TA, true, false, T, DET>(pl, h, L, gsbuf, plane, k, xs, 1.0f, gtk);
+    else if (blockIdx.z == 1) cell_table_grad_body<TA, false, PK, T, DET>(pl, h, L, gsbuf, plane, q, xs, qscale, gtq);
+    else cell_table_grad_body<TA, false, false, float, DET>(pl, h, L, pbuf, plane, grad_out, h * 16, 1.0f, gtv);
 }
 
 // What a launch refuses before anything else (nullptr: nothing), forward and backward in one place.  The texts are literals because
@@ -839,6 +857,54 @@ static void launch_cell_fwd(hipStream_t st, const pointops2_cell_plan *plan, int
     }
     if (variant == POINTOPS2_CELL_FWD_VALU80) launch_valu_fwd<80, RT, TT, PK>(st, plan, h, L, r, t, out, ml, pbuf);
     else launch_valu_fwd<160, RT, TT, PK>(st, plan, h, L, r, t, out, ml, pbuf);  // POINTOPS2_CELL_FWD_VALU160
+    check_launch();
+}
+
+// Rows of the table partials of a deterministic backward = grid.x of its table-gradient launch: one workgroup per CU of the device and
+// body, over all heads.  NOT usable_cus(): that follows the sampler launches still pending when the backward is enqueued, a matter of
+// host timing, and the grouping of the sums must not depend on it.
+static int cell_table_partial_rows(const pointops2_cell_plan *plan, int h) {
+    return max(1, min(max(1, num_cus() / max(h, 1)), div_up(plan->n_cells, CT_WAVES)));
+}
+
+// what a deterministic backward refuses on top of cell_refusal
+static const char *cell_det_refusal(const pointops2_cell_plan *plan, int h, int L, const CellDet &det) {
+    if (plan->task_step > 1 || plan->task_list != nullptr)
+        return "cell_attention deterministic backward: the plan is a share of the cells (task_step > 1 or a task_list)";
+    if (det.slot_offsets == nullptr || det.slot_order == nullptr || det.key_partials == nullptr || det.table_partials == nullptr)
+        return "cell_attention deterministic backward: slot_offsets, slot_order, key_partials and table_partials must not be NULL";
+    if (det.key_partial_floats < (size_t)2 * plan->n_keyslots * h * 16) return "cell_attention deterministic backward: key_partials holds fewer than 2 * K * h * 16 floats";
+    if (det.table_partial_floats < (size_t)3 * cell_table_partial_rows(plan, h) * h * L * 48)
+        return "cell_attention deterministic backward: table_partials holds fewer than 3 * pointops2_cell_table_partial_rows * h * L * 48 floats";
+    return nullptr;
+}
+
+// The deterministic launchers: the DET instances of the sweeps and the table bodies store partial sums (det.key_partials: dK [K, h, 16] then dV;
+// det.table_partials: [3 = q, k, v][rows][h][L * 48]) and two more launches (cell_det.hip) add them in a fixed order into g.k, g.v
+// and gt, which are fully written.
+template <typename RT, typename TT, bool PK>
+static void launch_cell_bwd_det(hipStream_t st, const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const CellRows<RT> &r,
+                                const float *out, const CellTables<TT> &t, const float *pbuf, float *gsbuf, const CellGrads &g, const CellGrads &gt,
+                                const CellDet &det) {
+    if (plan == nullptr || plan->n_points <= 0) return;
+    if (const char *why = cell_refusal(plan, hdim, L, true)) { set_error(why); return; }
+    if (const char *why = cell_det_refusal(plan, h, L, det)) { set_error(why); return; }
+    const size_t lds = TabGeo<80>::bytes(sizeof(TT)) + (size_t)CA_WAVES_BWD * 256 * sizeof(float);
+    allow_big_lds(cell_bwd_kernel<CA_NP_BWD, 80, RT, TT, PK, true>, lds);
+    const size_t plane = (size_t)plan->n_pairs, kplane = (size_t)plan->n_keyslots * h * 16;
+    float *dk = det.key_partials, *dv = det.key_partials + kplane;
+    hipLaunchKernelGGL((cell_bwd_kernel<CA_NP_BWD, 80, RT, TT, PK, true>), dim3(cell_grid_x(1, plan->n_cells, h, CA_WAVES_BWD), h), dim3(CA_WAVES_BWD * 64), lds,
+                       st, *plan, h, L, grad_out, r.q, r.k, r.v, r.rs, r.scale, out, t.q, t.k, t.v, pbuf, gsbuf, plane, g.q, dk, dv);
+    const int rows = cell_table_partial_rows(plan, h);
+    const size_t tplane = (size_t)rows * h * L * 48;
+    float *tq = det.table_partials, *tk = tq + tplane, *tv = tk + tplane;
+    const dim3 grid3(rows, h, 3), tblock(CT_WAVES * 64);
+    if (L <= 64) hipLaunchKernelGGL((cell_table_grad3_kernel<4, RT, PK, true>), grid3, tblock, CellTableGeo<4>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, r.q,
+                                    r.k, grad_out, tq, tk, tv, r.rs, r.scale);
+    else hipLaunchKernelGGL((cell_table_grad3_kernel<5, RT, PK, true>), grid3, tblock, CellTableGeo<5>::lds_bytes(), st, *plan, h, L, gsbuf, pbuf, plane, r.q, r.k,
+                            grad_out, tq, tk, tv, r.rs, r.scale);
+    cell_key_grads_reduce_launch(st, plan->n_points, h, det.slot_offsets, det.slot_order, dk, g.k, dv, g.v, PK ? r.rs : h * 16);
+    cell_table_grads_reduce_launch(st, rows, h, L, det.table_partials, gt.q, gt.k, gt.v);
     check_launch();
 }
 
@@ -933,6 +999,41 @@ void cell_attention_qkv_backward_launcher(const pointops2_cell_plan *plan, int h
         launch_cell_bwd<RT, float, true>(st, plan, h, hdim, L, grad_out, packed_rows<RT>(qkv, h, scale), out, {table_q, table_k, table_v}, pbuf, gsbuf,
                                          {grad_qkv, grad_qkv + h * 16, grad_qkv + 2 * h * 16}, {grad_table_q, grad_table_k, grad_table_v});
     })) set_error("cell_attention_qkv backward: unknown row_type");
+}
+
+// The three backward launchers without float atomics (include/pointops2_hip.h, "deterministic backward")
+int pointops2_cell_table_partial_rows(const pointops2_cell_plan *plan, int h) { return plan == nullptr ? 1 : cell_table_partial_rows(plan, h); }
+void cell_attention_det_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const float *q, const float *k,
+                                          const float *v, const float *out, const float *table_q, const float *table_k, const float *table_v,
+                                          const float *pbuf, float *gsbuf, float *grad_q, float *grad_k, float *grad_v, float *grad_table_q,
+                                          float *grad_table_k, float *grad_table_v, const int *slot_offsets, const int *slot_order, float *key_partials,
+                                          size_t key_partial_floats, float *table_partials, size_t table_partial_floats) {
+    launch_cell_bwd_det<float, float, false>(begin_launch().stream, plan, h, hdim, L, grad_out, {q, k, v, h * 16, 1.0f}, out, {table_q, table_k, table_v}, pbuf, gsbuf,
+                                             {grad_q, grad_k, grad_v}, {grad_table_q, grad_table_k, grad_table_v},
+                                             {slot_offsets, slot_order, key_partials, key_partial_floats, table_partials, table_partial_floats});
+}
+void cell_attention_det_backward_bf16_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const uint16_t *q,
+                                               const uint16_t *k, const uint16_t *v, const float *out, const uint16_t *table_q, const uint16_t *table_k,
+                                               const uint16_t *table_v, const float *pbuf, float *gsbuf, float *grad_q, float *grad_k, float *grad_v,
+                                               float *grad_table_q, float *grad_table_k, float *grad_table_v, const int *slot_offsets,
+                                               const int *slot_order, float *key_partials, size_t key_partial_floats, float *table_partials,
+                                               size_t table_partial_floats) {
+    launch_cell_bwd_det<bf16_t, bf16_t, false>(begin_launch().stream, plan, h, hdim, L, grad_out, {q, k, v, h * 16, 1.0f}, out, {table_q, table_k, table_v}, pbuf,
+                                               gsbuf, {grad_q, grad_k, grad_v}, {grad_table_q, grad_table_k, grad_table_v},
+                                               {slot_offsets, slot_order, key_partials, key_partial_floats, table_partials, table_partial_floats});
+}
+void cell_attention_qkv_det_backward_launcher(const pointops2_cell_plan *plan, int h, int hdim, int L, const float *grad_out, const void *qkv, int row_type,
+                                              float scale, const float *out, const float *table_q, const float *table_k, const float *table_v,
+                                              const float *pbuf, float *gsbuf, float *grad_qkv, float *grad_table_q, float *grad_table_k,
+                                              float *grad_table_v, const int *slot_offsets, const int *slot_order, float *key_partials,
+                                              size_t key_partial_floats, float *table_partials, size_t table_partial_floats) {
+    const hipStream_t st = begin_launch().stream;
+    if (!with_row_type(row_type, [&](auto tag) {
+        using RT = typename decltype(tag)::type;
+        launch_cell_bwd_det<RT, float, true>(st, plan, h, hdim, L, grad_out, packed_rows<RT>(qkv, h, scale), out, {table_q, table_k, table_v}, pbuf, gsbuf,
+                                             {grad_qkv, grad_qkv + h * 16, grad_qkv + 2 * h * 16}, {grad_table_q, grad_table_k, grad_table_v},
+                                             {slot_offsets, slot_order, key_partials, key_partial_floats, table_partials, table_partial_floats});
+    })) set_error("cell_attention_qkv deterministic backward: unknown row_type");
 }
 
 }  // extern "C"

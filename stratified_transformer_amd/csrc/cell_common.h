@@ -209,4 +209,19 @@ struct CellGrads {  // of the rows (the first point's row of each, laid out as t
 void cell_fwd_mfma_launch(hipStream_t st, int variant, const pointops2_cell_plan *plan, int h, int L, int row_type, bool packed, const CellRows<void> &rows,
                           const CellTables<float> &tabs, float *out, float *pbuf);
 
+// The extra operands of a deterministic backward (cell_attention_*det_backward_launcher): the key-major view of plan->cell_keys and the
+// two partial buffers with their sizes in floats
+struct CellDet {
+    const int *slot_offsets, *slot_order;
+    float *key_partials;
+    size_t key_partial_floats;
+    float *table_partials;
+    size_t table_partial_floats;
+};
+// cell_det.hip: the two sum passes behind the store passes of cell_attn.hip.  Keys: grad0 (and grad1 from partials1, unless NULL)
+// [n, .., h, 16] with rows row_stride floats apart; tables: partials [3 = q, k, v][rows][h][L * 48].  Fixed order, fully written.
+void cell_key_grads_reduce_launch(hipStream_t st, int n, int h, const int *slot_offsets, const int *slot_order, const float *partials0, float *grad0,
+                                  const float *partials1, float *grad1, int row_stride);
+void cell_table_grads_reduce_launch(hipStream_t st, int rows, int h, int L, const float *partials, float *gtq, float *gtk, float *gtv);
+
 }  // namespace p2

@@ -130,6 +130,48 @@ def _cell_backward_buffers(plan, pbuf, *accumulated):
     return gsbuf, [g.view(t.shape) for g, t in zip(acc.split([t.numel() for t in accumulated]), accumulated)]
 
 
+# The backward of cell_attention / cell_attention_qkv without float atomics (csrc/cell_det.hip): dK, dV and the table
+# gradients are stored as partial sums and added per destination in a fixed order, so two runs of one build on one device model give
+# the same bits.  What `deterministic=None` means at a call; the forward is the same kernel either way.
+DETERMINISTIC = False
+CELL_KEY_VIEWS = 0  # key-major views of a plan's key list built so far (tests: one per plan, not one per block)
+
+
+def _cell_key_view(plan):
+    """(slot_offsets [N + 1], slot_order [K]) of plan.cell_keys: per point its key slots, ascending.  Built once per plan."""
+    if plan.key_view is None:
+        global CELL_KEY_VIEWS
+        CELL_KEY_VIEWS += 1
+        K = plan.n_keyslots
+        rows = torch.arange(K + 1, dtype=torch.int32, device=plan.cell_keys.device)
+        offsets, order, _ = P._csc_build(rows, plan.cell_keys[:K], plan.n_points)
+        plan.key_view = (offsets, order)
+    return plan.key_view
+
+
+def _deterministic(flag, plan, name):
+    det = DETERMINISTIC if flag is None else bool(flag)
+    if det and plan.partial:
+        raise RuntimeError("%s: deterministic=True on a partial plan (CellPlan.share / with_tasks): the ranks' gradients are summed by an "
+                           "all-reduce whose order this mode does not fix" % name)
+    return det
+
+
+def cell_partial_buffers(plan, h, L, dev):
+    """The two workspaces of a deterministic backward, uninitialised: key partials [2, K, h, 16] (dK, dV per key slot) and table partials
+    [3, rows, h, L * 48] (an image of each table per workgroup), fp32."""
+    rows = int(_lib.lib().pointops2_cell_table_partial_rows(plan.c_arg(), int(h)))
+    f32 = dict(dtype=torch.float32, device=dev)
+    return torch.empty((2, max(plan.n_keyslots, 1), h, 16), **f32), torch.empty((3, rows, h, L * 48), **f32)
+
+
+def _det_args(plan, h, L, dev):
+    """the trailing arguments of the cell_attention_*det_backward launchers (and the tensors behind them, to be kept alive over the launch)"""
+    offsets, order = _cell_key_view(plan)
+    kp, tp = cell_partial_buffers(plan, h, L, dev)
+    return (ptr(offsets), ptr(order), ptr(kp), kp.numel(), ptr(tp), tp.numel()), (kp, tp)
+
+
 def _as_operand(dtype, *grads):
     """autograd wants a gradient of the operand's dtype; the kernels took the sums in fp32"""
     return grads if dtype == torch.float32 else tuple(g.to(dtype) for g in grads)
@@ -141,7 +183,7 @@ class CellAttention(Function):
     registers and takes the three table gradients from cell-ordered softmax weights / logit gradients."""
 
     @staticmethod
-    def forward(ctx, q, k, v, table_q, table_k, table_v, plan):
+    def forward(ctx, q, k, v, table_q, table_k, table_v, plan, det=False):
         N, h, hdim = q.shape
         L = table_q.shape[0]
         _cell_checks(plan, hdim, L, (N, k.shape[0], v.shape[0]), any(ctx.needs_input_grad[:6]))
@@ -153,7 +195,7 @@ class CellAttention(Function):
         out, ml, pbuf = _cell_forward_buffers(plan, N, h, q.device)
         _lib.call("cell_attention_forward_launcher" if st == torch.float32 else "cell_attention_forward_bf16_launcher", plan.c_arg(), h, hdim, L, ptr(q), ptr(k), ptr(v), ptr(table_q), ptr(table_k), ptr(table_v),
                   ptr(out), ptr(ml), ptr(pbuf), device=q.device)
-        ctx.plan = plan
+        ctx.plan, ctx.det = plan, det
         ctx.save_for_backward(q, k, v, table_q, table_k, table_v, out, pbuf)
         return out
 
@@ -165,19 +207,28 @@ class CellAttention(Function):
         L = table_q.shape[0]
         grad_out = grad_out.contiguous()
         _lib.check_tensors((grad_out, torch.float32, "grad_out"))
+        if ctx.det:  # every gradient is fully written: nothing to zero-fill
+            gsbuf = torch.empty_like(pbuf)
+            grad_q, grad_k, grad_v, gtq, gtk, gtv = (torch.empty(t.shape, dtype=torch.float32, device=q.device) for t in (q, k, v, table_q, table_k, table_v))
+            det_args, _keep = _det_args(plan, h, L, q.device)
+            _lib.call("cell_attention_det_backward_launcher" if q.dtype == torch.float32 else "cell_attention_det_backward_bf16_launcher", plan.c_arg(), h, hdim, L,
+                      ptr(grad_out), ptr(q), ptr(k), ptr(v), ptr(out), ptr(table_q), ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_q), ptr(grad_k),
+                      ptr(grad_v), ptr(gtq), ptr(gtk), ptr(gtv), *det_args, device=q.device)
+            return (*_as_operand(q.dtype, grad_q, grad_k, grad_v, gtq, gtk, gtv), None, None)
         grad_q = (torch.zeros if plan.partial else torch.empty)(q.shape, dtype=torch.float32, device=q.device)
         gsbuf, (grad_k, grad_v, gtq, gtk, gtv) = _cell_backward_buffers(plan, pbuf, k, v, table_q, table_k, table_v)
         _lib.call("cell_attention_backward_launcher" if q.dtype == torch.float32 else "cell_attention_backward_bf16_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(q), ptr(k), ptr(v), ptr(out), ptr(table_q),
                   ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_q), ptr(grad_k), ptr(grad_v), ptr(gtq), ptr(gtk), ptr(gtv),
                   device=q.device)
-        return (*_as_operand(q.dtype, grad_q, grad_k, grad_v, gtq, gtk, gtv), None)
+        return (*_as_operand(q.dtype, grad_q, grad_k, grad_v, gtq, gtk, gtv), None, None)
 
 
-def cell_attention(q, k, v, table_q, table_k, table_v, plan):
+def cell_attention(q, k, v, table_q, table_k, table_v, plan, deterministic=None):
     """q, k, v [N, h, 16] f32 (q already scaled, :181); tables [L, h, 16, 3]; plan = BlockIndex.cells of the block's
     pattern (index_build.stage_index_hip(..., cell_table_rows=L))  ->  [N, h, 16], same numbers as the five operators
-    up to the order of the sums."""
-    return CellAttention.apply(q, k, v, table_q, table_k, table_v, plan)
+    up to the order of the sums.  deterministic (None: fused.DETERMINISTIC): the backward without float atomics - the same gradient
+    bits from run to run on one device model, at the price of two partial buffers (cell_partial_buffers); not for a partial plan."""
+    return CellAttention.apply(q, k, v, table_q, table_k, table_v, plan, _deterministic(deterministic, plan, "cell_attention"))
 
 
 class CellAttentionQKV(Function):
@@ -186,7 +237,7 @@ class CellAttentionQKV(Function):
     Saved for the backward: qkv itself, the tables, out and pbuf - no [N, h, 16] copy of q, k or v."""
 
     @staticmethod
-    def forward(ctx, qkv, scale, table_q, table_k, table_v, plan):
+    def forward(ctx, qkv, scale, table_q, table_k, table_v, plan, det=False):
         if qkv.dim() != 4 or qkv.shape[1] != 3:
             raise RuntimeError("cell_attention_qkv: qkv must be [N, 3, h, 16], got %s" % (tuple(qkv.shape),))
         N, _, h, hdim = qkv.shape
@@ -200,7 +251,7 @@ class CellAttentionQKV(Function):
         out, ml, pbuf = _cell_forward_buffers(plan, N, h, qkv.device)
         _lib.call("cell_attention_qkv_forward_launcher", plan.c_arg(), h, hdim, L, ptr(qkv), _lib.ROW_TYPES[qkv.dtype], float(scale), ptr(table_q),
                   ptr(table_k), ptr(table_v), ptr(out), ptr(ml), ptr(pbuf), device=qkv.device)
-        ctx.plan, ctx.scale = plan, float(scale)
+        ctx.plan, ctx.scale, ctx.det = plan, float(scale), det
         ctx.save_for_backward(qkv, table_q, table_k, table_v, out, pbuf)
         return out
 
@@ -212,14 +263,23 @@ class CellAttentionQKV(Function):
         L = table_q.shape[0]
         grad_out = grad_out.contiguous()
         _lib.check_tensors((grad_out, torch.float32, "grad_out"))
+        if ctx.det:  # every gradient is fully written: nothing to zero-fill
+            gsbuf = torch.empty_like(pbuf)
+            grad_qkv, gtq, gtk, gtv = (torch.empty(t.shape, dtype=torch.float32, device=qkv.device) for t in (qkv, table_q, table_k, table_v))
+            det_args, _keep = _det_args(plan, h, L, qkv.device)
+            _lib.call("cell_attention_qkv_det_backward_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(qkv), _lib.ROW_TYPES[qkv.dtype], ctx.scale,
+                      ptr(out), ptr(table_q), ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_qkv), ptr(gtq), ptr(gtk), ptr(gtv), *det_args,
+                      device=qkv.device)
+            return (*_as_operand(qkv.dtype, grad_qkv), None, gtq, gtk, gtv, None, None)
         gsbuf, (grad_qkv, gtq, gtk, gtv) = _cell_backward_buffers(plan, pbuf, qkv, table_q, table_k, table_v)
         _lib.call("cell_attention_qkv_backward_launcher", plan.c_arg(), h, hdim, L, ptr(grad_out), ptr(qkv), _lib.ROW_TYPES[qkv.dtype], ctx.scale,
                   ptr(out), ptr(table_q), ptr(table_k), ptr(table_v), ptr(pbuf), ptr(gsbuf), ptr(grad_qkv), ptr(gtq), ptr(gtk), ptr(gtv), device=qkv.device)
-        return (*_as_operand(qkv.dtype, grad_qkv), None, gtq, gtk, gtv, None)
+        return (*_as_operand(qkv.dtype, grad_qkv), None, gtq, gtk, gtv, None, None)
 
 
-def cell_attention_qkv(qkv, scale, table_q, table_k, table_v, plan):
+def cell_attention_qkv(qkv, scale, table_q, table_k, table_v, plan, deterministic=None):
     """qkv [N, 3, h, 16] contiguous, f32 / f16 / bf16: the qkv Linear's output as it stands (`self.qkv(feats).view(N, 3, h, 16)`, under
     autocast too), q NOT yet scaled; scale: the model's `self.scale`; tables [L, h, 16, 3] f32; plan as for cell_attention
-    ->  [N, h, 16] f32: what cell_attention returns for (qkv[:, 0] * scale).float(), qkv[:, 1].float(), qkv[:, 2].float()."""
-    return CellAttentionQKV.apply(qkv, scale, table_q, table_k, table_v, plan)
+    ->  [N, h, 16] f32: what cell_attention returns for (qkv[:, 0] * scale).float(), qkv[:, 1].float(), qkv[:, 2].float().
+    deterministic: as for cell_attention."""
+    return CellAttentionQKV.apply(qkv, scale, table_q, table_k, table_v, plan, _deterministic(deterministic, plan, "cell_attention_qkv"))

@@ -231,6 +231,8 @@ class CellPlan:
     task_count: torch.Tensor = None
     task_first: int = 0            # this launch's share of the cells: cell_perm[task_first::task_step] (share(): one scene over ranks)
     task_step: int = 1
+    key_view: tuple = None         # (slot_offsets [N+1], slot_order [K]) i32: a point's key slots, ascending - built by the first
+                                   # deterministic backward on this plan (fused._cell_key_view), shared by every block it serves
 
     def c_arg(self):
         from ._lib import ptr

@@ -19,7 +19,8 @@ the UNMODIFIED model file; the modules' own parameters are used as they are (`qk
   * WindowAttention.forward computes qkv / scale / proj exactly as :180-182,212-215 and replaces :183-208 (three operators, the
     `+`, scatter_softmax, two range asserts) by ONE autograd function: `fused.cell_attention` on the plan when BasicLayer handed
     one over (d = 16, L <= 80 - every shipped config; under autocast `fused.cell_attention_qkv`, which reads the half qkv where
-    the Linear left it), else `fused.window_attention` on the pair list it was given (d = 16),
+    the Linear left it; `DETERMINISTIC_ATTENTION = True` runs their backward without float atomics, bitwise reproducible), else
+    `fused.window_attention` on the pair list it was given (d = 16),
     else the five operators in the reference's order.  Called on its own (no plan), it needs nothing but the reference's
     arguments.
 
@@ -80,6 +81,9 @@ POOLED_TRANSITION = False
 # pointops.residual_norm_stream when autocast is on with the stream's own dtype.  z is then rounded once per site from the fp32 sum, where
 # the original rounds DropPath's product first: the same tensor up to one rounding of the half type.
 HALF_STREAM = False
+# The cell attention of the installed WindowAttention forwards (both model files) with the deterministic backward of fused.cell_attention*:
+# no float atomics, the same gradient bits from run to run (csrc/cell_det.hip).  False: fused.DETERMINISTIC decides.
+DETERMINISTIC_ATTENTION = False
 STATS = {"layers": 0, "speculated": 0, "reruns": 0, "transitions_prefetched": 0}
 _CLOUDS = {}  # id(xyz) -> _Cloud
 _FLAG_HOST = {}  # device index -> ring of pinned bool [1] words (speculation checks)
@@ -178,18 +182,20 @@ def _attention(self, feats, index_0_offsets, index_1, n_max, rel_index):
     blk = getattr(self, "_sta_block", None)
     plan = getattr(blk, "cells", None) if blk is not None else None
     on_cells = plan is not None and d == 16 and L <= 80 and plan.table_rows == L and plan.n_points == N
+    # the switch on: the keyword is passed; off: the call is the one it always was (fused.DETERMINISTIC decides)
+    det = {"deterministic": True} if DETERMINISTIC_ATTENTION else {}
     qkv = self.qkv(feats)
     if on_cells and qkv.dtype in (torch.float16, torch.bfloat16):
         # autocast: the kernels read the half rows where the Linear left them, scale q as they load it (:181) and widen (:183):
         # no permute copy, no multiply, no casts, and the half qkv is what the backward keeps
-        x = fused.cell_attention_qkv(qkv.contiguous().view(N, 3, h, d), self.scale, tq, tk, tv, plan)
+        x = fused.cell_attention_qkv(qkv.contiguous().view(N, 3, h, d), self.scale, tq, tk, tv, plan, **det)
         return self.proj_drop(self.proj(x.view(N, C)))                                    # :212-215
     qkv = qkv.reshape(N, 3, h, d).permute(1, 0, 2, 3).contiguous()                       # :180
     query, key, value = qkv[0], qkv[1], qkv[2]
     query = (query * self.scale).float()                                                  # :182-183 (`.float()`: autocast)
     key, value = key.float(), value.float()
     if on_cells:
-        x = fused.cell_attention(query, key, value, tq, tk, tv, plan)
+        x = fused.cell_attention(query, key, value, tq, tk, tv, plan, **det)
     else:
         offs, i1 = index_0_offsets.int().contiguous(), index_1.int().contiguous()
         if blk is not None and blk.rel_idx is not None and blk.rel_idx.shape[0] == i1.shape[0]:
